@@ -2,14 +2,22 @@
 (Swin-S + BERT-base, 224 px, seq 80, MLM+ITM, bf16) on N MI355X GPUs.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 A step = forward + backward (+ RCCL gradient all-reduce) + AdamW over one
 synthetic batch that is already resident in HBM (B=32 per GPU: weak scaling).
-Rank 0 prints ONE JSON line with `roofline` (dominant kernel, timed live with
-HIP events on the launch stream) and `cpu_baseline` (the oracle timed on the
-host cores, N=1 only).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times exactly
+`--steps` steps and prints the headline (pairs/s, ms_per_step, per-block
+spread).  `--full` adds everything else: `roofline` (dominant kernels, timed
+with HIP events on the launch stream in a bracketed run of its own), the
+dense-rows and packed-rows variants, other configs, the one-rank RCCL arms
+and `cpu_baseline` (the oracle timed on the host cores, N=1 only).
+`--dump-outputs DIR` writes what one step of the timed path hands its caller
+from fixed inputs (a fresh replica of the benchmark's model, the same batch):
+the loss and seeded samples of the updated parameters and of the gradients.
 """
 import argparse
 import json
@@ -20,6 +28,7 @@ import time
 
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")     # before the HIP runtime starts (mvlt_amd/__init__.py says why)
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -74,6 +83,10 @@ def _cpu_threads():
         n = len(os.sched_getaffinity(0))
     except AttributeError:
         n = os.cpu_count() or 1
+    # a host that grants this job fewer cores than it shows says so through OMP_NUM_THREADS: more threads only slow the oracle down
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
     return max(1, min(n, 64))
 
 
@@ -211,6 +224,27 @@ def block_stats(per_gpu_batch, world):
                     "(rank 0; `value` itself is steps / wall time of the whole region, max over ranks)"}
 
 
+def dump_outputs(out_dir, model, loss, per_tensor=8192, seed=97531):
+    """What a step handed its caller, as .npy files in `out_dir`: `loss.npy` (float64 [1]), and
+    `params.npy` / `grads.npy` (float32): the updated f32 master parameters and this step's gradients, tensor after tensor
+    in named_parameters() order -- every element of a tensor with at most `per_tensor` of them, else `per_tensor` indices
+    drawn by one generator seeded with `seed` (the same indices in every run of the same model); a parameter without a
+    gradient this step (p.grad is None) contributes zeros.  546 tensors: ~7 MB per file."""
+    g = torch.Generator().manual_seed(seed)
+    params, grads = [], []
+    with torch.no_grad():
+        for _, p in model.named_parameters():
+            n = p.numel()
+            idx = None if n <= per_tensor else torch.randint(0, n, (per_tensor,), generator=g).sort().values.to(p.device)
+            pick = (lambda t: t.reshape(-1)) if idx is None else (lambda t: t.reshape(-1)[idx])
+            params.append(pick(p.detach()).float())
+            grads.append(torch.zeros_like(params[-1]) if p.grad is None else pick(p.grad).float())
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(out_dir, "loss.npy"), np.array([float(loss.item())], dtype=np.float64))
+        np.save(os.path.join(out_dir, "params.npy"), torch.cat(params).cpu().numpy())
+        np.save(os.path.join(out_dir, "grads.npy"), torch.cat(grads).cpu().numpy())
+
+
 def other_configs(M):
     """BASELINE configs #4 and #5 at their stated sizes, one GPU, reported as extra keys of the same line (the
     headline stays config #2).  #4: greedy report generation, Swin-S + BERT-base, B=32, max_length=150 (MIMIC-CXR
@@ -340,7 +374,8 @@ def roofline_entry(samples, name, traffic_key, every):
             "traffic_over_algorithmic": None if (algo is None or not traffic) else round(traffic / algo, 2),
             "launches": len(samples), "avg_launch_us": round(1e3 * ms / len(samples), 2),
             "flops": "executed: 2 M N K with the row count the kernels read on the device (ragged batches), not the dense bound",
-            "sampling": f"1 in {every} launches of the family inside the timed region, HIP events on the launch stream"}
+            "sampling": f"1 in {every} launches of the family inside a timed region of --steps steps right after the headline's, "
+                        "HIP events on the launch stream"}
 
 
 def main():
@@ -348,10 +383,18 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)      # >= 100 timed steps
     ap.add_argument("--warmup", type=int, default=20)     # ... after >= 20 warm-up steps
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: roofline brackets (a timed run of their own), dense-rows / packed-rows variants, "
+                         "other configs, one-rank RCCL arms, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write one step's loss and seeded samples of the updated parameters / gradients, from the benchmark's fixed "
+                         "initial state, as DIR/*.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-baseline-only", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the packed-rows / labelled-rows extra measurement")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the variants, other configs and RCCL arms")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.cpu_baseline_only:
         cpu_baseline_worker()
         return
@@ -391,26 +434,32 @@ def main():
     from mvlt_amd.ddp import GradReducer, seed_coin_flip
     from mvlt_amd.train import PretrainStep, synthetic_batch
 
-    torch.manual_seed(1234)                         # same random-init replica on every rank
-    cfg = M.MVLBertPretrainConfig()
-    cfg.ITM_task = True                             # BASELINE config: Pretrain (MLM+ITM)
-    # PRIMARY number = the reference's own call: model(image, caption_masked, caption_label, ITM_label)
-    # (modules/model.py:372) with the module defaults: the packing plan for the zero-padded caption tails and the
-    # labelled-rows-first MLM head are derived on the device from the ids / labels themselves (no new argument, no host
-    # sync; same loss and gradients as computing every row, which is reported beside it as value_dense_rows).
-    cfg.mlm_max_labels_per_sample = None
-    model = M.MVLBertForPretraining(cfg).cuda().train()
-    M.manual_seed(4321 + rank)                      # dropout stream differs per rank
-    seed_coin_flip(5678)                            # seq2seq/bidir flip identical on all ranks
     # MVLT_DDP_BF16=1: bf16-compressed gradient exchange (non-default; the reference-equivalent sum is f32)
     comm = torch.bfloat16 if os.environ.get("MVLT_DDP_BF16") == "1" else torch.float32
     bucket_mb = int(os.environ.get("MVLT_DDP_BUCKET_MB", "64"))
-    reducer = GradReducer(model, comm_dtype=comm, bucket_bytes=bucket_mb << 20) if use_dist else None
     # MVLT_DEFER_OPT_TAIL=1 (A/B switch, off by default): the AdamW sweep over BertLayers 1.. and the heads runs beside the NEXT
     # step's encoder forward (mvlt_amd/optim.py).  Measured 11.41 / 11.41 / 11.43 against 11.46 / 11.47 / 11.40 ms: inside the box's
     # noise -- the encoder forward gives back what the sweep gains (profiles/HISTORY.md, round 6)
     defer_tail = os.environ.get("MVLT_DEFER_OPT_TAIL", "0") == "1"
-    step = PretrainStep(model, reducer=reducer, world_size=world, defer_optimizer_tail=defer_tail)
+
+    def replica():
+        """(cfg, model, step) from fixed seeds: every call, in every run, starts from the same weights, optimizer state and
+        dropout / seq2seq-bidir streams."""
+        torch.manual_seed(1234)                         # same random-init replica on every rank
+        cfg = M.MVLBertPretrainConfig()
+        cfg.ITM_task = True                             # BASELINE config: Pretrain (MLM+ITM)
+        # PRIMARY number = the reference's own call: model(image, caption_masked, caption_label, ITM_label)
+        # (modules/model.py:372) with the module defaults: the packing plan for the zero-padded caption tails and the
+        # labelled-rows-first MLM head are derived on the device from the ids / labels themselves (no new argument, no host
+        # sync; same loss and gradients as computing every row, which is reported beside it as value_dense_rows).
+        cfg.mlm_max_labels_per_sample = None
+        model = M.MVLBertForPretraining(cfg).cuda().train()
+        M.manual_seed(4321 + rank)                      # dropout stream differs per rank
+        seed_coin_flip(5678)                            # seq2seq/bidir flip identical on all ranks
+        reducer = GradReducer(model, comm_dtype=comm, bucket_bytes=bucket_mb << 20) if use_dist else None
+        return cfg, model, PretrainStep(model, reducer=reducer, world_size=world, defer_optimizer_tail=defer_tail)
+
+    cfg, model, step = replica()
     lens = None
     if world > 1:
         # caption lengths of the GLOBAL batch (same draw on every rank), dealt to the ranks with equal sums: with packed rows a
@@ -423,29 +472,35 @@ def main():
 
     for _ in range(args.warmup):
         step(batch)
+    # the headline: exactly args.steps steps with nothing bracketed inside the region
+    elapsed, loss = timed_run(step, batch, args.steps, use_dist, dist)
+    blocks = block_stats(PER_GPU_BATCH, world)
+    loss_value = float(loss.item())
+
+    # --full, ROOFLINE: the same step for another args.steps steps with launches of the dominant families bracketed by HIP
+    # events; the brackets perturb the step (below), so the headline region above has none
     every = int(os.environ.get("MVLT_BENCH_SAMPLE", "4"))
     timer = KernelTimer(DOMINANT, every=every)
     native_samples = fam_samples = None
     # ~10 of ~280 launches per step (every bracket costs host time and a barrier packet on the stream); a PRIME period, so
     # the sample does not alias with the 4-6 products per layer (a period of 32 kept hitting the same product of every layer)
     fam_every = 29
-    if ops.NATIVE:          # the launches are issued by csrc/host.cpp: it brackets them itself (same method)
-        ops.host().timer_begin(0, every, 64 * args.steps)
-        ops.host().timer_begin(1, fam_every, 64 * args.steps)
-    else:
-        ops.GEMM_TIMER = timer
-    elapsed, loss = timed_run(step, batch, args.steps, use_dist, dist)
-    blocks = block_stats(PER_GPU_BATCH, world)
-    ops.GEMM_TIMER = None
-    if ops.NATIVE:
-        native_samples = ops.host().timer_collect(0)          # [(executed flops, ms)] -- the stream is idle: timed_run synchronised
-        fam_samples = ops.host().timer_collect(1)
-    loss_value = float(loss.item())
+    if args.full:
+        if ops.NATIVE:          # the launches are issued by csrc/host.cpp: it brackets them itself (same method)
+            ops.host().timer_begin(0, every, 64 * args.steps)
+            ops.host().timer_begin(1, fam_every, 64 * args.steps)
+        else:
+            ops.GEMM_TIMER = timer
+        timed_run(step, batch, args.steps, use_dist, dist)
+        ops.GEMM_TIMER = None
+        if ops.NATIVE:
+            native_samples = ops.host().timer_collect(0)          # [(executed flops, ms)] -- the stream is idle: timed_run synchronised
+            fam_samples = ops.host().timer_collect(1)
 
     # EXTRA 1: the same call with config.auto_pack_rows = False -- every zero-padded caption row is computed, i.e.
     # exactly the reference's work (the default plans the packing on the device from the ids themselves)
     dense = None
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         cfg.auto_pack_rows = False               # (also turns the labelled-rows-first MLM head off: all 80 rows per sample)
         for _ in range(max(2, args.warmup // 2)):
             step(batch)
@@ -461,7 +516,7 @@ def main():
     # EXTRA 2 (opt-in API, not reachable from the reference's unchanged caller): packed BERT rows via the added
     # text_lengths= argument + MLM head on the labelled rows only (config.mlm_max_labels_per_sample = 10)
     extra = None
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         cfg.mlm_max_labels_per_sample = 10
         for _ in range(max(2, args.warmup // 2)):
             step(batch_full)
@@ -476,17 +531,21 @@ def main():
                  "packed_step_tflops_per_gpu_executed": round(PER_GPU_BATCH * args.steps / e2 * gpp / 1e3, 2),
                  "packed_loss": round(float(l2.item()), 4)}
         cfg.mlm_max_labels_per_sample = None
+    # --dump-outputs: what the timed path computes from fixed inputs.  The last timed step's own inputs are not fixed: its
+    # parameters come out of W + N - 1 earlier updates, whose float-atomic gradient sums differ in the last bits from run to
+    # run, and training on one batch amplifies that (two runs at 100 / 20 steps: 0.4 % apart in the loss).  So a fresh
+    # replica takes one step through the same PretrainStep on the same batch, after everything above has been measured.
+    if args.dump_outputs:
+        del step, model
+        _, model, step = replica()
+        dump_loss = step(batch)
+        step.flush()
+        torch.cuda.synchronize()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, model, dump_loss)
     if rank == 0:
         pairs = PER_GPU_BATCH * world * args.steps
         value = pairs / elapsed
-        kr = timer.result()
-        roofline = roofline_entry(fam_samples, DOMINANT_NAME, "family", fam_every)
-        roofline_wgrad = roofline_entry(native_samples, WGRAD_NAME, "wgrad_group", every)
-        if roofline is None and kr is not None:          # ctypes host path (MVLT_NATIVE_HOST=0): only the grouped kernel is bracketed
-            roofline_wgrad = roofline_entry([(kr["tflops"] * 1e12 * kr["avg_us"] * 1e-6, kr["avg_us"] * 1e-3, 0.0)] * kr["launches"],
-                                            WGRAD_NAME, "wgrad_group", every)
-            roofline = roofline_wgrad
-        gpp_exec = packed_gflop_per_pair(batch_full)
         out = {"metric": "image-text pairs/sec pretrain step (Swin-S+BERT, 224px, seq80)", "value": round(value, 2),
                "unit": "pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True, "scaling": "weak",
@@ -510,19 +569,29 @@ def main():
                                             "ddp.GradReducer.label_sync), so the rank average equals the one-process step on the "
                                             "whole batch"),
                           "loss": round(loss_value, 4)},
-               # FLOPs the default path EXECUTES (padded caption rows and unlabelled MLM rows skipped) over the step time; the
-               # reference-equivalent 132.7 GFLOP/pair figure is quoted only for the run that executes it (value_dense_rows)
-               "executed_gflop_per_pair": round(gpp_exec, 1),
-               "step_tflops_per_gpu": round(value / world * gpp_exec / 1e3, 2),
-               "step_mfma_frac": round(value / world * gpp_exec / 1e3 / PEAK_BF16_TFLOPS, 4),
-               "roofline": roofline, "roofline_wgrad_group": roofline_wgrad, "blocks": blocks,
+               "blocks": blocks,
                # sticky error words of the fused W-MSA kernels' in-launch hand-off (a bounded wait that ran out): must be 0
                "wmsa2_sync_errors": ops.wmsa2_sync_errors()}
+        if args.full:
+            kr = timer.result()
+            roofline = roofline_entry(fam_samples, DOMINANT_NAME, "family", fam_every)
+            roofline_wgrad = roofline_entry(native_samples, WGRAD_NAME, "wgrad_group", every)
+            if roofline is None and kr is not None:      # ctypes host path (MVLT_NATIVE_HOST=0): only the grouped kernel is bracketed
+                roofline_wgrad = roofline_entry([(kr["tflops"] * 1e12 * kr["avg_us"] * 1e-6, kr["avg_us"] * 1e-3, 0.0)] * kr["launches"],
+                                                WGRAD_NAME, "wgrad_group", every)
+                roofline = roofline_wgrad
+            gpp_exec = packed_gflop_per_pair(batch_full)
+            # FLOPs the default path EXECUTES (padded caption rows and unlabelled MLM rows skipped) over the headline step time;
+            # the reference-equivalent 132.7 GFLOP/pair figure is quoted only for the run that executes it (value_dense_rows)
+            out.update({"executed_gflop_per_pair": round(gpp_exec, 1),
+                        "step_tflops_per_gpu": round(value / world * gpp_exec / 1e3, 2),
+                        "step_mfma_frac": round(value / world * gpp_exec / 1e3 / PEAK_BF16_TFLOPS, 4),
+                        "roofline": roofline, "roofline_wgrad_group": roofline_wgrad})
         if dense is not None:
             out.update(dense)
         if extra is not None:
             out.update(extra)
-        if world == 1 and not args.no_extra:
+        if args.full and world == 1 and not args.no_extra:
             out["other_configs"] = other_configs(M)
             if not use_dist:
                 out["other_configs"]["one_rank_rccl"] = one_rank_rccl()
@@ -530,7 +599,7 @@ def main():
                     o = out["other_configs"]["one_rank_rccl"]
                     o["plain_step_ms"] = out["ms_per_step"]
                     o["reducer_overhead_ms"] = round((o.get("ms_per_step_without_the_collective") or 0) - out["ms_per_step"], 3) if o.get("ms_per_step_without_the_collective") else None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         line = json.dumps(out)
         if real_stdout is not None:

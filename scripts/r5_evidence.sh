@@ -11,7 +11,7 @@ python3 $R/scripts/pmc.py --out $O/pmc --match gemm --passes sq1,fetch,write \
 echo pmc done
 python3 $R/scripts/pmc.py --out $O/pmc_rs --match rowstream --passes sq1,fetch,write -- python3 $R/bench.py --no-extra --no-cpu-baseline --steps 4 --warmup 2 > $O/r5_step_rowstream_pmc.txt 2>$O/pmc_rs.err
 echo pmc rowstream done
-rocprofv3 --kernel-trace --stats -d $O/trace -o b --output-format csv -- python3 $R/bench.py --no-extra --no-cpu-baseline --steps 30 --warmup 10 > $O/traced_bench.json 2>$O/trace.err
+rocprofv3 --kernel-trace --stats -d $O/trace -o b --output-format csv -- python3 $R/bench.py --full --no-extra --no-cpu-baseline --steps 30 --warmup 10 > $O/traced_bench.json 2>$O/trace.err
 echo trace done
 cd $R
 python scripts/roofline_vs_trace.py $(find $O/trace -name "*kernel_trace.csv" | head -1) $O/traced_bench.json 10 30 > $O/r5_roofline_vs_trace.txt 2>&1 || true
@@ -26,5 +26,5 @@ rocprofv3 --kernel-trace --stats -d $O/dec -o d --output-format csv -- python3 $
 cp $(find $O/dec -name "*kernel_stats.csv" | head -1) $O/r5_decode_kernel_stats.csv || true
 cd $R
 rm -rf $O/trace $O/step $O/dec $O/pmc $O/pmc_rs
-python bench.py > $O/r5_bench.json 2> $O/bench.err
+python bench.py --full > $O/r5_bench.json 2> $O/bench.err
 tail -c 600 $O/r5_bench.json

@@ -14,7 +14,7 @@ python3 $R/scripts/pmc.py --out $O/pmc --match gemm --passes sq1,fetch,write \
 echo pmc done
 python3 $R/scripts/pmc.py --out $O/pmc_rs --match rowstream --passes sq1,fetch,write -- python3 $R/bench.py --no-extra --no-cpu-baseline --steps 4 --warmup 2 > $O/r6_step_rowstream_pmc.txt 2>$O/pmc_rs.err
 echo pmc rowstream done
-rocprofv3 --kernel-trace --stats -d $O/trace -o b --output-format csv -- python3 $R/bench.py --no-extra --no-cpu-baseline --steps 30 --warmup 10 > $O/traced_bench.json 2>$O/trace.err
+rocprofv3 --kernel-trace --stats -d $O/trace -o b --output-format csv -- python3 $R/bench.py --full --no-extra --no-cpu-baseline --steps 30 --warmup 10 > $O/traced_bench.json 2>$O/trace.err
 echo trace done
 cd $R
 python scripts/roofline_vs_trace.py $(find $O/trace -name "*kernel_trace.csv" | head -1) $O/traced_bench.json 10 30 > $O/r6_roofline_vs_trace.txt 2>&1 || true
@@ -42,5 +42,5 @@ STAGE=2 SAVE=1 python3 $R/scripts/pmc.py --out $O/pmc_w2s --match wmsa2 --passes
 cd $R
 ONLY=fused python scripts/bench_wmsa.py > $O/r6_wmsa2_bench.txt 2>&1 || true
 rm -rf $O/dec $O/pmc_w0 $O/pmc_w1 $O/pmc_w2 $O/pmc_w2s
-python bench.py > $O/r6_bench.json 2> $O/bench.err
+python bench.py --full > $O/r6_bench.json 2> $O/bench.err
 tail -c 600 $O/r6_bench.json

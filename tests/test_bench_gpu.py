@@ -49,3 +49,39 @@ def test_bench_one_rank_over_rccl_with_and_without_the_collective():
         assert out["n_gpus"] == 1 and out["value"] > 0
         loss = out["config"]["loss"]
         assert loss == loss and 5.0 < loss < 15.0
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_same_outputs_every_run(tmp_path):
+    """A plain run (no --full): exactly --steps timed steps and the headline keys, none of the figures that --full adds;
+    --dump-outputs writes one step's loss and the seeded parameter / gradient samples from fixed inputs as float .npy files, and
+    two runs with the same arguments write the same outputs up to rounding (the gradients' float-atomic sums)."""
+    import numpy as np
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        env.pop(k, None)
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-2000:] + "\n" + r.stderr[-4000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["unit"] == "pairs/s" and out["dtype"] == "bf16"
+        assert out["higher_is_better"] is True and out["ms_per_step"] > 0
+        assert abs(out["value"] * out["ms_per_step"] - 32e3) < 1e-3 * 32e3          # B=32 pairs per step of ms_per_step
+        for k in ("roofline", "roofline_wgrad_group", "value_dense_rows", "value_packed", "other_configs", "cpu_baseline"):
+            assert k not in out, k
+        assert sorted(os.listdir(d)) == ["grads.npy", "loss.npy", "params.npy"]
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 << 20
+        loss, params, grads = (np.load(d / f) for f in ("loss.npy", "params.npy", "grads.npy"))
+        assert loss.dtype == np.float64 and loss.shape == (1,) and 5.0 < loss[0] < 15.0   # ~ln(30522) + ln 2 at random init
+        assert params.dtype == grads.dtype == np.float32 and params.shape == grads.shape and params.ndim == 1
+        assert np.isfinite(params).all() and np.isfinite(grads).all() and np.count_nonzero(grads) > grads.size // 10
+        dumps.append((loss, params, grads))
+    (la, pa, ga), (lb, pb, gb) = dumps
+    rel = lambda x, y: float(np.linalg.norm(x.astype(np.float64) - y) / np.linalg.norm(y.astype(np.float64)))
+    # measured between two runs: loss 9e-8, parameters 1e-11 and gradients 2e-11 apart (relative L2)
+    assert abs(la[0] - lb[0]) < 1e-5 * abs(lb[0]), (la, lb)
+    assert rel(pa, pb) < 1e-8 and rel(ga, gb) < 1e-6, (rel(pa, pb), rel(ga, gb))

@@ -130,8 +130,21 @@ def test_pretrain_loss_and_grads(golden, pretrain_sd, name):
     for k in keys:
         pn = k[len(f"gradnorm_{name}_"):]
         gr = pretrain_sd[pn].grad
+        if pn.endswith("key.bias"):
+            # softmax is invariant to it: the true gradient is 0, what is left is rounding noise, whose value depends on the
+            # host BLAS's summation order (MKL's AVX2 and AVX-512 kernels differ) -- both sides must be zero at rounding level
+            scale = pretrain_sd[pn.replace("key.bias", "query.weight")].grad.double().norm().item()
+            assert gr.double().norm().item() < 1e-5 * scale and g[k].item() < 1e-5 * scale, pn
+            continue
         assert abs(gr.double().norm().item() - g[k].item()) < 2e-3 * g[k].item() + 1e-9, pn
-        assert rel_err(gr.reshape(-1)[:64], g[f"grad_{name}_{pn}"]) < 2e-3, pn
+        # the first 64 entries, against the norm of a 64-entry slice of average size of the same tensor (`typical`).  A head
+        # below 5 % of it (test_model_gpu.py's threshold; on these rank-2 formula weights: the stage-2 qkv bias, 1e-8 of it,
+        # and e.g. a stage-2 fc1 head, 0.8 %) is what is left after cancellation, and its last digits follow the host BLAS's
+        # summation order (MKL / oneDNN / ATen kernels differ between CPUs): it is held to 2e-3 of `typical` instead of its own
+        got, want = gr.reshape(-1)[:64].double(), g[f"grad_{name}_{pn}"].double()
+        typical = g[k].item() * (want.numel() / gr.numel()) ** 0.5
+        scale = want.norm().item() if want.norm().item() > 0.05 * typical else typical
+        assert (got - want).norm().item() < 2e-3 * scale, pn
     head = "MLM_head_" + name
     rows = labels[labels >= 0][:4]
     assert rel_err(pretrain_sd[f"{head}.predictions.decoder.weight"].grad[rows, :32], g[f"grad_{name}_decoder_rows"]) < 2e-3
@@ -181,6 +194,11 @@ def test_tiny_all_outputs_and_grads(golden, specs, name):
             continue
         if f"gradnone_{name}_{k}" in g:
             assert v.grad is None, k
+        elif f"gradnorm_{name}_{k}" in g and k.endswith("key.bias"):
+            # the true gradient is 0 (softmax is shift invariant); its rounding noise depends on the host BLAS's summation order
+            scale = sd[k.replace("key.bias", "query.weight")].grad.double().norm().item()
+            assert v.grad.double().norm().item() < 1e-5 * scale and g[f"gradnorm_{name}_{k}"].item() < 1e-5 * scale, k
+            n_checked += 1
         elif f"gradnorm_{name}_{k}" in g:
             ref = g[f"gradnorm_{name}_{k}"].item()
             assert abs(v.grad.double().norm().item() - ref) < 1e-3 * ref + 1e-10, k
