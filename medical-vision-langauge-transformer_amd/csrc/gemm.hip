@@ -158,8 +158,13 @@ MVLT_DEV void gemm_body(const GemmDev& p_in, const int bx, const int by, const i
     // the next tile's global loads are in flight in registers while this tile is multiplied.
     Vec ra[GA::PER_THREAD], rb[GB::PER_THREAD];
     const int nkt = (ke - ks + GA::BKE - 1) / GA::BKE;
-    // number of k-tiles that lie fully inside [ks, ke) and can use unpredicated vector loads
-    const int nfast = (p.a_vec && p.b_vec && (AK || p.M >= 1) ) ? (ke - ks) / GA::BKE : 0;
+    // number of k-tiles that lie fully inside [ks, ke) and can use unpredicated vector loads.  Not for a k-major operand
+    // whose extent (M / N) ends inside a 16-byte chunk behind a padded stride (the MLM decoder's weight gradient: M = 30522,
+    // lda = 30528): FastLoader clamps that chunk back inside the extent, which loads other columns into its place
+    // (wrong output rows 30520, 30521); the predicated loads below zero its tail instead.  Only the last row / column tile
+    // holds that chunk: the other workgroups keep the fast loop.
+    const bool ragged = (AK && p.M % GA::E != 0 && m0 + BM > p.M) || (BK_ && p.N % GB::E != 0 && n0 + BN > p.N);
+    const int nfast = (p.a_vec && p.b_vec && !ragged) ? (ke - ks) / GA::BKE : 0;
     FastLoader<T, BM, AK> la;
     FastLoader<T, BN, BK_> lb;
     la.init(A, p.lda, m0, p.M, ks);

@@ -445,6 +445,46 @@ def test_gemm_argmax_fused(ops, dt, M, N, K):
     assert (idx2 == 2).all()
 
 
+@pytest.mark.parametrize("dt", DT)
+@pytest.mark.parametrize("M", [1, 16, 17, 33, 48, 49, 64])
+def test_gemm_argmax_row_buckets(ops, dt, M):
+    """gemm_argmax128_kernel<T, NRT> for every row bucket (NRT = 1..4 by M <= 16 / 32 / 48 / 64, partly filled last
+    16-row group) on the decoder shape, with A strided as hidden[:, -1] (lda > K): against the float64 argmax with the
+    near-tie rule of test_gemm_argmax_fused.  Then a maximum in the last, partial 16-column block, and an exact tie
+    between columns of two different workgroups (128 columns each): the first index wins."""
+    N, K = 30522, 768
+    hidden = rnd((M, 3, K), dt, 1, 0.5)
+    a = hidden[:, -1]
+    assert a.stride(0) == 3 * K
+    w, bias = rnd((N, K), dt, 2, 0.5), rnd((N,), torch.float32, 3)
+    idx, val = ops.gemm_argmax(a, w, bias)
+    ref = a.double() @ w.double().t() + bias.double()
+    rv, ri = ref.max(-1)
+    rt = 2e-5 if dt == torch.float32 else 1e-3
+    assert idx.shape == (M,) and int(idx.min()) >= 0 and int(idx.max()) < N
+    assert torch.allclose(val.double(), rv, rtol=rt, atol=1e-4)
+    assert torch.allclose(ref.gather(1, idx[:, None]).squeeze(1), rv, rtol=rt, atol=1e-4)
+    assert (idx == ri).double().mean() > 0.9
+    # every row's maximum inside the last, partial block (columns 30512 .. 30521): +1e4 on those ten biases
+    b2 = bias.clone()
+    b2[N - 10:] += 1e4
+    i2, v2 = ops.gemm_argmax(a, w, b2)
+    ref2 = ref.clone()
+    ref2[:, N - 10:] += 1e4
+    rv2 = ref2.max(-1).values
+    assert bool((i2 >= N - 10).all()), i2.tolist()
+    assert torch.allclose(ref2.gather(1, i2[:, None]).squeeze(1), rv2, rtol=rt, atol=1e-4)
+    assert torch.allclose(v2.double(), rv2, rtol=rt, atol=1e-4)
+    # exact tie across workgroups: columns 200 (workgroup 1) and 30000 (workgroup 234), and 30520 in the partial block
+    w3 = w.clone()
+    w3[30000] = w3[200]
+    w3[30520] = w3[200]
+    b3 = bias.clone()
+    b3[200] = b3[30000] = b3[30520] = 1e4
+    i3, _ = ops.gemm_argmax(a, w3, b3)
+    assert bool((i3 == 200).all()), i3.tolist()
+
+
 def test_gemm_bad_args(ops):
     A = torch.zeros(4, 4, device="cuda")
     with pytest.raises(AssertionError):
