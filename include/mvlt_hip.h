@@ -36,7 +36,7 @@ enum { MVLT_OK = 0, MVLT_ERR_ARG = -1, MVLT_ERR_LAUNCH = -2, MVLT_ERR_UNSUPPORTE
  * signature; a binding compiles / hard-codes the value it was written against and compares it with what the
  * loaded library returns.  mvlt_sizeof(MVLT_STRUCT_*) lets a binding that mirrors the structs by hand (ctypes,
  * cgo, JNI) prove that its mirror has the size the library was compiled with (0 for an unknown id). */
-#define MVLT_ABI_VERSION 8
+#define MVLT_ABI_VERSION 9
 int mvlt_version(void);            /* MVLT_ABI_VERSION of the loaded library */
 const char* mvlt_arch(void);       /* "gfx950" */
 enum { MVLT_STRUCT_GEMM = 0, MVLT_STRUCT_LAYERNORM = 1, MVLT_STRUCT_LAYERNORM_BWD = 2, MVLT_STRUCT_LN_REDUCE_ITEM = 3,
@@ -236,7 +236,9 @@ typedef struct MvltAttn {
     /* packed rows (optional, MVLBert modes): sequence s occupies rows [row_start[s], row_start[s]+seq_len[s])
      * of qkv/out/dout/dqkv, seq_len[s] <= L; trailing zero-padded caption positions are simply absent
      * (they are masked keys in BIDIR mode and lie above the causal diagonal in SEQ2SEQ mode, so no kept
-     * row ever reads them).  lse / delta_ws keep the [nseq,nH,L] layout.  NULL = dense [nseq*L] rows. */
+     * row ever reads them).  lse / delta_ws keep the [nseq,nH,L] layout.  NULL = dense [nseq*L] rows.
+     * Rows outside every sequence are neither read (qkv / dout) nor written (out / dqkv), and neither are the lse
+     * entries at q >= seq_len[s]. */
     const int32_t* row_start; const int32_t* seq_len;
     /* backward only, MVLT_ATTN_SWIN only (optional): the output projection's dgrad inside the launch.  When non-NULL, `dout`
      * is the gradient of the PROJECTION's output ([nseq*L, nH*hd], window order) and dout_weight the projection weight
@@ -257,6 +259,29 @@ int mvlt_attn_bwd(const MvltAttn* p, void* stream);   /* delta_ws: f32 [nseq,nH,
  * BertLayer / Swin block (modeling_bert.py:282-293 backward; visual_feature_extractor.py:224-254 backward): the caller
  * then hipStreamWaitEvent()s on it.  Nothing is recorded when the call fails. */
 int mvlt_attn_bwd_ev(const MvltAttn* p, void* stream, void* event);
+/* The kernel mvlt_attn_fwd (bwd = 0) / mvlt_attn_bwd (bwd != 0) would launch for *p, without launching anything:
+ * an MvltAttnRoute, or MVLT_ERR_ARG when the call itself would answer that.  For tests that must know which kernel they
+ * check; the launch takes its route from the same function. */
+enum MvltAttnRoute {
+    MVLT_ATTN_ROUTE_UNSUPPORTED = 0,       /* the call answers MVLT_ERR_UNSUPPORTED */
+    MVLT_ATTN_ROUTE_SWIN_FWD = 1,          /* attn_fwd_kernel<T, 32, 4, SWIN> */
+    MVLT_ATTN_ROUTE_BERT_FWD_KT5 = 2,      /* attn_fwd_kernel<T, 64, KT>: L <= 80 / 144 / 208 */
+    MVLT_ATTN_ROUTE_BERT_FWD_KT9 = 3,
+    MVLT_ATTN_ROUTE_BERT_FWD_KT13 = 4,
+    MVLT_ATTN_ROUTE_SWIN_BWD_KS0 = 5,      /* swin_attn_bwd2_kernel (scores once; bf16, no dropout, shift 0 / 3) */
+    MVLT_ATTN_ROUTE_SWIN_BWD_KS3 = 6,      /* ... with dout_weight, 3 / 6 / 12 heads */
+    MVLT_ATTN_ROUTE_SWIN_BWD_KS6 = 7,
+    MVLT_ATTN_ROUTE_SWIN_BWD_KS12 = 8,
+    MVLT_ATTN_ROUTE_SWIN_BWD = 9,          /* attn_bwd_kernel<T, 32, 4, SWIN> (f32, dropout, other shifts) */
+    MVLT_ATTN_ROUTE_BERT_BWD2_NW5 = 10,    /* bert_attn_bwd2_kernel, one launch: bf16, L <= 160 (5 waves) / 192 (6 waves) */
+    MVLT_ATTN_ROUTE_BERT_BWD2_NW6 = 11,
+    MVLT_ATTN_ROUTE_BERT_BWD_SPLIT_KT5 = 12,   /* attn_bwd_split_kernel, two launches through delta_ws */
+    MVLT_ATTN_ROUTE_BERT_BWD_SPLIT_KT9 = 13,
+    MVLT_ATTN_ROUTE_BERT_BWD_SPLIT_KT13 = 14,
+    MVLT_ATTN_ROUTE_BERT_BWD_KT5 = 15,     /* attn_bwd_kernel<T, 64, KT>: no delta_ws, L <= 144 */
+    MVLT_ATTN_ROUTE_BERT_BWD_KT9 = 16
+};
+int mvlt_attn_route(const MvltAttn* p, int bwd);
 
 /* ------------------------------------------------------------------ fused Swin (S)W-MSA (SURVEY.md 8b `swin_wmsa`)
  * The attention half of SwinTransformerBlock.forward in ONE launch (visual_feature_extractor.py:356-384 around

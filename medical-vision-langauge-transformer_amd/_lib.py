@@ -11,13 +11,17 @@ LIB_PATH = os.path.join(_HERE, "libmvlt_hip.so")
 
 F32, BF16 = 0, 1
 OK = 0
-ABI_VERSION = 8          # == MVLT_ABI_VERSION of the include/mvlt_hip.h these mirrors were written against
+ABI_VERSION = 9          # == MVLT_ABI_VERSION of the include/mvlt_hip.h these mirrors were written against
 ERRORS = {-1: "MVLT_ERR_ARG", -2: "MVLT_ERR_LAUNCH", -3: "MVLT_ERR_UNSUPPORTED"}
 
 EPI_BIAS, EPI_GELU, EPI_SAVE_PRE, EPI_DROPOUT = 1, 2, 4, 8
 EPI_ROWSCALE, EPI_RESIDUAL, EPI_ROWMAP, EPI_MUL_GELU_GRAD = 16, 32, 64, 128
 EPI_OUT_F32, EPI_ACCUM = 256, 512
 ATTN_SWIN, ATTN_BIDIR, ATTN_SEQ2SEQ = 0, 1, 2
+# enum MvltAttnRoute (mvlt_attn_route)
+ATTN_ROUTES = ("UNSUPPORTED", "SWIN_FWD", "BERT_FWD_KT5", "BERT_FWD_KT9", "BERT_FWD_KT13", "SWIN_BWD_KS0", "SWIN_BWD_KS3",
+               "SWIN_BWD_KS6", "SWIN_BWD_KS12", "SWIN_BWD", "BERT_BWD2_NW5", "BERT_BWD2_NW6", "BERT_BWD_SPLIT_KT5",
+               "BERT_BWD_SPLIT_KT9", "BERT_BWD_SPLIT_KT13", "BERT_BWD_KT5", "BERT_BWD_KT9")
 
 vp, i32, i64, u64, u32, f32, sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_uint32, C.c_float, C.c_size_t
 
@@ -144,6 +148,7 @@ SYMBOLS = {
     "mvlt_attn_fwd": (i32, [C.POINTER(MvltAttn), vp]),
     "mvlt_attn_bwd": (i32, [C.POINTER(MvltAttn), vp]),
     "mvlt_attn_bwd_ev": (i32, [C.POINTER(MvltAttn), vp, vp]),
+    "mvlt_attn_route": (i32, [C.POINTER(MvltAttn), i32]),
     "mvlt_swin_wmsa_supported": (i32, [i32, i32, i32]),
     "mvlt_swin_wmsa_fwd": (i32, [C.POINTER(MvltSwinWmsa), vp]),
     "mvlt_swin_wmsa_bwd": (i32, [C.POINTER(MvltSwinWmsa), vp]),

@@ -1369,35 +1369,73 @@ static int launch_swin_bwd2(const AttnDev& d, hipStream_t s) {
     return MVLT_OK;
 }
 
+// Which kernel a call takes (enum MvltAttnRoute): a pure function of the call's arguments, shared by the launch below
+// and by mvlt_attn_route, so a test can assert the route it means to check.  d.NT / rows_alloc / ld are set (geometry).
 template <typename T>
-int dispatch(AttnDev d, bool bwd, int dtype, hipStream_t s) {
+void geometry(AttnDev& d) {
     constexpr int TPB = Tok<T>::TPB;
     d.NT = ceil_div(d.L, 16);
     d.rows_alloc = ceil_div(d.NT, TPB) * TPB * 16;
     d.ld = d.hd + (sizeof(T) == 2 ? 8 : 4);
+}
+template <typename T>
+int attn_route(const AttnDev& d, bool bwd) {
+    constexpr bool BF = sizeof(T) == 2;
+    constexpr int dtype = BF ? MVLT_BF16 : MVLT_F32;
+    constexpr size_t SMEM_MAX = 160 * 1024;
     if (d.mode == MVLT_ATTN_SWIN) {
-        if (d.hd != 32 || d.L != 49) return MVLT_ERR_UNSUPPORTED;
-        if (bwd && sizeof(T) == 2 && d.drop_thresh == 0 && swin_bwd_form() && (d.shift == 0 || d.shift == 3) &&
-            (double)d.nseq * 49 * 3 * d.nH * 32 * 2 < 2147483648.0) return launch_swin_bwd2(d, s);     // buffer-store range check: < 2 GB
-        if (d.dw) return MVLT_ERR_UNSUPPORTED;          // the projection dgrad only rides on the scores-once kernel
-        return launch<T, 32, 4, true>(d, bwd, dtype, s);
+        if (d.hd != 32 || d.L != 49) return MVLT_ATTN_ROUTE_UNSUPPORTED;
+        if (bwd && BF && d.drop_thresh == 0 && swin_bwd_form() && (d.shift == 0 || d.shift == 3) &&
+            (double)d.nseq * 49 * 3 * d.nH * 32 * 2 < 2147483648.0) {                  // buffer-store range check: < 2 GB
+            if (!d.dw) return MVLT_ATTN_ROUTE_SWIN_BWD_KS0;
+            if (d.nH == 3) return MVLT_ATTN_ROUTE_SWIN_BWD_KS3;
+            if (d.nH == 6) return MVLT_ATTN_ROUTE_SWIN_BWD_KS6;
+            if (d.nH == 12) return MVLT_ATTN_ROUTE_SWIN_BWD_KS12;
+            return MVLT_ATTN_ROUTE_UNSUPPORTED;
+        }
+        if (d.dw) return MVLT_ATTN_ROUTE_UNSUPPORTED;        // the projection dgrad only rides on the scores-once kernel
+        if (smem_bytes(dtype, d.rows_alloc, d.ld, bwd, true) > SMEM_MAX) return MVLT_ATTN_ROUTE_UNSUPPORTED;
+        return bwd ? MVLT_ATTN_ROUTE_SWIN_BWD : MVLT_ATTN_ROUTE_SWIN_FWD;
     }
-    if (d.hd != 64) return MVLT_ERR_UNSUPPORTED;
-    if (bwd && sizeof(T) == 2 && d.NT <= 10 && bert_bwd_form()) return launch_bert_bwd2<5>(d, s);
-    if (bwd && sizeof(T) == 2 && d.NT <= 12 && bert_bwd_form()) return launch_bert_bwd2<6>(d, s);          // up to 192 rows (config #5)
+    if (d.hd != 64) return MVLT_ATTN_ROUTE_UNSUPPORTED;
+    if (bwd && BF && d.NT <= 10 && bert_bwd_form()) return MVLT_ATTN_ROUTE_BERT_BWD2_NW5;
+    if (bwd && BF && d.NT <= 12 && bert_bwd_form()) return MVLT_ATTN_ROUTE_BERT_BWD2_NW6;     // up to 192 rows (config #5)
     if (bwd && d.delta_ws) {           // two-launch backward (dQ+delta, then dK/dV): 2 workgroups per CU
-        if (d.NT <= 5) return launch_split<T, 64, 5>(d, dtype, s);
-        if (d.NT <= 9) return launch_split<T, 64, 9>(d, dtype, s);
-        if (d.NT <= 13) return launch_split<T, 64, 13>(d, dtype, s);      // seq 128 (L = 179, BASELINE config #5)
-        return MVLT_ERR_UNSUPPORTED;
+        if (d.NT > 13 || smem_bytes_split(dtype, d.rows_alloc, d.ld) > SMEM_MAX) return MVLT_ATTN_ROUTE_UNSUPPORTED;
+        return d.NT <= 5 ? MVLT_ATTN_ROUTE_BERT_BWD_SPLIT_KT5 : d.NT <= 9 ? MVLT_ATTN_ROUTE_BERT_BWD_SPLIT_KT9
+                                                                           : MVLT_ATTN_ROUTE_BERT_BWD_SPLIT_KT13;  // seq 128 (L = 179)
     }
-    if (d.NT <= 5) return launch<T, 64, 5, false>(d, bwd, dtype, s);
-    if (d.NT <= 9) return launch<T, 64, 9, false>(d, bwd, dtype, s);
-    if (d.NT <= 13 && !bwd) return launch<T, 64, 13, false>(d, bwd, dtype, s);
-    return MVLT_ERR_UNSUPPORTED;
+    if (d.NT > (bwd ? 9 : 13) || smem_bytes(dtype, d.rows_alloc, d.ld, bwd) > SMEM_MAX) return MVLT_ATTN_ROUTE_UNSUPPORTED;
+    if (bwd) return d.NT <= 5 ? MVLT_ATTN_ROUTE_BERT_BWD_KT5 : MVLT_ATTN_ROUTE_BERT_BWD_KT9;
+    return d.NT <= 5 ? MVLT_ATTN_ROUTE_BERT_FWD_KT5 : d.NT <= 9 ? MVLT_ATTN_ROUTE_BERT_FWD_KT9 : MVLT_ATTN_ROUTE_BERT_FWD_KT13;
 }
 
-int run(const MvltAttn* p, bool bwd, void* stream) {
+template <typename T>
+int dispatch(AttnDev d, bool bwd, int dtype, hipStream_t s) {
+    geometry<T>(d);
+    switch (attn_route<T>(d, bwd)) {
+    case MVLT_ATTN_ROUTE_SWIN_FWD:
+    case MVLT_ATTN_ROUTE_SWIN_BWD: return launch<T, 32, 4, true>(d, bwd, dtype, s);
+    case MVLT_ATTN_ROUTE_SWIN_BWD_KS0:
+    case MVLT_ATTN_ROUTE_SWIN_BWD_KS3:
+    case MVLT_ATTN_ROUTE_SWIN_BWD_KS6:
+    case MVLT_ATTN_ROUTE_SWIN_BWD_KS12: return launch_swin_bwd2(d, s);
+    case MVLT_ATTN_ROUTE_BERT_FWD_KT5:
+    case MVLT_ATTN_ROUTE_BERT_BWD_KT5: return launch<T, 64, 5, false>(d, bwd, dtype, s);
+    case MVLT_ATTN_ROUTE_BERT_FWD_KT9:
+    case MVLT_ATTN_ROUTE_BERT_BWD_KT9: return launch<T, 64, 9, false>(d, bwd, dtype, s);
+    case MVLT_ATTN_ROUTE_BERT_FWD_KT13: return launch<T, 64, 13, false>(d, false, dtype, s);
+    case MVLT_ATTN_ROUTE_BERT_BWD2_NW5: return launch_bert_bwd2<5>(d, s);
+    case MVLT_ATTN_ROUTE_BERT_BWD2_NW6: return launch_bert_bwd2<6>(d, s);
+    case MVLT_ATTN_ROUTE_BERT_BWD_SPLIT_KT5: return launch_split<T, 64, 5>(d, dtype, s);
+    case MVLT_ATTN_ROUTE_BERT_BWD_SPLIT_KT9: return launch_split<T, 64, 9>(d, dtype, s);
+    case MVLT_ATTN_ROUTE_BERT_BWD_SPLIT_KT13: return launch_split<T, 64, 13>(d, dtype, s);
+    default: return MVLT_ERR_UNSUPPORTED;
+    }
+}
+
+// argument checks and the device-side view of a call (MVLT_OK, or the error the call answers)
+int prepare(const MvltAttn* p, bool bwd, AttnDev& d) {
     MVLT_CHECK(p && p->qkv && p->out, MVLT_ERR_ARG);
     MVLT_CHECK(p->nseq > 0 && p->L > 0 && p->nH > 0, MVLT_ERR_ARG);
     MVLT_CHECK(aligned16(p->qkv) && aligned16(p->out), MVLT_ERR_ARG);
@@ -1409,7 +1447,7 @@ int run(const MvltAttn* p, bool bwd, void* stream) {
     MVLT_CHECK(p->dropout_p >= 0.f && p->dropout_p < 1.f, MVLT_ERR_ARG);
     MVLT_CHECK((double)p->nseq * p->nH * p->L * p->L < 4294967296.0 || p->dropout_p == 0.f, MVLT_ERR_ARG);
     if (bwd) MVLT_CHECK(p->dout && p->dqkv && p->lse && aligned16(p->dout) && aligned16(p->dqkv), MVLT_ERR_ARG);
-    AttnDev d{};
+    d = AttnDev{};
     d.mode = p->mode; d.nseq = p->nseq; d.L = p->L; d.nH = p->nH; d.hd = p->hd;
     d.qkv = p->qkv; d.out = p->out; d.lse = p->lse; d.scale = p->scale;
     d.bias_table = p->bias_table; d.nW = p->nW; d.res = p->win_res; d.shift = p->shift;
@@ -1428,16 +1466,34 @@ int run(const MvltAttn* p, bool bwd, void* stream) {
     MVLT_CHECK((p->row_start == nullptr) == (p->seq_len == nullptr), MVLT_ERR_ARG);
     MVLT_CHECK(p->row_start == nullptr || p->mode != MVLT_ATTN_SWIN, MVLT_ERR_ARG);
     d.row_start = p->row_start; d.seq_len = p->seq_len;
+    return MVLT_OK;
+}
+
+int run(const MvltAttn* p, bool bwd, void* stream) {
+    AttnDev d{};
+    const int rc = prepare(p, bwd, d);
+    if (rc != MVLT_OK) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (p->dtype == MVLT_F32) return dispatch<float>(d, bwd, MVLT_F32, s);
     if (p->dtype == MVLT_BF16) return dispatch<bf16_t>(d, bwd, MVLT_BF16, s);
     return MVLT_ERR_UNSUPPORTED;
 }
 
+int route(const MvltAttn* p, bool bwd) {
+    AttnDev d{};
+    const int rc = prepare(p, bwd, d);
+    if (rc == MVLT_ERR_UNSUPPORTED) return MVLT_ATTN_ROUTE_UNSUPPORTED;
+    if (rc != MVLT_OK) return rc;
+    if (p->dtype == MVLT_F32) { geometry<float>(d); return attn_route<float>(d, bwd); }
+    if (p->dtype == MVLT_BF16) { geometry<bf16_t>(d); return attn_route<bf16_t>(d, bwd); }
+    return MVLT_ATTN_ROUTE_UNSUPPORTED;
+}
+
 }  // namespace
 
 extern "C" int mvlt_attn_fwd(const MvltAttn* p, void* stream) { return run(p, false, stream); }
 extern "C" int mvlt_attn_bwd(const MvltAttn* p, void* stream) { return run(p, true, stream); }
+extern "C" int mvlt_attn_route(const MvltAttn* p, int bwd) { return route(p, bwd != 0); }
 extern "C" int mvlt_attn_bwd_ev(const MvltAttn* p, void* stream, void* event) {
     MVLT_CHECK(event, MVLT_ERR_ARG);
     t_stop_event = reinterpret_cast<hipEvent_t>(event);

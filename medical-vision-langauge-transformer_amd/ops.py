@@ -628,14 +628,18 @@ def _attn_struct(qkv, out, lse, mode, nseq, Lq, nH, hd, scale, *, bias_table=Non
     return p
 
 
-def attn_fwd(qkv, mode, nseq, Lq, nH, hd, scale, **kw):
+def attn_fwd(qkv, mode, nseq, Lq, nH, hd, scale, out=None, lse=None, **kw):
     """qkv: [nseq*L, 3*nH*hd] -> (out [nseq*L, nH*hd], lse [nseq,nH,L]); with pack= the rows are packed
-    ([R, ...], sequence s at rows row_start[s] .. +seq_len[s])."""
+    ([R, ...], sequence s at rows row_start[s] .. +seq_len[s]).  out / lse: optional caller buffers."""
     _need_cuda(qkv)
     rows = nseq * Lq if kw.get("pack") is None else kw["pack"][2]
     assert qkv.is_contiguous() and qkv.shape == (rows, 3 * nH * hd)
-    out = torch.empty((rows, nH * hd), dtype=qkv.dtype, device=qkv.device)
-    lse = torch.empty((nseq, nH, Lq), dtype=torch.float32, device=qkv.device)
+    if out is None:
+        out = torch.empty((rows, nH * hd), dtype=qkv.dtype, device=qkv.device)
+    if lse is None:
+        lse = torch.empty((nseq, nH, Lq), dtype=torch.float32, device=qkv.device)
+    assert out.is_contiguous() and out.dtype == qkv.dtype and out.shape == (rows, nH * hd)
+    assert lse.is_contiguous() and lse.dtype == torch.float32 and lse.shape == (nseq, nH, Lq)
     p = _attn_struct(qkv, out, lse, mode, nseq, Lq, nH, hd, scale, **kw)
     L.check(L.lib().mvlt_attn_fwd(C.byref(p), _stream()), "mvlt_attn_fwd")
     return out, lse
@@ -646,24 +650,49 @@ def swin_bwd_proj_supported(dtype, nH, hd, shift):
     return dtype == torch.bfloat16 and hd == 32 and nH in (3, 6, 12) and shift in (0, 3)
 
 
-def attn_bwd(dout, qkv, out, lse, mode, nseq, Lq, nH, hd, scale, dbias_table=None, event=None, dout_weight=None, **kw):
-    """event: a hipEvent_t handle (int) that completes with the call's last kernel (mvlt_attn_bwd_ev: the fork of the
-    weight-gradient stream without a marker packet on this stream).  dout_weight (Swin only): `dout` is the gradient of the output
-    projection's OUTPUT and the kernel applies proj.weight's transpose per head itself (MvltAttn.dout_weight)."""
-    _need_cuda(qkv, dout)
-    assert dout.is_contiguous() and dout.shape == out.shape
-    dqkv = torch.empty_like(qkv)
+def _attn_bwd_struct(dout, qkv, out, lse, mode, nseq, Lq, nH, hd, scale, dbias_table, dout_weight, dqkv, delta_ws, kw):
     p = _attn_struct(qkv, out, lse, mode, nseq, Lq, nH, hd, scale, **kw)
     p.dout, p.dqkv = _p(dout), _p(dqkv)
     if dout_weight is not None:
         assert mode == L.ATTN_SWIN and dout_weight.dtype == qkv.dtype and dout_weight.is_contiguous() and dout_weight.shape == (nH * hd, nH * hd)
         p.dout_weight = _p(dout_weight)
-    if mode != L.ATTN_SWIN:
+    if mode != L.ATTN_SWIN and delta_ws:
         delta = torch.empty_like(lse)          # delta_q hand-over between the two backward launches
         p.delta_ws = _p(delta)
     if dbias_table is not None:
         assert dbias_table.dtype == torch.float32
         p.dbias_table = _p(dbias_table)
+    return p
+
+
+def attn_route(qkv, mode, nseq, Lq, nH, hd, scale, bwd=False, dout_weight=None, delta_ws=True, **kw):
+    """The kernel mvlt_attn_fwd / mvlt_attn_bwd would launch for these arguments (a name of _lib.ATTN_ROUTES), nothing
+    launched.  Same keywords as attn_fwd / attn_bwd."""
+    rows = qkv.shape[0]
+    out = torch.empty((rows, nH * hd), dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty((nseq, nH, Lq), dtype=torch.float32, device=qkv.device)
+    if bwd:
+        p = _attn_bwd_struct(out, qkv, out, lse, mode, nseq, Lq, nH, hd, scale, None, dout_weight, qkv, delta_ws, kw)
+    else:
+        p = _attn_struct(qkv, out, lse, mode, nseq, Lq, nH, hd, scale, **kw)
+    r = L.lib().mvlt_attn_route(C.byref(p), int(bool(bwd)))
+    L.check(min(r, 0), "mvlt_attn_route")
+    return L.ATTN_ROUTES[r]
+
+
+def attn_bwd(dout, qkv, out, lse, mode, nseq, Lq, nH, hd, scale, dbias_table=None, event=None, dout_weight=None,
+             dqkv=None, delta_ws=True, **kw):
+    """event: a hipEvent_t handle (int) that completes with the call's last kernel (mvlt_attn_bwd_ev: the fork of the
+    weight-gradient stream without a marker packet on this stream).  dout_weight (Swin only): `dout` is the gradient of the output
+    projection's OUTPUT and the kernel applies proj.weight's transpose per head itself (MvltAttn.dout_weight).
+    dqkv: optional caller buffer.  delta_ws=False (MVLBert modes): no delta_q workspace, which leaves the two-launch
+    backward out and takes the generic one (MVLT_ERR_UNSUPPORTED where that does not apply)."""
+    _need_cuda(qkv, dout)
+    assert dout.is_contiguous() and dout.shape == out.shape
+    if dqkv is None:
+        dqkv = torch.empty_like(qkv)
+    assert dqkv.is_contiguous() and dqkv.dtype == qkv.dtype and dqkv.shape == qkv.shape
+    p = _attn_bwd_struct(dout, qkv, out, lse, mode, nseq, Lq, nH, hd, scale, dbias_table, dout_weight, dqkv, delta_ws, kw)
     if event is not None:
         L.check(L.lib().mvlt_attn_bwd_ev(C.byref(p), _stream(), C.c_void_p(event)), "mvlt_attn_bwd_ev")
     else:

@@ -101,9 +101,10 @@ def colsum_ref(a, k_eff=None):
     return a.sum(1), C_ACC * U32 * math.sqrt(max(k_eff, 1)) * a.abs().sum(1) + 1e-30
 
 
-def check_bound(out, ref, bound, what=""):
+def check_bound(out, ref, bound, what="", heads=None):
     """Assert |out - ref| <= bound element by element; on failure name the worst element (row, column, ratio to the
-    bound) and how many elements are out.  Non-finite outputs count as out with an infinite ratio."""
+    bound) and how many elements are out.  Non-finite outputs count as out with an infinite ratio.  heads = (hd, nH):
+    the columns are [part][head][hd] (attention: out, dqkv), and the message names the part and head as well."""
     out = out.double().to(ref.device)
     assert out.shape == ref.shape, (what, tuple(out.shape), tuple(ref.shape))
     if out.numel() == 0:
@@ -116,6 +117,7 @@ def check_bound(out, ref, bound, what=""):
         r, c = divmod(flat, ref.shape[1]) if ref.dim() == 2 else (flat, 0)
         bad = int((ratio > 1.0).sum())
         idx = (r, c) if ref.dim() == 2 else (r,)
+        where = "" if heads is None else f" (part {c // (heads[0] * heads[1])}, head {c // heads[0] % heads[1]})"
         raise AssertionError(
-            f"{what}: {bad} of {ref.numel()} elements outside the bound; worst at row {r}, column {c}: "
+            f"{what}: {bad} of {ref.numel()} elements outside the bound; worst at row {r}, column {c}{where}: "
             f"out {float(out[idx]):.9g}, ref {float(ref[idx]):.9g}, bound {float(bound[idx]):.3g}, ratio {worst:.3g}")
