@@ -36,12 +36,13 @@ enum { MVLT_OK = 0, MVLT_ERR_ARG = -1, MVLT_ERR_LAUNCH = -2, MVLT_ERR_UNSUPPORTE
  * signature; a binding compiles / hard-codes the value it was written against and compares it with what the
  * loaded library returns.  mvlt_sizeof(MVLT_STRUCT_*) lets a binding that mirrors the structs by hand (ctypes,
  * cgo, JNI) prove that its mirror has the size the library was compiled with (0 for an unknown id). */
-#define MVLT_ABI_VERSION 9
+#define MVLT_ABI_VERSION 10
 int mvlt_version(void);            /* MVLT_ABI_VERSION of the loaded library */
 const char* mvlt_arch(void);       /* "gfx950" */
 enum { MVLT_STRUCT_GEMM = 0, MVLT_STRUCT_LAYERNORM = 1, MVLT_STRUCT_LAYERNORM_BWD = 2, MVLT_STRUCT_LN_REDUCE_ITEM = 3,
        MVLT_STRUCT_ATTN = 4, MVLT_STRUCT_SWIN_WMSA = 5, MVLT_STRUCT_EMBED = 6, MVLT_STRUCT_ATTN_CACHED = 7,
-       MVLT_STRUCT_ZERO_ITEM = 8, MVLT_STRUCT_RANGE = 9, MVLT_STRUCT_MLM_MASK = 10, MVLT_STRUCT_GREEDY_STATE = 11, MVLT_STRUCT_SWIN_DBIAS_ITEM = 12, MVLT_STRUCT_COUNT = 13 };
+       MVLT_STRUCT_ZERO_ITEM = 8, MVLT_STRUCT_RANGE = 9, MVLT_STRUCT_MLM_MASK = 10, MVLT_STRUCT_GREEDY_STATE = 11, MVLT_STRUCT_SWIN_DBIAS_ITEM = 12,
+       MVLT_STRUCT_SAMPLE_STATE = 13, MVLT_STRUCT_COUNT = 14 };
 size_t mvlt_sizeof(int struct_id);
 
 /* ------------------------------------------------------------------ GEMM
@@ -132,6 +133,29 @@ typedef struct MvltGreedyState {
     int32_t* ticket;
 } MvltGreedyState;
 int mvlt_gemm_argmax_greedy(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltGreedyState* g, void* stream);
+/* Last-row MLM head fused with the SAMPLED pick (model.py:901-906, sample_mode = 'sample'): multinomial(softmax(x)) drawn as
+ * argmax_n (x_n + G_n) with i.i.d. standard Gumbel noise (Gumbel-max); the logits are never stored.  Per element, in f32:
+ *   x = (A W^T + bias)[m, n] * inv_temperature
+ *   u = rng_u32(seed, tag, m * N + n)              (the counter hash of the dropout masks; N = p->N, not a padded width)
+ *   u01 = ((u >> 8) + 0.5) * 2^-24,  G = -log(-log(u01))     (finite; |G_f32 - G| <= 2^-22 (3 + |G|): mvlt_gumbel_noise)
+ *   out_idx[m] = first argmax_n (x + G),  out_logprob[m] = x[out_idx[m]] - logsumexp_n x
+ * Same preconditions and error codes as mvlt_gemm_argmax_greedy (M <= 64, K a whole number of k-blocks, k-contiguous 16-byte
+ * aligned operands, only MVLT_EPI_BIAS; C unused), M * N < 2^32, 0 < inv_temperature < inf.
+ * part_val: scratch, 4 * M * ceil(N / 16) floats; part_idx: M * ceil(N / 16). */
+int mvlt_gemm_sample(const MvltGemm* p, float* part_val, int32_t* part_idx, int64_t* out_idx, float* out_logprob,
+                     uint64_t seed, uint32_t tag, float inv_temperature, void* stream);
+/* The graph form: the bookkeeping of mvlt_gemm_argmax_greedy with the sampled pick; scores[m, *col] = the log-probability of
+ * the DRAWN token (also for a finished sample, whose id becomes pad_id: the reference gathers the score first).  The noise of
+ * the token in output column c uses seed = *seed and tag = tag0 + c, both read on the device: one captured graph serves every
+ * call and every token.  A decode of max_length tokens uses the tags tag0 .. tag0 + max_length - 1. */
+typedef struct MvltSampleState {
+    int64_t* unfinished; int64_t eos_id, pad_id; int has_eos;
+    int64_t* col; int32_t* past;
+    int64_t* ids; int64_t ld_ids; float* scores; int64_t ld_scores; int64_t* alive; int64_t* new_ids; int64_t ld_new;
+    int32_t* ticket;
+    const uint64_t* seed; uint32_t tag0; float inv_temperature;
+} MvltSampleState;
+int mvlt_gemm_sample_step(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltSampleState* g, void* stream);
 
 /* Decode step (model.py:82-108: 2 new tokens per sample): skinny product with the reduction split over workgroups:
  * acc[s][M][N] (f32, k_splits slabs) = A[:, k-slice s] B[:, k-slice s]^T, M <= 64, both operands k-contiguous, no epilogue;
@@ -443,6 +467,8 @@ int mvlt_softmax_rows(int dtype, const void* x, int64_t ld, int rows, int V, flo
 int mvlt_tanh_fwd(int dtype, const void* x, void* y, int64_t n, void* stream);
 int mvlt_tanh_bwd(int dtype, const void* y, const void* dy, void* dx, int64_t n, void* stream);
 int mvlt_dropout_mask(uint8_t* keep, int64_t n, float p, uint64_t seed, uint32_t tag, void* stream);
+/* the Gumbel noise of mvlt_gemm_sample as its kernel computes it: out[m * N + n] (f32, rows * N < 2^32) for one (seed, tag) */
+int mvlt_gumbel_noise(uint64_t seed, uint32_t tag, int rows, int N, float* out, void* stream);
 int mvlt_droppath_scale(float* scale, int B, float p, uint64_t seed, uint32_t tag, void* stream);
 /* every DropPath scale of a forward pass in one launch (visual_feature_extractor.py:30-44 for each of the 2 x 24 residual
  * branches): scale [rows, B] f32, row r keeps sample b with probability 1 - probs[r] (device f32 [rows], each < 1) and

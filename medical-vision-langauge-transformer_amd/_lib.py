@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(_HERE, "libmvlt_hip.so")
 
 F32, BF16 = 0, 1
 OK = 0
-ABI_VERSION = 9          # == MVLT_ABI_VERSION of the include/mvlt_hip.h these mirrors were written against
+ABI_VERSION = 10         # == MVLT_ABI_VERSION of the include/mvlt_hip.h these mirrors were written against
 ERRORS = {-1: "MVLT_ERR_ARG", -2: "MVLT_ERR_LAUNCH", -3: "MVLT_ERR_UNSUPPORTED"}
 
 EPI_BIAS, EPI_GELU, EPI_SAVE_PRE, EPI_DROPOUT = 1, 2, 4, 8
@@ -124,6 +124,10 @@ class MvltGreedyState(C.Structure):
                 ("alive", vp), ("new_ids", vp), ("ld_new", i64), ("ticket", vp)]
 
 
+class MvltSampleState(C.Structure):
+    _fields_ = MvltGreedyState._fields_ + [("seed", vp), ("tag0", u32), ("inv_temperature", f32)]
+
+
 # every symbol include/mvlt_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "mvlt_version": (i32, []),
@@ -136,6 +140,8 @@ SYMBOLS = {
     "mvlt_gemm_group_workspace_bytes": (sz, [C.POINTER(MvltGemm), i32]),
     "mvlt_gemm_argmax": (i32, [C.POINTER(MvltGemm), vp, vp, vp, vp, vp]),
     "mvlt_gemm_argmax_greedy": (i32, [C.POINTER(MvltGemm), vp, vp, C.POINTER(MvltGreedyState), vp]),
+    "mvlt_gemm_sample": (i32, [C.POINTER(MvltGemm), vp, vp, vp, vp, u64, u32, f32, vp]),
+    "mvlt_gemm_sample_step": (i32, [C.POINTER(MvltGemm), vp, vp, C.POINTER(MvltSampleState), vp]),
     "mvlt_gemm_skinny_accum": (i32, [C.POINTER(MvltGemm), vp, i32, vp]),
     "mvlt_layernorm_acc_fwd": (i32, [i32, vp, i32, vp, vp, vp, vp, f32, i32, i32, vp, vp]),
     "mvlt_colsum": (i32, [i32, vp, i64, i32, i32, vp, i32, vp, vp]),
@@ -176,6 +182,7 @@ SYMBOLS = {
     "mvlt_tanh_fwd": (i32, [i32, vp, vp, i64, vp]),
     "mvlt_tanh_bwd": (i32, [i32, vp, vp, vp, i64, vp]),
     "mvlt_dropout_mask": (i32, [vp, i64, f32, u64, u32, vp]),
+    "mvlt_gumbel_noise": (i32, [u64, u32, i32, i32, vp, vp]),
     "mvlt_droppath_scale": (i32, [vp, i32, f32, u64, u32, vp]),
     "mvlt_droppath_scales": (i32, [vp, vp, i32, i32, u64, u32, vp]),
     "mvlt_ce_fwd": (i32, [i32, vp, i64, i32, i32, vp, vp, vp, vp, vp]),
@@ -195,7 +202,8 @@ SYMBOLS = {
 
 # ctypes mirror of every struct, in the order of the MVLT_STRUCT_* ids of the header
 STRUCTS = [MvltGemm, MvltLayerNorm, MvltLayerNormBwd, MvltLnReduceItem, MvltAttn, MvltSwinWmsa, MvltEmbed,
-           MvltAttnCached, MvltZeroItem, MvltRange, MvltMlmMask, MvltGreedyState, MvltSwinDbiasItem]
+           MvltAttnCached, MvltZeroItem, MvltRange, MvltMlmMask, MvltGreedyState, MvltSwinDbiasItem,
+           MvltSampleState]
 
 _lib = None
 

@@ -65,6 +65,25 @@ MVLT_DEV bool rng_keep(uint64_t seed, uint32_t tag, uint32_t idx, uint32_t thres
     return rng_u32(seed, tag, idx) >= thresh;
 }
 
+// Standard Gumbel noise g = -log(-log(u01)), u01 = ((rng_u32 >> 8) + 0.5) 2^-24 (never 0 or 1, so g is finite: -2.86 .. 17.33),
+// for Gumbel-max sampling (gemm.hip: sampled pick).  With k = rng_u32 >> 8, k + 0.5 has 25 significant bits and is exact in f32
+// only below 2^23; above, h = fl(k + 0.5) is k or k + 1 and the remainder l = (k - h) + 0.5 in {-0.5, 0, +0.5} is exact, so
+//     t = -log(u01) = -(log(h 2^-24) + log1p(l / h)),   log1p(l / h) = l / h up to (l / h)^2 / 2 <= 2^-49
+// keeps t RELATIVELY accurate where u01 -> 1 (t -> 2^-25; fl(k + 0.5) alone would give u01 = 1 and g = inf at k = 2^24 - 1).
+// Both logarithms are the library's logf (NOT __logf: v_log_f32 times ln 2 loses relative accuracy next to 1), taken at <= 2 ulp
+// = 2^-22 relative; v_rcp_f32 is <= 1 ulp.  Error: |log(h 2^-24)| <= (4/3) t, so t is off by at most
+// (4/3 + 1 + 1/4 + 1/4) 2^-22 < 3 2^-22 relative (logf, the l / h term with its rcp and product roundings, the dropped square,
+// the rounding of the sum), which is an absolute error of log t; the outer logf adds 2^-22 |g|:
+//     |g_f32 - g| <= e_g(u01) = 2^-22 (3 + |g|) (1 + 2^-10)
+// (tests/sample_ref.py restates it, tests/test_sample_bound_cpu.py proves it over all 2^24 values of k).
+MVLT_DEV float gumbel_noise(uint64_t seed, uint32_t tag, uint32_t idx) {
+    const float kf = (float)(rng_u32(seed, tag, idx) >> 8);          // < 2^24: exact
+    const float h = __fadd_rn(kf, 0.5f);
+    const float l = __fadd_rn(__fadd_rn(kf, -h), 0.5f);
+    const float t = -__fadd_rn(logf(h * 5.9604644775390625e-8f), __fmul_rn(l, __builtin_amdgcn_rcpf(h)));
+    return -logf(t);
+}
+
 // ---------------------------------------------------------------- wave reductions (64 lanes)
 MVLT_DEV float wave_sum(float v) {
 #pragma unroll

@@ -781,6 +781,27 @@ struct GreedyState {
     int64_t* ids; long ld_ids; float* scores; long ld_scores; int64_t* alive; int64_t* new_ids; long ld_new;
     int32_t* ticket;
 };
+// The per-token bookkeeping both pick kernels end with (one thread per row): `tok` is the row's pick, `score` what goes into
+// scores[:, col] -- of the PICKED token also for a finished row (the reference gathers the score before PAD replaces the token).
+MVLT_DEV void pick_bookkeeping(const GreedyState& st, const int m, const int M, const long col, const int tok, const float score) {
+    int64_t nxt = tok;
+    if (st.has_eos) {
+        const int64_t unf = st.unfinished[m];
+        nxt = nxt * unf + st.pad * (1 - unf);
+        const int64_t unf2 = unf * (nxt != st.eos ? 1 : 0);
+        st.unfinished[m] = unf2;
+        if (unf2) atomicMax(reinterpret_cast<unsigned long long*>(st.alive + col), 1ULL);
+    }
+    st.ids[(long)m * st.ld_ids + col] = nxt;
+    st.scores[(long)m * st.ld_scores + col] = score;
+    st.new_ids[(long)m * st.ld_new] = nxt;
+    __threadfence();
+    if (atomicAdd(st.ticket, 1) == M - 1) {
+        *st.ticket = 0;
+        st.col[0] = col + 1;
+        if (st.past) st.past[0] += 1;
+    }
+}
 // One workgroup per row (256 threads: ~8 partials per thread, one memory round trip; a single workgroup walking all rows took
 // 26 us).  alive[col] is raised with an atomic max by the rows that are still unfinished (the caller zeroes `alive` when a
 // decode starts); the LAST workgroup to arrive (ticket) advances col and past and re-arms the ticket.  Every workgroup reads
@@ -809,23 +830,140 @@ __global__ __launch_bounds__(256) void greedy_pick_kernel(const float* part_val,
             const float ov = s_val[w]; const int oi = s_idx[w];
             if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
         }
-        int64_t nxt = bi;
-        if (st.has_eos) {
-            const int64_t unf = st.unfinished[m];
-            nxt = nxt * unf + st.pad * (1 - unf);
-            const int64_t unf2 = unf * (nxt != st.eos ? 1 : 0);
-            st.unfinished[m] = unf2;
-            if (unf2) atomicMax(reinterpret_cast<unsigned long long*>(st.alive + col), 1ULL);
+        pick_bookkeeping(st, m, M, col, bi, best);
+    }
+}
+
+// SAMPLED pick (greedy_search 'sample' mode, model.py:901-906): multinomial(softmax(x)) is argmax_n (x_n + G_n) with i.i.d.
+// standard Gumbel noise G (Gumbel-max), so the sampled step is the greedy product with a noise term in the epilogue and an online
+// log-sum-exp beside the running maximum (the score is the log-probability of the drawn token).  Sibling of
+// gemm_argmax128_kernel: the same main loop (kept apart so the greedy instantiations stay exactly what they were); epilogue
+// per element (m, n), all in f32, no fused multiply-add:
+//     x = (acc + bias[n]) * inv_temperature;   y = x + gumbel_noise(seed, tag0 + step, m N + n)      (common.h)
+// seed = *seed_dev and step = *col are read from device memory (one captured graph serves every call and every token).
+// Per row and 16-column part it writes five values, part_val[j][m][part]: j = 0 max y, 1 x at that index, 2 max x,
+// 3 sum exp(x - max x); part_idx[m][part] = first index of max y.  Columns n >= N take part in neither.
+struct SampleIn { const uint64_t* seed_dev; uint64_t seed; const int64_t* col; uint32_t tag0; float inv_t; };
+template <typename T, int NRT>
+__global__ __launch_bounds__(64 * SKINNY_WAVES) void gemm_sample128_kernel(const GemmDev p, float* part_val, int* part_idx, int nparts, const SampleIn si) {
+    using M_ = Mma<T>;
+    using Frag = typename M_::Frag;
+    constexpr int KB = M_::KB, E = TypeInfo<T>::E, UNR = NRT <= 2 ? 12 : 8;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), r15 = lane & 15, g = lane >> 4;
+    const int n0 = (blockIdx.x * SKINNY_WAVES + wave) * 16;
+    if (n0 >= p.N) return;
+    const uint64_t seed = si.seed_dev ? si.seed_dev[0] : si.seed;
+    const uint32_t tag = si.tag0 + (si.col ? (uint32_t)si.col[0] : 0u);
+    const T* A = reinterpret_cast<const T*>(p.A);
+    const T* brow = reinterpret_cast<const T*>(p.B) + (long)min(n0 + r15, p.N - 1) * p.ldb + g * E;
+    const T* arow[NRT];
+#pragma unroll
+    for (int i = 0; i < NRT; ++i) arow[i] = A + (long)min(16 * i + r15, p.M - 1) * p.lda + g * E;
+    f32x4 acc[NRT];
+#pragma unroll
+    for (int i = 0; i < NRT; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int nkb = p.K / KB;
+    for (int kb0 = 0; kb0 < nkb; kb0 += UNR) {
+        Frag fb[UNR], fa[UNR][NRT];
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            const int k = min(kb0 + u, nkb - 1) * KB;          // past the end: reload the last block, never multiplied
+            fb[u] = skinny_wload(reinterpret_cast<const Frag*>(brow + k));
+#pragma unroll
+            for (int i = 0; i < NRT; ++i) fa[u][i] = *reinterpret_cast<const Frag*>(arow[i] + k);
         }
-        st.ids[(long)m * st.ld_ids + col] = nxt;
-        st.scores[(long)m * st.ld_scores + col] = best;
-        st.new_ids[(long)m * st.ld_new] = nxt;
-        __threadfence();
-        if (atomicAdd(st.ticket, 1) == M - 1) {
-            *st.ticket = 0;
-            st.col[0] = col + 1;
-            if (st.past) st.past[0] += 1;
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            if (kb0 + u < nkb) {
+#pragma unroll
+                for (int i = 0; i < NRT; ++i) M_::mma(acc[i], fb[u], fa[u][i]);
+            }
         }
+    }
+    // acc[i][r] <-> n = n0 + 4 g + r, m = 16 i + r15
+    f32x4 bias4{0.f, 0.f, 0.f, 0.f};
+    if (p.epi & MVLT_EPI_BIAS) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bias4[r] = p.bias[min(n0 + 4 * g + r, p.N - 1)];
+    }
+    const int part = blockIdx.x * SKINNY_WAVES + wave;
+    const long plane = (long)p.M * nparts;
+#pragma unroll
+    for (int i = 0; i < NRT; ++i) {
+        const int m = 16 * i + r15;
+        float x[4];
+        float best = -3.0e38f, bx = 0.f, xm = -3.0e38f; int bi = 0x7fffffff;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int n = n0 + 4 * g + r;
+            x[r] = __fmul_rn(__fadd_rn(acc[i][r], bias4[r]), si.inv_t);
+            const float y = __fadd_rn(x[r], gumbel_noise(seed, tag, (uint32_t)m * (uint32_t)p.N + (uint32_t)n));
+            if (n < p.N) {
+                if (y > best) { best = y; bi = n; bx = x[r]; }          // ascending n: ties keep the first index
+                xm = fmaxf(xm, x[r]);
+            }
+        }
+#pragma unroll
+        for (int o = 16; o < 64; o <<= 1) {
+            const float ov = __shfl_xor(best, o, 64), ox = __shfl_xor(bx, o, 64); const int oi = __shfl_xor(bi, o, 64);
+            if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; bx = ox; }
+            xm = fmaxf(xm, __shfl_xor(xm, o, 64));
+        }
+        // (n0 < N: every part has a valid column, so xm is a logit; __expf of a non-positive argument: v_exp_f32 of x log2 e)
+        float se = 0.f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) se += (n0 + 4 * g + r < p.N) ? __expf(x[r] - xm) : 0.f;
+        se += __shfl_xor(se, 16, 64);
+        se += __shfl_xor(se, 32, 64);
+        if (g == 0 && m < p.M) {
+            const long o = (long)m * nparts + part;
+            part_val[o] = best; part_val[plane + o] = bx; part_val[2 * plane + o] = xm; part_val[3 * plane + o] = se;
+            part_idx[o] = bi;
+        }
+    }
+}
+
+// Finish of the sampled pick, one workgroup per row like greedy_pick_kernel: the parts reduce to the token (first index of the
+// largest y), lse = M + log(sum_parts s_p exp(m_p - M)) with M the row's largest logit, score = x_token - lse (logf: <= 2 ulp).
+// STEP: then the bookkeeping of greedy_pick_kernel; else the stand-alone outputs out_idx / out_logprob.
+template <bool STEP>
+__global__ __launch_bounds__(256) void sample_pick_kernel(const float* part_val, const int* part_idx, int nparts, int M, const GreedyState st,
+                                                          int64_t* out_idx, float* out_logprob) {
+    __shared__ float s_val[4], s_x[4], s_max[4], s_sum[4];
+    __shared__ int s_idx[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = blockIdx.x;
+    const long col = STEP ? st.col[0] : 0;
+    const long base = (long)m * nparts, plane = (long)M * nparts;
+    float best = -3.0e38f, bx = 0.f, xm = -3.0e38f; int bi = 0x7fffffff;
+    for (int i = threadIdx.x; i < nparts; i += 256) {
+        const float v = part_val[base + i]; const int idx = part_idx[base + i];
+        if (v > best || (v == best && idx < bi)) { best = v; bi = idx; bx = part_val[plane + base + i]; }
+        xm = fmaxf(xm, part_val[2 * plane + base + i]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64), ox = __shfl_xor(bx, o, 64); const int oi = __shfl_xor(bi, o, 64);
+        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; bx = ox; }
+        xm = fmaxf(xm, __shfl_xor(xm, o, 64));
+    }
+    if (lane == 0) { s_val[wave] = best; s_idx[wave] = bi; s_x[wave] = bx; s_max[wave] = xm; }
+    __syncthreads();
+    xm = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
+    float se = 0.f;
+    for (int i = threadIdx.x; i < nparts; i += 256) se += part_val[3 * plane + base + i] * __expf(part_val[2 * plane + base + i] - xm);
+    se = wave_sum(se);
+    if (lane == 0) s_sum[wave] = se;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 1; w < 4; ++w) {
+            const float ov = s_val[w]; const int oi = s_idx[w];
+            if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; bx = s_x[w]; }
+        }
+        const float lse = __fadd_rn(xm, logf((s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3])));
+        const float score = __fadd_rn(bx, -lse);
+        if (STEP) pick_bookkeeping(st, m, M, col, bi, score);
+        else { out_idx[m] = bi; out_logprob[m] = score; }
     }
 }
 
@@ -1605,6 +1743,66 @@ extern "C" int mvlt_gemm_argmax_greedy(const MvltGemm* p, float* part_val, int32
     GreedyState st{g->unfinished, g->eos_id, g->pad_id, g->has_eos, g->col, g->past, g->ids, g->ld_ids, g->scores, g->ld_scores, g->alive,
                    g->new_ids, g->ld_new, g->ticket};
     hipLaunchKernelGGL(greedy_pick_kernel, dim3(p->M), dim3(256), 0, s, part_val, part_idx, nblk, p->M, st);
+    MVLT_LAUNCH_CHECK();
+    return MVLT_OK;
+}
+
+// the sampled partials: always the wide streaming form (it handles any N; the 16-column skinny kernel has no sampled sibling)
+template <typename T>
+static int sample_products(const MvltGemm* p, float* part_val, int32_t* part_idx, int nblk, const SampleIn& si, hipStream_t s) {
+    MVLT_CHECK(is_skinny<T>(p) && p->K % Mma<T>::KB == 0 && p->lda % TypeInfo<T>::E == 0 && p->ldb % TypeInfo<T>::E == 0 &&
+               aligned16(p->A) && aligned16(p->B), MVLT_ERR_UNSUPPORTED);
+    GemmDev d;
+    Plan pl{64, 16, 1};
+    { const int rc = fill_dev<T>(p, pl, d); if (rc != MVLT_OK) return rc; }
+    const dim3 grid(ceil_div(nblk, SKINNY_WAVES)), block(64 * SKINNY_WAVES);
+    if (p->M <= 16) hipLaunchKernelGGL((gemm_sample128_kernel<T, 1>), grid, block, 0, s, d, part_val, part_idx, nblk, si);
+    else if (p->M <= 32) hipLaunchKernelGGL((gemm_sample128_kernel<T, 2>), grid, block, 0, s, d, part_val, part_idx, nblk, si);
+    else if (p->M <= 48) hipLaunchKernelGGL((gemm_sample128_kernel<T, 3>), grid, block, 0, s, d, part_val, part_idx, nblk, si);
+    else hipLaunchKernelGGL((gemm_sample128_kernel<T, 4>), grid, block, 0, s, d, part_val, part_idx, nblk, si);
+    return MVLT_OK;
+}
+
+static int sample_check(const MvltGemm* p, const float* part_val, const int32_t* part_idx, float inv_temperature) {
+    MVLT_CHECK(p && p->A && p->B && part_val && part_idx, MVLT_ERR_ARG);
+    MVLT_CHECK(p->M > 0 && p->M <= 64 && p->N > 0 && p->K > 0 && p->lda > 0 && p->ldb > 0, MVLT_ERR_ARG);
+    MVLT_CHECK((long)p->M * p->N < (1L << 32) && inv_temperature > 0.f && inv_temperature < 3.0e38f, MVLT_ERR_ARG);
+    MVLT_CHECK(!p->a_kmajor && !p->b_kmajor && (p->epilogue & ~(MVLT_EPI_BIAS)) == 0, MVLT_ERR_UNSUPPORTED);
+    if (p->epilogue & MVLT_EPI_BIAS) MVLT_CHECK(p->bias, MVLT_ERR_ARG);
+    return MVLT_OK;
+}
+
+extern "C" int mvlt_gemm_sample(const MvltGemm* p, float* part_val, int32_t* part_idx, int64_t* out_idx, float* out_logprob,
+                                uint64_t seed, uint32_t tag, float inv_temperature, void* stream) {
+    { const int rc = sample_check(p, part_val, part_idx, inv_temperature); if (rc != MVLT_OK) return rc; }
+    MVLT_CHECK(out_idx && out_logprob, MVLT_ERR_ARG);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int nblk = ceil_div(p->N, 16);
+    const SampleIn si{nullptr, seed, nullptr, tag, inv_temperature};
+    int rc = MVLT_ERR_UNSUPPORTED;
+    if (p->dtype == MVLT_BF16) rc = sample_products<bf16_t>(p, part_val, part_idx, nblk, si, s);
+    else if (p->dtype == MVLT_F32) rc = sample_products<float>(p, part_val, part_idx, nblk, si, s);
+    if (rc != MVLT_OK) return rc;
+    hipLaunchKernelGGL(sample_pick_kernel<false>, dim3(p->M), dim3(256), 0, s, part_val, part_idx, nblk, p->M, GreedyState{}, out_idx, out_logprob);
+    MVLT_LAUNCH_CHECK();
+    return MVLT_OK;
+}
+
+extern "C" int mvlt_gemm_sample_step(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltSampleState* g, void* stream) {
+    MVLT_CHECK(g, MVLT_ERR_ARG);
+    { const int rc = sample_check(p, part_val, part_idx, g->inv_temperature); if (rc != MVLT_OK) return rc; }
+    MVLT_CHECK(g->seed && g->col && g->ticket && g->ids && g->scores && g->new_ids && g->ld_ids > 0 && g->ld_scores > 0 && g->ld_new > 0, MVLT_ERR_ARG);
+    if (g->has_eos) MVLT_CHECK(g->unfinished && g->alive, MVLT_ERR_ARG);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int nblk = ceil_div(p->N, 16);
+    const SampleIn si{g->seed, 0, g->col, g->tag0, g->inv_temperature};
+    int rc = MVLT_ERR_UNSUPPORTED;
+    if (p->dtype == MVLT_BF16) rc = sample_products<bf16_t>(p, part_val, part_idx, nblk, si, s);
+    else if (p->dtype == MVLT_F32) rc = sample_products<float>(p, part_val, part_idx, nblk, si, s);
+    if (rc != MVLT_OK) return rc;
+    GreedyState st{g->unfinished, g->eos_id, g->pad_id, g->has_eos, g->col, g->past, g->ids, g->ld_ids, g->scores, g->ld_scores, g->alive,
+                   g->new_ids, g->ld_new, g->ticket};
+    hipLaunchKernelGGL(sample_pick_kernel<true>, dim3(p->M), dim3(256), 0, s, part_val, part_idx, nblk, p->M, st, (int64_t*)nullptr, (float*)nullptr);
     MVLT_LAUNCH_CHECK();
     return MVLT_OK;
 }

@@ -275,6 +275,10 @@ __global__ void dropout_mask_kernel(uint8_t* keep, long n, uint32_t thresh, uint
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
         keep[i] = rng_keep(seed, tag, (uint32_t)i, thresh) ? 1 : 0;
 }
+__global__ void gumbel_noise_kernel(float* out, long n, uint64_t seed, uint32_t tag) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+        out[i] = gumbel_noise(seed, tag, (uint32_t)i);
+}
 __global__ void droppath_kernel(float* scale, int B, uint32_t thresh, float inv_keep, uint64_t seed, uint32_t tag) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b < B) scale[b] = rng_keep(seed, tag, (uint32_t)b, thresh) ? inv_keep : 0.f;
@@ -718,6 +722,7 @@ extern "C" size_t mvlt_sizeof(int struct_id) {
         case MVLT_STRUCT_MLM_MASK: return sizeof(MvltMlmMask);
         case MVLT_STRUCT_GREEDY_STATE: return sizeof(MvltGreedyState);
         case MVLT_STRUCT_SWIN_DBIAS_ITEM: return sizeof(MvltSwinDbiasItem);
+        case MVLT_STRUCT_SAMPLE_STATE: return sizeof(MvltSampleState);
         default: return 0;
     }
 }
@@ -851,6 +856,14 @@ extern "C" int mvlt_gelu_bwd(int dtype, const void* x, const void* dy, void* dx,
 extern "C" int mvlt_tanh_bwd(int dtype, const void* y, const void* dy, void* dx, int64_t n, void* stream) {
     MVLT_CHECK(dy, MVLT_ERR_ARG);
     return unary<2>(dtype, y, dy, dx, n, stream);
+}
+
+extern "C" int mvlt_gumbel_noise(uint64_t seed, uint32_t tag, int rows, int N, float* out, void* stream) {
+    MVLT_CHECK(out && rows > 0 && N > 0 && (int64_t)rows * N < 4294967296LL, MVLT_ERR_ARG);
+    const long n = (long)rows * N;
+    hipLaunchKernelGGL(gumbel_noise_kernel, dim3(grid_for(n, 256)), dim3(256), 0, STREAM(stream), out, n, seed, tag);
+    MVLT_LAUNCH_CHECK();
+    return MVLT_OK;
 }
 
 extern "C" int mvlt_dropout_mask(uint8_t* keep, int64_t n, float p, uint64_t seed, uint32_t tag, void* stream) {

@@ -10,7 +10,9 @@ K/V in place and attends causally (``mvlt_attn_cached``).  "Trimming the [MASK]
 slot" (model.py:890-894) is just ``past += 1``: the next step overwrites it.
 Greedy mode replays one captured HIP graph per token (``_GreedyGraph``: position,
 output column and finished flags live on the device; ``MVLT_DECODE_GRAPH=0`` selects
-the eager loop, which 'sample' mode always uses).
+the eager loop).  'sample' mode (B <= 64) is the same graph with the Gumbel-max pick of ``mvlt_gemm_sample_step`` as
+its head: the token of output column c is ``argmax_n (logit_n / T + G_n)`` with the noise a pure function of
+``(seed, SAMPLE_TAG0 + c, row * V + n)``, so the graph loop and the eager loop draw the same tokens from the same seed.
 Beam search (``beam_search``): same cached steps over B*beams rows, cache rows gathered by beam
 index, scorer bookkeeping restated from HF transformers 4.16 (parity with the reference unpinned).
 """
@@ -31,6 +33,9 @@ from .runtime import compute_dtype_of
 # LayerNorm launch behind them adds in slice order (round 5: no float atomics -- bf16 greedy decoding is reproducible run to run)
 _SKINNY_SPLIT = True
 _SPLITS = (2, 4)      # reduction splits of (attention output, FFN-out) projections: the fastest of the round-2 sweep
+# noise tags of sampled decoding: output column c draws with tag SAMPLE_TAG0 + c (the seed is the call's own, so the range
+# cannot meet the dropout / DropPath / MLM-mask tags of a training step, which hash their step seed)
+SAMPLE_TAG0 = 0x53000000
 
 
 def _layers_cached(mv, ar, x, kc, vc, past, n_new, out_last=None):
@@ -141,7 +146,7 @@ class _GreedyGraph:
     def __reduce__(self):                 # captured graphs do not survive pickling: rebuilt on the next call
         return (_no_graph, ())
 
-    def __init__(self, model, B, n_img, max_length, cd, pad, eos, mask_id, key):
+    def __init__(self, model, B, n_img, max_length, cd, pad, eos, mask_id, key, mode='greedy', temperature=1.0):
         mv, cfg = model.MVLBert, model.config
         dev = next(model.parameters()).device
         H, nH = cfg.hidden_size, cfg.num_attention_heads
@@ -163,7 +168,12 @@ class _GreedyGraph:
         self.cd, self.graph = cd, None
         # device-side state of the greedy loop, handed to mvlt_gemm_argmax_greedy: the pick, PAD for finished samples, the
         # EOS flags, the ids / scores columns, the next input id, `past` and `col` are all advanced by its finishing launch
-        st = self.state = L.MvltGreedyState()
+        # (mode 'sample': mvlt_gemm_sample_step, the same state plus the seed cell the loop fills before the first replay)
+        self.mode = mode
+        self.seed = torch.zeros(1, dtype=torch.int64, device=dev)
+        st = self.state = L.MvltGreedyState() if mode == 'greedy' else L.MvltSampleState()
+        if mode != 'greedy':
+            st.seed, st.tag0, st.inv_temperature = self.seed.data_ptr(), SAMPLE_TAG0, 1.0 / float(temperature)
         st.unfinished, st.eos_id, st.pad_id, st.has_eos = self.unfinished.data_ptr(), (eos if eos is not None else -1), pad, int(eos is not None)
         st.col, st.past = self.col.data_ptr(), self.past.data_ptr()
         st.ids, st.ld_ids, st.scores, st.ld_scores = self.ids.data_ptr(), max_length, self.scores.data_ptr(), max_length
@@ -178,7 +188,8 @@ class _GreedyGraph:
         hd = model.MLM_head_seq2seq
         _, _, t2, _, _ = hd._transform(ar, self.hlast, False)
         # decoder GEMM fused with the greedy pick and its bookkeeping: the [B, 30522] logits are never written
-        ops.gemm_argmax_greedy(t2, ar.compute(hd.predictions.decoder.weight), hd.predictions.decoder.bias.data, self.state)
+        pick = ops.gemm_argmax_greedy if self.mode == 'greedy' else ops.gemm_sample_step
+        pick(t2, ar.compute(hd.predictions.decoder.weight), hd.predictions.decoder.bias.data, self.state)
 
     def forward2(self):
         """2-token cached forward of [last token, MASK] at positions past, past+1 (model.py:82-108).  `past` was advanced by
@@ -204,18 +215,22 @@ class _GreedyGraph:
         self.graph = g
 
 
-def _greedy_graph_loop(model, feat, max_length, pad, eos, mask_id, cd):
+def _greedy_graph_loop(model, feat, max_length, pad, eos, mask_id, cd, mode='greedy', seed=0, temperature=1.0):
     mv, cfg = model.MVLBert, model.config
     B, n_img, H = feat.shape
     nH = cfg.num_attention_heads
     nl = len(mv.encoder.layer)
     ar = Arena.of(model, cd)
     key = (B, n_img, max_length, cd, pad, eos, mask_id, ar.flat.data_ptr(), feat.device.index)
-    gg = model.__dict__.get("_mvlt_greedy_graph")
+    slot = "_mvlt_greedy_graph"
+    if mode != 'greedy':          # a graph of its own beside the greedy one: neither recaptures the other
+        key, slot = key + (mode, float(temperature)), "_mvlt_sample_graph"
+    gg = model.__dict__.get(slot)
     if gg is None or gg.key != key:
-        gg = _GreedyGraph(model, B, n_img, max_length, cd, pad, eos, mask_id, key)
+        gg = _GreedyGraph(model, B, n_img, max_length, cd, pad, eos, mask_id, key, mode, temperature)
         gg.capture()
-        model.__dict__["_mvlt_greedy_graph"] = gg
+        model.__dict__[slot] = gg
+    gg.seed.fill_(ops.s64(int(seed) & ((1 << 64) - 1)))
     # ---- step 0: [CLS] img [SEP] [MASK], full seq2seq forward (model.py:110-160), eager
     mask_col = gg.new_ids[:, 1:2].contiguous()
     hidden, _, saved = mv._forward(feat, mask_col, mask_col, None, True, True)
@@ -247,9 +262,12 @@ def _greedy_graph_loop(model, feat, max_length, pad, eos, mask_id, cd):
 
 @torch.no_grad()
 def greedy_search(model, image_feature, learning_strategy='unilm', sample_mode='greedy', max_length=None,
-                  pad_token_id=None, eos_token_id=None):
+                  pad_token_id=None, eos_token_id=None, seed=None, temperature=1.0):
     """Returns ``(input_ids [B, n_steps], token_scores)`` like the reference
-    (model.py:984: scores of all but the final step, concatenated along dim -1)."""
+    (model.py:984: scores of all but the final step, concatenated along dim -1).
+    ``sample_mode='sample'``, B <= 64: Gumbel-max draws from softmax(logits / temperature), reproducible from ``seed``
+    (None: a 63-bit seed from torch's default CPU generator, so torch.manual_seed makes a run reproducible); the graph
+    loop and the eager loop give the same tokens.  B > 64 samples with torch.multinomial (seed / temperature unused)."""
     if learning_strategy != 'unilm':
         raise NotImplementedError("only learning_strategy='unilm' is coherent with the KV cache (SURVEY.md 3.3)")
     mv, cfg = model.MVLBert, model.config
@@ -265,6 +283,14 @@ def greedy_search(model, image_feature, learning_strategy='unilm', sample_mode='
     # (the fused decoder-GEMM + argmax of the graph path holds the whole batch in one 64-row tile)
     if sample_mode == 'greedy' and os.environ.get("MVLT_DECODE_GRAPH", "1") == "1" and feat.shape[0] <= 64:
         return _greedy_graph_loop(model, feat, max_length, pad, eos, mask_id, cd)
+    fused_sample = sample_mode == 'sample' and feat.shape[0] <= 64
+    if fused_sample:
+        if not float(temperature) > 0.0:
+            raise ValueError("temperature must be positive")
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        if os.environ.get("MVLT_DECODE_GRAPH", "1") == "1":
+            return _greedy_graph_loop(model, feat, max_length, pad, eos, mask_id, cd, 'sample', seed, temperature)
     B, n_img, H = feat.shape
     nH = cfg.num_attention_heads
     hd = H // nH
@@ -281,6 +307,9 @@ def greedy_search(model, image_feature, learning_strategy='unilm', sample_mode='
         pre, t1, t2, _, _ = head._transform(ar, hlast.contiguous(), False)
         if sample_mode == 'greedy' and t2.shape[0] <= 64:
             return ops.gemm_argmax(t2, ar.compute(head.predictions.decoder.weight), head.predictions.decoder.bias.data)
+        if fused_sample:              # the pick of the graph loop, stand-alone: same seed, tag and column -> same tokens
+            return ops.gemm_sample(t2, ar.compute(head.predictions.decoder.weight), head.predictions.decoder.bias.data,
+                                   seed, SAMPLE_TAG0 + len(ids_cols), temperature)
         logits, _ = head._logits(ar, t2)
         if sample_mode == 'greedy':
             nxt = ops.argmax(logits, V)

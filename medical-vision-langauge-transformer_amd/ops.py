@@ -356,6 +356,57 @@ def gemm_argmax_greedy(A, W, bias, state):
 _argmax_parts = {}
 
 
+def _sample_parts(M, N, device):
+    nblk = (N + 15) // 16
+    key = ("sample_parts", M, nblk, device.index, _stream_cache[1])      # a captured graph keeps its own (addresses are recorded)
+    buf = _argmax_parts.get(key)
+    if buf is None:
+        buf = _argmax_parts[key] = (torch.empty((4, M, nblk), dtype=torch.float32, device=device),
+                                    torch.empty((M, nblk), dtype=torch.int32, device=device))
+    return buf
+
+
+def _sample_gemm(A, W, bias):
+    _need_cuda(A, W)
+    M, K = A.shape
+    N = W.shape[0]
+    p = L.MvltGemm()
+    p.dtype, p.M, p.N, p.K = _dt(A), M, N, K
+    p.A, p.lda, p.B, p.ldb = _p(A), _ld(A), _p(W), _ld(W)
+    if bias is not None:
+        assert bias.dtype == torch.float32 and bias.numel() == N
+        p.epilogue, p.bias = L.EPI_BIAS, _p(bias)
+    return p, M, N
+
+
+def gemm_sample(A, W, bias, seed, tag, temperature=1.0):
+    """One draw per row from softmax((A @ W^T + bias) / temperature) by Gumbel-max and its log-probability, without
+    materialising the logits (mvlt_gemm_sample; the noise is a pure function of (seed, tag, row, column)).
+    A: [M <= 64, K] (rows may be strided), W: [N, K] -> (int64 [M], f32 [M])."""
+    p, M, N = _sample_gemm(A, W, bias)
+    pv, pi = _sample_parts(M, N, A.device)
+    idx = torch.empty(M, dtype=torch.int64, device=A.device)
+    lp = torch.empty(M, dtype=torch.float32, device=A.device)
+    L.check(L.lib().mvlt_gemm_sample(C.byref(p), _p(pv), _p(pi), _p(idx), _p(lp), int(seed) & ((1 << 64) - 1), int(tag) & 0xFFFFFFFF,
+                                     1.0 / float(temperature), _stream()), "mvlt_gemm_sample")
+    return idx, lp
+
+
+def gemm_sample_step(A, W, bias, state):
+    """Decoder GEMM + sampled pick + the per-token bookkeeping of greedy_search in two launches (mvlt_gemm_sample_step).
+    ``state``: a prepared ``L.MvltSampleState`` (decode._GreedyGraph, mode 'sample')."""
+    p, M, N = _sample_gemm(A, W, bias)
+    pv, pi = _sample_parts(M, N, A.device)
+    L.check(L.lib().mvlt_gemm_sample_step(C.byref(p), _p(pv), _p(pi), C.byref(state), _stream()), "mvlt_gemm_sample_step")
+
+
+def gumbel_noise(seed, tag, rows, N, device):
+    """The noise of gemm_sample as the kernel computes it, f32 [rows, N] (tests)."""
+    out = torch.empty((rows, N), dtype=torch.float32, device=device)
+    L.check(L.lib().mvlt_gumbel_noise(int(seed) & ((1 << 64) - 1), int(tag) & 0xFFFFFFFF, rows, N, _p(out), _stream()), "mvlt_gumbel_noise")
+    return out
+
+
 def gemm_skinny_accum(A, W, acc, k_splits):
     """acc[s] (f32 [k_splits, M, N]) = A[:, k-slice s] @ W[:, k-slice s]^T: the reduction split over k_splits workgroups per
     column tile, every slice in a slab of its own (no atomics; layernorm_acc_fwd adds them in slice order)."""
