@@ -66,7 +66,7 @@ MVLT_DEV bool rng_keep(uint64_t seed, uint32_t tag, uint32_t idx, uint32_t thres
 }
 
 // Standard Gumbel noise g = -log(-log(u01)), u01 = ((rng_u32 >> 8) + 0.5) 2^-24 (never 0 or 1, so g is finite: -2.86 .. 17.33),
-// for Gumbel-max sampling (gemm.hip: sampled pick).  With k = rng_u32 >> 8, k + 0.5 has 25 significant bits and is exact in f32
+// for Gumbel-max sampling (skinny.hip: sampled pick).  With k = rng_u32 >> 8, k + 0.5 has 25 significant bits and is exact in f32
 // only below 2^23; above, h = fl(k + 0.5) is k or k + 1 and the remainder l = (k - h) + 0.5 in {-0.5, 0, +0.5} is exact, so
 //     t = -log(u01) = -(log(h 2^-24) + log1p(l / h)),   log1p(l / h) = l / h up to (l / h)^2 / 2 <= 2^-49
 // keeps t RELATIVELY accurate where u01 -> 1 (t -> 2^-25; fl(k + 0.5) alone would give u01 = 1 and g = inf at k = 2^24 - 1).

@@ -1,4 +1,4 @@
-// Device-side pieces shared by the GEMM translation units (gemm.hip, gemm8.hip): the kernel argument block, the
+// Device-side pieces shared by the GEMM translation units (gemm.hip, skinny.hip, gemm8.hip, rowstream.hip): the kernel argument block, the
 // fused epilogue (order documented in include/mvlt_hip.h, MvltGemm), the XCD-aware tile order and the weight prefetch.
 #pragma once
 #include "common.h"

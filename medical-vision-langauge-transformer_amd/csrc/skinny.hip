@@ -1,0 +1,632 @@
+// Everything the decode path runs at M <= 64 (see include/mvlt_hip.h): the skinny product behind mvlt_gemm, its K-split form
+// (mvlt_gemm_skinny_accum), and the MLM head fused with the pick of the next token -- greedy (mvlt_gemm_argmax,
+// mvlt_gemm_argmax_greedy) and sampled (mvlt_gemm_sample, mvlt_gemm_sample_step).  No LDS staging anywhere: the weight matrix is
+// read once and nothing is reused inside a workgroup, so every wave loads its MFMA fragments straight from global memory.
+// Same argument block as the tile kernels of gemm.hip (gemm_dev.h); gemm.hip reaches the plain product through mvlt_skinny_try.
+#include "common.h"
+#include "gemm_dev.h"
+#include "gemm_host.h"
+
+namespace {
+
+// (value, index) picks: the candidate (ov, oi) replaces the best so far (v, i) when it is larger, or equal with a LOWER index -- the
+// first index of the maximum is what the greedy tests pin, and this is the one place the rule is written.  A macro, not a
+// function: hipcc schedules every kernel below differently as soon as the comparison sits behind a call, inlined or not
+// (profiles/skinny_split_isa.md).
+#define BEATS(ov, oi, v, i) ((ov) > (v) || ((ov) == (v) && (oi) < (i)))
+
+// Skinny products (M <= 64: the 2-token decode step, poolers, classifier heads): the weight matrix is read once
+// and nothing is reused inside a workgroup, so there is no LDS staging -- every wave loads its MFMA fragments
+// straight from global memory (16 B per lane, k-contiguous rows).  Workgroup = 16 output columns x all rows;
+// its 8 waves split K (3 k-blocks in flight per wave: the loop is latency bound, so memory-level parallelism is
+// what matters), partial accumulators meet in LDS, wave i < 4 finishes row tile i.
+constexpr int SKINNY_WAVES = 8, SKINNY_UNROLL = 3;
+// ARGMAX (greedy decoding, model.py:896-900): instead of storing the logits, every workgroup reduces its 16
+// columns to (max, first index of the max) per row -> part_val/part_idx [M][gridDim.x]; argmax_parts_kernel
+// finishes the rows.  The maximum is taken over the f32 accumulators (+ bias).
+struct ArgmaxOut { float* part_val; int* part_idx; };
+// Weight fragments of the skinny products: every workgroup reads ITS 16 (or 128) weight rows exactly once, and in decoding the
+// 217 MB of weights + ~150 MB of K / V rows per step cycle through a 256 MB Infinity Cache -- non-temporal loads
+// (MI355X_MICROARCH.md "nt-weights": once-read streamed weights, 5-10 % per decode layer).  -DMVLT_SKINNY_NT=0 restores the
+// default cache policy (A/B builds).
+#ifndef MVLT_SKINNY_NT
+#define MVLT_SKINNY_NT 1
+#endif
+template <typename F> MVLT_DEV F skinny_wload(const F* q) {
+#if MVLT_SKINNY_NT
+    return __builtin_nontemporal_load(q);
+#else
+    return *q;
+#endif
+}
+template <typename T, bool ARGMAX = false>
+__global__ __launch_bounds__(64 * SKINNY_WAVES) void gemm_skinny_kernel(const GemmDev p_in, const ArgmaxOut am) {
+    const GemmDev p = effective<false>(p_in);          // ragged row counts (m_dev): rows beyond it are neither read nor written
+    if (p.M <= 0) return;
+    using M_ = Mma<T>;
+    using Frag = typename M_::Frag;
+    constexpr int KB = M_::KB, E = TypeInfo<T>::E;
+    __shared__ f32x4 red[SKINNY_WAVES][4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r15 = lane & 15, g = lane >> 4;
+    const int n0 = blockIdx.x * 16;
+    const T* A = reinterpret_cast<const T*>(p.A);
+    const T* B = reinterpret_cast<const T*>(p.B);
+    const T* brow = B + (long)min(n0 + r15, p.N - 1) * p.ldb + g * E;
+    const T* arow[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) arow[i] = A + (long)min(16 * i + r15, p.M - 1) * p.lda + g * E;
+    f32x4 acc[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // the finishing waves fetch their bias / residual values now, so the epilogue does not start with a
+    // dependent memory round trip (the decode step is a chain of ~100 such kernels)
+    constexpr int FASTMASK = MVLT_EPI_BIAS | MVLT_EPI_GELU | MVLT_EPI_RESIDUAL;
+    const bool fast_epi = !ARGMAX && (p.epi & ~FASTMASK) == 0 && p.epi_vec && n0 + 16 <= p.N && wave < 4 && 16 * wave + r15 < p.M;
+    f32x4 pre_bias{0.f, 0.f, 0.f, 0.f}, pre_res{0.f, 0.f, 0.f, 0.f};
+    if (fast_epi) {
+        if (p.epi & MVLT_EPI_BIAS) pre_bias = *reinterpret_cast<const f32x4*>(p.bias + n0 + 4 * g);
+        if (p.epi & MVLT_EPI_RESIDUAL)
+            pre_res = load4f(reinterpret_cast<const T*>(p.residual) + (long)(16 * wave + r15) * p.ldr + n0 + 4 * g);
+    }
+    const int nkb = p.K / KB;
+    for (int kb0 = wave; kb0 < nkb; kb0 += SKINNY_WAVES * SKINNY_UNROLL) {
+        Frag fb[SKINNY_UNROLL], fa[SKINNY_UNROLL][4];
+#pragma unroll
+        for (int u = 0; u < SKINNY_UNROLL; ++u) {
+            const int kb = kb0 + u * SKINNY_WAVES;
+            const int k = (kb < nkb ? kb : kb0) * KB;          // past the end: reload a valid block, never multiplied
+            fb[u] = skinny_wload(reinterpret_cast<const Frag*>(brow + k));
+#pragma unroll
+            for (int i = 0; i < 4; ++i) fa[u][i] = *reinterpret_cast<const Frag*>(arow[i] + k);
+        }
+#pragma unroll
+        for (int u = 0; u < SKINNY_UNROLL; ++u) {
+            if (kb0 + u * SKINNY_WAVES < nkb) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) M_::mma(acc[i], fb[u], fa[u][i]);
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) red[wave][i][lane] = acc[i];
+    __syncthreads();
+    const int i = wave;                                  // row tile finished by this wave
+    if (i < 4 && 16 * i < p.M) {
+        f32x4 v = red[0][i][lane];
+#pragma unroll
+        for (int w = 1; w < SKINNY_WAVES; ++w) v += red[w][i][lane];
+        // acc[r] <-> n = n0 + 4*g + r, m = 16*i + (lane & 15)   (same orientation as gemm_body)
+        if (!ARGMAX) {
+            if (fast_epi) {
+                f32x4 o = v + pre_bias;
+                if (p.epi & MVLT_EPI_GELU) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) o[r] = gelu_f(o[r]);
+                }
+                o += pre_res;
+                store4f(reinterpret_cast<T*>(p.C) + (long)(16 * i + r15) * p.ldc + n0 + 4 * g, o);
+            } else {
+                epilogue4<T>(p, 16 * i + r15, n0 + 4 * g, v);
+            }
+        } else {
+            float best = -3.0e38f; int bi = 0x7fffffff;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int n = n0 + 4 * g + r;
+                if (n < p.N) {
+                    const float x = v[r] + ((p.epi & MVLT_EPI_BIAS) ? p.bias[n] : 0.f);
+                    if (x > best) { best = x; bi = n; }          // ascending n: ties keep the first index
+                }
+            }
+#pragma unroll
+            for (int o = 16; o < 64; o <<= 1) {
+                const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
+                if (BEATS(ov, oi, best, bi)) { best = ov; bi = oi; }
+            }
+            const int m = 16 * i + r15;
+            if (g == 0 && m < p.M) { am.part_val[(long)m * gridDim.x + blockIdx.x] = best; am.part_idx[(long)m * gridDim.x + blockIdx.x] = bi; }
+        }
+    }
+}
+
+// Skinny product with K split over workgroups (decode: M = 2B rows, N = 768, K = 768 / 3072).  The plain skinny kernel
+// gives every 16-column workgroup the WHOLE activation matrix to read (N/16 x M x K bytes through L2: 48 x 393 KB for
+// the FFN-out product, 10 us per workgroup at the ~50 GB/s a CU takes in); here workgroup (j, s) reads only k-slice s
+// of it and writes its partial 64x16 tile into the slab of its slice.  No epilogue: the consumer
+// (mvlt_layernorm_acc_fwd: sum of the slices + bias + residual, LayerNorm) is the launch that follows anyway.
+template <typename T>
+__global__ __launch_bounds__(64 * SKINNY_WAVES) void gemm_skinny_accum_kernel(const GemmDev p, float* accout) {
+    using M_ = Mma<T>;
+    using Frag = typename M_::Frag;
+    constexpr int KB = M_::KB, E = TypeInfo<T>::E;
+    __shared__ f32x4 red[SKINNY_WAVES][4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r15 = lane & 15, g = lane >> 4;
+    const int n0 = blockIdx.x * 16;
+    const T* A = reinterpret_cast<const T*>(p.A);
+    const T* B = reinterpret_cast<const T*>(p.B);
+    const T* brow = B + (long)min(n0 + r15, p.N - 1) * p.ldb + g * E;
+    const T* arow[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) arow[i] = A + (long)min(16 * i + r15, p.M - 1) * p.lda + g * E;
+    f32x4 acc[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int nkb = p.K / KB;
+    const int per = (nkb + (int)gridDim.y - 1) / (int)gridDim.y;
+    const int kb_lo = blockIdx.y * per, kb_hi = min(nkb, kb_lo + per);
+    for (int kb0 = kb_lo + wave; kb0 < kb_hi; kb0 += SKINNY_WAVES * SKINNY_UNROLL) {
+        Frag fb[SKINNY_UNROLL], fa[SKINNY_UNROLL][4];
+#pragma unroll
+        for (int u = 0; u < SKINNY_UNROLL; ++u) {
+            const int kb = kb0 + u * SKINNY_WAVES;
+            const int k = (kb < kb_hi ? kb : kb0) * KB;
+            fb[u] = skinny_wload(reinterpret_cast<const Frag*>(brow + k));
+#pragma unroll
+            for (int i = 0; i < 4; ++i) fa[u][i] = *reinterpret_cast<const Frag*>(arow[i] + k);
+        }
+#pragma unroll
+        for (int u = 0; u < SKINNY_UNROLL; ++u) {
+            if (kb0 + u * SKINNY_WAVES < kb_hi) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) M_::mma(acc[i], fb[u], fa[u][i]);
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) red[wave][i][lane] = acc[i];
+    __syncthreads();
+    const int i = wave;
+    if (i < 4 && 16 * i + r15 < p.M) {
+        f32x4 v = red[0][i][lane];
+#pragma unroll
+        for (int w = 1; w < SKINNY_WAVES; ++w) v += red[w][i][lane];
+        // slab of this k-slice: [gridDim.y][M][N] f32, written once with plain stores; the consumer (ln_acc_fwd_kernel) adds the
+        // slices in slice order -- no float atomics, no zeroing pass, bit-reproducible (round 5; the atomic form cost ~1 us more)
+        float* c = accout + ((long)blockIdx.y * p.M + 16 * i + r15) * p.N + n0 + 4 * g;
+        if (n0 + 4 * g + 4 <= p.N) store4f(c, v);
+        else
+#pragma unroll
+            for (int r = 0; r < 4; ++r) if (n0 + 4 * g + r < p.N) c[r] = v[r];
+    }
+}
+
+// one wave per row: (max, first index) over the workgroup partials
+__global__ __launch_bounds__(64) void argmax_parts_kernel(const float* part_val, const int* part_idx, int nparts,
+                                                          int64_t* out_idx, float* out_val) {
+    const long base = (long)blockIdx.x * nparts;
+    float best = -3.0e38f; int bi = 0x7fffffff;
+    for (int i = threadIdx.x; i < nparts; i += 64) {
+        const float v = part_val[base + i]; const int idx = part_idx[base + i];
+        if (BEATS(v, idx, best, bi)) { best = v; bi = idx; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
+        if (BEATS(ov, oi, best, bi)) { best = ov; bi = oi; }
+    }
+    if (threadIdx.x == 0) { out_idx[blockIdx.x] = bi; if (out_val) out_val[blockIdx.x] = best; }
+}
+
+// Decoder GEMM of the last-row MLM head fused with the greedy pick, wide form (round 5): a workgroup = 128 vocabulary columns,
+// wave w = columns 16 w .. +16 over the WHOLE reduction -- no k-split across waves, so no LDS reduction and no barrier; the
+// 47 MB weight matrix is streamed once by 239 workgroups (one per CU) with UNR k-blocks in flight per wave, the 32-64
+// activation rows come from L1 / L2.  The 16-column form above launches 1,908 workgroups that each re-read the whole
+// activation matrix and meet in LDS: 29 us for a product whose bytes take 9 us.  Same partial layout (one (max, index) per row
+// and 16 columns), so the finishing kernel is shared.
+template <typename T, int NRT>
+__global__ __launch_bounds__(64 * SKINNY_WAVES) void gemm_argmax128_kernel(const GemmDev p, const ArgmaxOut am, int nparts) {
+    using M_ = Mma<T>;
+    using Frag = typename M_::Frag;
+    constexpr int KB = M_::KB, E = TypeInfo<T>::E, UNR = NRT <= 2 ? 12 : 8;          // k-blocks in flight per wave (12 KB of weights; K = 768 in two rounds)
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), r15 = lane & 15, g = lane >> 4;
+    const int n0 = (blockIdx.x * SKINNY_WAVES + wave) * 16;
+    if (n0 >= p.N) return;
+    const T* A = reinterpret_cast<const T*>(p.A);
+    const T* brow = reinterpret_cast<const T*>(p.B) + (long)min(n0 + r15, p.N - 1) * p.ldb + g * E;
+    const T* arow[NRT];
+#pragma unroll
+    for (int i = 0; i < NRT; ++i) arow[i] = A + (long)min(16 * i + r15, p.M - 1) * p.lda + g * E;
+    f32x4 acc[NRT];
+#pragma unroll
+    for (int i = 0; i < NRT; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int nkb = p.K / KB;
+    for (int kb0 = 0; kb0 < nkb; kb0 += UNR) {
+        Frag fb[UNR], fa[UNR][NRT];
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            const int k = min(kb0 + u, nkb - 1) * KB;          // past the end: reload the last block, never multiplied
+            fb[u] = skinny_wload(reinterpret_cast<const Frag*>(brow + k));
+#pragma unroll
+            for (int i = 0; i < NRT; ++i) fa[u][i] = *reinterpret_cast<const Frag*>(arow[i] + k);
+        }
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            if (kb0 + u < nkb) {
+#pragma unroll
+                for (int i = 0; i < NRT; ++i) M_::mma(acc[i], fb[u], fa[u][i]);
+            }
+        }
+    }
+    // acc[i][r] <-> n = n0 + 4 g + r, m = 16 i + r15
+    f32x4 bias4{0.f, 0.f, 0.f, 0.f};
+    if (p.epi & MVLT_EPI_BIAS) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bias4[r] = p.bias[min(n0 + 4 * g + r, p.N - 1)];
+    }
+    const int part = blockIdx.x * SKINNY_WAVES + wave;
+#pragma unroll
+    for (int i = 0; i < NRT; ++i) {
+        float best = -3.0e38f; int bi = 0x7fffffff;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int n = n0 + 4 * g + r;
+            const float x = acc[i][r] + bias4[r];
+            if (n < p.N && x > best) { best = x; bi = n; }          // ascending n: ties keep the first index
+        }
+#pragma unroll
+        for (int o = 16; o < 64; o <<= 1) {
+            const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
+            if (BEATS(ov, oi, best, bi)) { best = ov; bi = oi; }
+        }
+        const int m = 16 * i + r15;
+        if (g == 0 && m < p.M) { am.part_val[(long)m * nparts + part] = best; am.part_idx[(long)m * nparts + part] = bi; }
+    }
+}
+
+// Finish of the greedy pick for ALL rows in one workgroup, with the per-token bookkeeping of greedy_search (model.py:896-913)
+// folded in: next = argmax; finished samples emit PAD; unfinished &= (next != EOS); ids[:, col] = next; scores[:, col] = max
+// logit; new_ids[:, 0] = next (the first of the two tokens the next cached step feeds); alive[col] = any sample unfinished;
+// past += 1 (the cache position the NEXT forward reads: the previous step's [MASK] slot is overwritten); col += 1.
+// Replaces argmax_parts_kernel + ten one-line torch kernels per replayed decode step.  M <= 64; 16 waves, wave w = rows w, w + 16, ...
+struct GreedyState {
+    int64_t* unfinished; int64_t eos, pad; int has_eos;
+    int64_t* col; int32_t* past;
+    int64_t* ids; long ld_ids; float* scores; long ld_scores; int64_t* alive; int64_t* new_ids; long ld_new;
+    int32_t* ticket;
+};
+// The per-token bookkeeping both pick kernels end with (one thread per row): `tok` is the row's pick, `score` what goes into
+// scores[:, col] -- of the PICKED token also for a finished row (the reference gathers the score before PAD replaces the token).
+MVLT_DEV void pick_bookkeeping(const GreedyState& st, const int m, const int M, const long col, const int tok, const float score) {
+    int64_t nxt = tok;
+    if (st.has_eos) {
+        const int64_t unf = st.unfinished[m];
+        nxt = nxt * unf + st.pad * (1 - unf);
+        const int64_t unf2 = unf * (nxt != st.eos ? 1 : 0);
+        st.unfinished[m] = unf2;
+        if (unf2) atomicMax(reinterpret_cast<unsigned long long*>(st.alive + col), 1ULL);
+    }
+    st.ids[(long)m * st.ld_ids + col] = nxt;
+    st.scores[(long)m * st.ld_scores + col] = score;
+    st.new_ids[(long)m * st.ld_new] = nxt;
+    __threadfence();
+    if (atomicAdd(st.ticket, 1) == M - 1) {
+        *st.ticket = 0;
+        st.col[0] = col + 1;
+        if (st.past) st.past[0] += 1;
+    }
+}
+// One workgroup per row (256 threads: ~8 partials per thread, one memory round trip; a single workgroup walking all rows took
+// 26 us).  alive[col] is raised with an atomic max by the rows that are still unfinished (the caller zeroes `alive` when a
+// decode starts); the LAST workgroup to arrive (ticket) advances col and past and re-arms the ticket.  Every workgroup reads
+// col before it draws its ticket, and col is written only after all tickets are drawn.
+__global__ __launch_bounds__(256) void greedy_pick_kernel(const float* part_val, const int* part_idx, int nparts, int M, const GreedyState st) {
+    __shared__ float s_val[4];
+    __shared__ int s_idx[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = blockIdx.x;
+    const long col = st.col[0];
+    const long base = (long)m * nparts;
+    float best = -3.0e38f; int bi = 0x7fffffff;
+    for (int i = threadIdx.x; i < nparts; i += 256) {
+        const float v = part_val[base + i]; const int idx = part_idx[base + i];
+        if (BEATS(v, idx, best, bi)) { best = v; bi = idx; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
+        if (BEATS(ov, oi, best, bi)) { best = ov; bi = oi; }
+    }
+    if (lane == 0) { s_val[wave] = best; s_idx[wave] = bi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 1; w < 4; ++w) {
+            const float ov = s_val[w]; const int oi = s_idx[w];
+            if (BEATS(ov, oi, best, bi)) { best = ov; bi = oi; }
+        }
+        pick_bookkeeping(st, m, M, col, bi, best);
+    }
+}
+
+// SAMPLED pick (greedy_search 'sample' mode, model.py:901-906): multinomial(softmax(x)) is argmax_n (x_n + G_n) with i.i.d.
+// standard Gumbel noise G (Gumbel-max), so the sampled step is the greedy product with a noise term in the epilogue and an online
+// log-sum-exp beside the running maximum (the score is the log-probability of the drawn token).  Sibling of
+// gemm_argmax128_kernel: the same main loop (two copies: behind a shared helper hipcc schedules both differently, profiles/skinny_split_isa.md); epilogue
+// per element (m, n), all in f32, no fused multiply-add:
+//     x = (acc + bias[n]) * inv_temperature;   y = x + gumbel_noise(seed, tag0 + step, m N + n)      (common.h)
+// seed = *seed_dev and step = *col are read from device memory (one captured graph serves every call and every token).
+// Per row and 16-column part it writes five values, part_val[j][m][part]: j = 0 max y, 1 x at that index, 2 max x,
+// 3 sum exp(x - max x); part_idx[m][part] = first index of max y.  Columns n >= N take part in neither.
+struct SampleIn { const uint64_t* seed_dev; uint64_t seed; const int64_t* col; uint32_t tag0; float inv_t; };
+template <typename T, int NRT>
+__global__ __launch_bounds__(64 * SKINNY_WAVES) void gemm_sample128_kernel(const GemmDev p, float* part_val, int* part_idx, int nparts, const SampleIn si) {
+    using M_ = Mma<T>;
+    using Frag = typename M_::Frag;
+    constexpr int KB = M_::KB, E = TypeInfo<T>::E, UNR = NRT <= 2 ? 12 : 8;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), r15 = lane & 15, g = lane >> 4;
+    const int n0 = (blockIdx.x * SKINNY_WAVES + wave) * 16;
+    if (n0 >= p.N) return;
+    const uint64_t seed = si.seed_dev ? si.seed_dev[0] : si.seed;
+    const uint32_t tag = si.tag0 + (si.col ? (uint32_t)si.col[0] : 0u);
+    const T* A = reinterpret_cast<const T*>(p.A);
+    const T* brow = reinterpret_cast<const T*>(p.B) + (long)min(n0 + r15, p.N - 1) * p.ldb + g * E;
+    const T* arow[NRT];
+#pragma unroll
+    for (int i = 0; i < NRT; ++i) arow[i] = A + (long)min(16 * i + r15, p.M - 1) * p.lda + g * E;
+    f32x4 acc[NRT];
+#pragma unroll
+    for (int i = 0; i < NRT; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int nkb = p.K / KB;
+    for (int kb0 = 0; kb0 < nkb; kb0 += UNR) {
+        Frag fb[UNR], fa[UNR][NRT];
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            const int k = min(kb0 + u, nkb - 1) * KB;          // past the end: reload the last block, never multiplied
+            fb[u] = skinny_wload(reinterpret_cast<const Frag*>(brow + k));
+#pragma unroll
+            for (int i = 0; i < NRT; ++i) fa[u][i] = *reinterpret_cast<const Frag*>(arow[i] + k);
+        }
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            if (kb0 + u < nkb) {
+#pragma unroll
+                for (int i = 0; i < NRT; ++i) M_::mma(acc[i], fb[u], fa[u][i]);
+            }
+        }
+    }
+    // acc[i][r] <-> n = n0 + 4 g + r, m = 16 i + r15
+    f32x4 bias4{0.f, 0.f, 0.f, 0.f};
+    if (p.epi & MVLT_EPI_BIAS) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bias4[r] = p.bias[min(n0 + 4 * g + r, p.N - 1)];
+    }
+    const int part = blockIdx.x * SKINNY_WAVES + wave;
+    const long plane = (long)p.M * nparts;
+#pragma unroll
+    for (int i = 0; i < NRT; ++i) {
+        const int m = 16 * i + r15;
+        float x[4];
+        float best = -3.0e38f, bx = 0.f, xm = -3.0e38f; int bi = 0x7fffffff;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int n = n0 + 4 * g + r;
+            x[r] = __fmul_rn(__fadd_rn(acc[i][r], bias4[r]), si.inv_t);
+            const float y = __fadd_rn(x[r], gumbel_noise(seed, tag, (uint32_t)m * (uint32_t)p.N + (uint32_t)n));
+            if (n < p.N) {
+                if (y > best) { best = y; bi = n; bx = x[r]; }          // ascending n: ties keep the first index
+                xm = fmaxf(xm, x[r]);
+            }
+        }
+#pragma unroll
+        for (int o = 16; o < 64; o <<= 1) {
+            const float ov = __shfl_xor(best, o, 64), ox = __shfl_xor(bx, o, 64); const int oi = __shfl_xor(bi, o, 64);
+            if (BEATS(ov, oi, best, bi)) { best = ov; bi = oi; bx = ox; }
+            xm = fmaxf(xm, __shfl_xor(xm, o, 64));
+        }
+        // (n0 < N: every part has a valid column, so xm is a logit; __expf of a non-positive argument: v_exp_f32 of x log2 e)
+        float se = 0.f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) se += (n0 + 4 * g + r < p.N) ? __expf(x[r] - xm) : 0.f;
+        se += __shfl_xor(se, 16, 64);
+        se += __shfl_xor(se, 32, 64);
+        if (g == 0 && m < p.M) {
+            const long o = (long)m * nparts + part;
+            part_val[o] = best; part_val[plane + o] = bx; part_val[2 * plane + o] = xm; part_val[3 * plane + o] = se;
+            part_idx[o] = bi;
+        }
+    }
+}
+
+// Finish of the sampled pick, one workgroup per row like greedy_pick_kernel: the parts reduce to the token (first index of the
+// largest y), lse = M + log(sum_parts s_p exp(m_p - M)) with M the row's largest logit, score = x_token - lse (logf: <= 2 ulp).
+// STEP: then the bookkeeping of greedy_pick_kernel; else the stand-alone outputs out_idx / out_logprob.
+template <bool STEP>
+__global__ __launch_bounds__(256) void sample_pick_kernel(const float* part_val, const int* part_idx, int nparts, int M, const GreedyState st,
+                                                          int64_t* out_idx, float* out_logprob) {
+    __shared__ float s_val[4], s_x[4], s_max[4], s_sum[4];
+    __shared__ int s_idx[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = blockIdx.x;
+    const long col = STEP ? st.col[0] : 0;
+    const long base = (long)m * nparts, plane = (long)M * nparts;
+    float best = -3.0e38f, bx = 0.f, xm = -3.0e38f; int bi = 0x7fffffff;
+    for (int i = threadIdx.x; i < nparts; i += 256) {
+        const float v = part_val[base + i]; const int idx = part_idx[base + i];
+        if (BEATS(v, idx, best, bi)) { best = v; bi = idx; bx = part_val[plane + base + i]; }
+        xm = fmaxf(xm, part_val[2 * plane + base + i]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64), ox = __shfl_xor(bx, o, 64); const int oi = __shfl_xor(bi, o, 64);
+        if (BEATS(ov, oi, best, bi)) { best = ov; bi = oi; bx = ox; }
+        xm = fmaxf(xm, __shfl_xor(xm, o, 64));
+    }
+    if (lane == 0) { s_val[wave] = best; s_idx[wave] = bi; s_x[wave] = bx; s_max[wave] = xm; }
+    __syncthreads();
+    xm = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
+    float se = 0.f;
+    for (int i = threadIdx.x; i < nparts; i += 256) se += part_val[3 * plane + base + i] * __expf(part_val[2 * plane + base + i] - xm);
+    se = wave_sum(se);
+    if (lane == 0) s_sum[wave] = se;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 1; w < 4; ++w) {
+            const float ov = s_val[w]; const int oi = s_idx[w];
+            if (BEATS(ov, oi, best, bi)) { best = ov; bi = oi; bx = s_x[w]; }
+        }
+        const float lse = __fadd_rn(xm, logf((s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3])));
+        const float score = __fadd_rn(bx, -lse);
+        if (STEP) pick_bookkeeping(st, m, M, col, bi, score);
+        else { out_idx[m] = bi; out_logprob[m] = score; }
+    }
+}
+
+// --------------------------------------------------------------------------------------------------------------- host
+// run f(T{}) for the product's element type
+template <typename F> int by_dtype(const int dtype, F&& f) {
+    if (dtype == MVLT_BF16) return f(bf16_t{});
+    if (dtype == MVLT_F32) return f(float{});
+    return MVLT_ERR_UNSUPPORTED;
+}
+
+// the one precondition of every kernel in this file
+template <typename T> bool skinny_ok(const MvltGemm* p) { return is_skinny<T>(p) && skinny_loads_ok<T>(p); }
+
+// The kernel argument block of the head products and the K-split product: they read only M N K A lda B ldb epi bias (m_dev); the
+// rest stays zero.
+GemmDev skinny_dev(const MvltGemm* p) {
+    GemmDev d{};
+    d.M = p->M; d.N = p->N; d.K = p->K; d.A = p->A; d.lda = p->lda; d.B = p->B; d.ldb = p->ldb;
+    d.epi = p->epilogue; d.bias = p->bias; d.m_dev = p->m_dev;
+    return d;
+}
+
+// kernel<T, NRT> for the NRT = ceil(M / 16) row tiles of the wide products
+#define LAUNCH_NRT(kernel, T, M, grid, block, s, ...)                                                     \
+    do {                                                                                                  \
+        if ((M) <= 16) hipLaunchKernelGGL((kernel<T, 1>), grid, block, 0, s, __VA_ARGS__);                \
+        else if ((M) <= 32) hipLaunchKernelGGL((kernel<T, 2>), grid, block, 0, s, __VA_ARGS__);           \
+        else if ((M) <= 48) hipLaunchKernelGGL((kernel<T, 3>), grid, block, 0, s, __VA_ARGS__);           \
+        else hipLaunchKernelGGL((kernel<T, 4>), grid, block, 0, s, __VA_ARGS__);                          \
+    } while (0)
+
+int parts_of(const MvltGemm* p) { return ceil_div(p->N, 16); }          // one part per row and 16 columns
+
+// the (max, index) partials per row and 16 columns: wide streaming form for big vocabularies, else the 16-column skinny kernel
+int argmax_products(const MvltGemm* p, float* part_val, int32_t* part_idx, hipStream_t s) {
+    MVLT_CHECK((p->epilogue & ~(MVLT_EPI_BIAS)) == 0, MVLT_ERR_UNSUPPORTED);
+    return by_dtype(p->dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        MVLT_CHECK(skinny_ok<T>(p), MVLT_ERR_UNSUPPORTED);
+        const GemmDev d = skinny_dev(p);
+        const int nblk = parts_of(p);
+        const ArgmaxOut am{part_val, part_idx};
+        const dim3 block(64 * SKINNY_WAVES);
+        if (p->N >= 4096) LAUNCH_NRT(gemm_argmax128_kernel, T, p->M, dim3(ceil_div(nblk, SKINNY_WAVES)), block, s, d, am, nblk);
+        else hipLaunchKernelGGL((gemm_skinny_kernel<T, true>), dim3(nblk), block, 0, s, d, am);
+        return (int)MVLT_OK;
+    });
+}
+
+// the sampled partials: always the wide streaming form (it handles any N; the 16-column skinny kernel has no sampled sibling)
+int sample_products(const MvltGemm* p, float* part_val, int32_t* part_idx, const SampleIn& si, hipStream_t s) {
+    return by_dtype(p->dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        MVLT_CHECK(skinny_ok<T>(p), MVLT_ERR_UNSUPPORTED);
+        const GemmDev d = skinny_dev(p);
+        const int nblk = parts_of(p);
+        LAUNCH_NRT(gemm_sample128_kernel, T, p->M, dim3(ceil_div(nblk, SKINNY_WAVES)), dim3(64 * SKINNY_WAVES), s, d, part_val, part_idx, nblk, si);
+        return (int)MVLT_OK;
+    });
+}
+
+// what mvlt_gemm_argmax_greedy, mvlt_gemm_sample and mvlt_gemm_sample_step ask of the product and the scratch
+int head_check(const MvltGemm* p, const float* part_val, const int32_t* part_idx) {
+    MVLT_CHECK(p && p->A && p->B && part_val && part_idx, MVLT_ERR_ARG);
+    MVLT_CHECK(p->M > 0 && p->M <= 64 && p->N > 0 && p->K > 0 && p->lda > 0 && p->ldb > 0, MVLT_ERR_ARG);
+    MVLT_CHECK(!p->a_kmajor && !p->b_kmajor && (p->epilogue & ~(MVLT_EPI_BIAS)) == 0, MVLT_ERR_UNSUPPORTED);
+    if (p->epilogue & MVLT_EPI_BIAS) MVLT_CHECK(p->bias, MVLT_ERR_ARG);
+    return MVLT_OK;
+}
+int sample_check(const MvltGemm* p, const float* part_val, const int32_t* part_idx, float inv_temperature) {
+    { const int rc = head_check(p, part_val, part_idx); if (rc != MVLT_OK) return rc; }
+    MVLT_CHECK((long)p->M * p->N < (1L << 32) && inv_temperature > 0.f && inv_temperature < 3.0e38f, MVLT_ERR_ARG);
+    return MVLT_OK;
+}
+
+// MvltGreedyState / MvltSampleState (the same bookkeeping fields) -> the pick kernels' argument
+template <typename S> int greedy_state(const S* g, GreedyState& st) {
+    MVLT_CHECK(g->col && g->ticket && g->ids && g->scores && g->new_ids && g->ld_ids > 0 && g->ld_scores > 0 && g->ld_new > 0, MVLT_ERR_ARG);
+    if (g->has_eos) MVLT_CHECK(g->unfinished && g->alive, MVLT_ERR_ARG);
+    st = GreedyState{g->unfinished, g->eos_id, g->pad_id, g->has_eos, g->col, g->past, g->ids, g->ld_ids, g->scores, g->ld_scores, g->alive,
+                     g->new_ids, g->ld_new, g->ticket};
+    return MVLT_OK;
+}
+
+}  // namespace
+
+extern "C" __attribute__((visibility("hidden"))) int mvlt_skinny_try(const MvltGemm* p, const void* dev_block, void* stream) {
+    const GemmDev& d = *reinterpret_cast<const GemmDev*>(dev_block);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int rc = by_dtype(p->dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        if (!skinny_ok<T>(p)) return 0;
+        hipLaunchKernelGGL((gemm_skinny_kernel<T, false>), dim3(ceil_div(p->N, 16)), dim3(64 * SKINNY_WAVES), 0, s, d, ArgmaxOut{nullptr, nullptr});
+        return hipGetLastError() == hipSuccess ? 1 : -1;
+    });
+    return rc == MVLT_ERR_UNSUPPORTED ? 0 : rc;
+}
+
+extern "C" int mvlt_gemm_argmax(const MvltGemm* p, float* part_val, int32_t* part_idx, int64_t* out_idx, float* out_val,
+                                void* stream) {
+    MVLT_CHECK(p && p->A && p->B && part_val && part_idx && out_idx, MVLT_ERR_ARG);
+    MVLT_CHECK(p->M > 0 && p->N > 0 && p->K > 0 && p->lda > 0 && p->ldb > 0, MVLT_ERR_ARG);
+    if (p->epilogue & MVLT_EPI_BIAS) MVLT_CHECK(p->bias, MVLT_ERR_ARG);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    { const int rc = argmax_products(p, part_val, part_idx, s); if (rc != MVLT_OK) return rc; }
+    hipLaunchKernelGGL(argmax_parts_kernel, dim3(p->M), dim3(64), 0, s, part_val, part_idx, parts_of(p), out_idx, out_val);
+    MVLT_LAUNCH_CHECK();
+    return MVLT_OK;
+}
+
+extern "C" int mvlt_gemm_argmax_greedy(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltGreedyState* g, void* stream) {
+    MVLT_CHECK(g, MVLT_ERR_ARG);
+    { const int rc = head_check(p, part_val, part_idx); if (rc != MVLT_OK) return rc; }
+    GreedyState st;
+    { const int rc = greedy_state(g, st); if (rc != MVLT_OK) return rc; }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    { const int rc = argmax_products(p, part_val, part_idx, s); if (rc != MVLT_OK) return rc; }
+    hipLaunchKernelGGL(greedy_pick_kernel, dim3(p->M), dim3(256), 0, s, part_val, part_idx, parts_of(p), p->M, st);
+    MVLT_LAUNCH_CHECK();
+    return MVLT_OK;
+}
+
+extern "C" int mvlt_gemm_sample(const MvltGemm* p, float* part_val, int32_t* part_idx, int64_t* out_idx, float* out_logprob,
+                                uint64_t seed, uint32_t tag, float inv_temperature, void* stream) {
+    { const int rc = sample_check(p, part_val, part_idx, inv_temperature); if (rc != MVLT_OK) return rc; }
+    MVLT_CHECK(out_idx && out_logprob, MVLT_ERR_ARG);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const SampleIn si{nullptr, seed, nullptr, tag, inv_temperature};
+    { const int rc = sample_products(p, part_val, part_idx, si, s); if (rc != MVLT_OK) return rc; }
+    hipLaunchKernelGGL(sample_pick_kernel<false>, dim3(p->M), dim3(256), 0, s, part_val, part_idx, parts_of(p), p->M, GreedyState{}, out_idx, out_logprob);
+    MVLT_LAUNCH_CHECK();
+    return MVLT_OK;
+}
+
+extern "C" int mvlt_gemm_sample_step(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltSampleState* g, void* stream) {
+    MVLT_CHECK(g, MVLT_ERR_ARG);
+    { const int rc = sample_check(p, part_val, part_idx, g->inv_temperature); if (rc != MVLT_OK) return rc; }
+    MVLT_CHECK(g->seed, MVLT_ERR_ARG);
+    GreedyState st;
+    { const int rc = greedy_state(g, st); if (rc != MVLT_OK) return rc; }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const SampleIn si{g->seed, 0, g->col, g->tag0, g->inv_temperature};
+    { const int rc = sample_products(p, part_val, part_idx, si, s); if (rc != MVLT_OK) return rc; }
+    hipLaunchKernelGGL(sample_pick_kernel<true>, dim3(p->M), dim3(256), 0, s, part_val, part_idx, parts_of(p), p->M, st, (int64_t*)nullptr, (float*)nullptr);
+    MVLT_LAUNCH_CHECK();
+    return MVLT_OK;
+}
+
+extern "C" int mvlt_gemm_skinny_accum(const MvltGemm* p, float* acc, int k_splits, void* stream) {
+    MVLT_CHECK(p && p->A && p->B && acc && k_splits >= 1 && k_splits <= 64, MVLT_ERR_ARG);
+    MVLT_CHECK(p->M > 0 && p->M <= 64 && p->N > 0 && p->K > 0 && !p->a_kmajor && !p->b_kmajor && p->epilogue == 0, MVLT_ERR_UNSUPPORTED);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int rc = by_dtype(p->dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        MVLT_CHECK(skinny_loads_ok<T>(p), MVLT_ERR_UNSUPPORTED);          // (split_k / a_colsum of the product are not looked at here)
+        hipLaunchKernelGGL((gemm_skinny_accum_kernel<T>), dim3(ceil_div(p->N, 16), k_splits), dim3(64 * SKINNY_WAVES), 0, s, skinny_dev(p), acc);
+        return (int)MVLT_OK;
+    });
+    if (rc != MVLT_OK) return rc;
+    MVLT_LAUNCH_CHECK();
+    return MVLT_OK;
+}

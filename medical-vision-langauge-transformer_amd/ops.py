@@ -313,20 +313,42 @@ def gemm(A, B, *, a_kmajor=False, b_kmajor=False, out=None, out_f32=False, bias=
     return out
 
 
-def gemm_argmax(A, W, bias=None):
-    """argmax_n (A @ W^T + bias) and its value, without materialising the logits (greedy decoding).
-    A: [M <= 64, K], W: [N, K] -> (int64 [M], f32 [M])."""
+def _head_gemm(A, W, bias, lda=None):
+    """The MvltGemm of an MLM-head product (A: [M <= 64, K], W: [N, K], f32 bias or None; no output matrix) -> (p, M, N).
+    ``lda``: row stride of A when its rows are read in place out of a wider buffer."""
     _need_cuda(A, W)
     M, K = A.shape
     N = W.shape[0]
     p = L.MvltGemm()
     p.dtype, p.M, p.N, p.K = _dt(A), M, N, K
-    p.A, p.lda, p.B, p.ldb = _p(A), _ld(A), _p(W), _ld(W)
+    p.A, p.lda, p.B, p.ldb = _p(A), _ld(A) if lda is None else lda, _p(W), _ld(W)
     if bias is not None:
         assert bias.dtype == torch.float32 and bias.numel() == N
         p.epilogue, p.bias = L.EPI_BIAS, _p(bias)
+    return p, M, N
+
+
+# scratch of the head products, one part per row and 16 columns: planes x [M, nblk] f32 values + [M, nblk] int32 indices
+_head_parts_cache = {}
+
+
+def _head_parts(planes, M, N, device, tag=None):
     nblk = (N + 15) // 16
-    pv = torch.empty((M, nblk), dtype=torch.float32, device=A.device)
+    key = (planes, M, nblk, device.index, tag)
+    buf = _head_parts_cache.get(key)
+    if buf is None:
+        shape = (M, nblk) if planes == 1 else (planes, M, nblk)
+        buf = _head_parts_cache[key] = (torch.empty(shape, dtype=torch.float32, device=device),
+                                        torch.empty((M, nblk), dtype=torch.int32, device=device))
+    return buf
+
+
+def gemm_argmax(A, W, bias=None):
+    """argmax_n (A @ W^T + bias) and its value, without materialising the logits (greedy decoding).
+    A: [M <= 64, K], W: [N, K] -> (int64 [M], f32 [M])."""
+    p, M, N = _head_gemm(A, W, bias)
+    nblk = (N + 15) // 16
+    pv = torch.empty((M, nblk), dtype=torch.float32, device=A.device)          # a stand-alone call: its scratch lives as long as the call
     pi = torch.empty((M, nblk), dtype=torch.int32, device=A.device)
     idx = torch.empty(M, dtype=torch.int64, device=A.device)
     val = torch.empty(M, dtype=torch.float32, device=A.device)
@@ -337,53 +359,22 @@ def gemm_argmax(A, W, bias=None):
 def gemm_argmax_greedy(A, W, bias, state):
     """Decoder GEMM + greedy pick + the per-token bookkeeping of greedy_search in two launches (mvlt_gemm_argmax_greedy).
     A: [M <= 64, K] (rows may be strided), W: [N, K]; ``state``: a prepared ``L.MvltGreedyState`` (decode._GreedyGraph)."""
-    M, K = A.shape
-    N = W.shape[0]
-    p = L.MvltGemm()
-    p.dtype, p.M, p.N, p.K = _dt(A), M, N, K
-    p.A, p.lda, p.B, p.ldb = _p(A), A.stride(0), _p(W), _ld(W)
-    if bias is not None:
-        p.epilogue, p.bias = L.EPI_BIAS, _p(bias)
-    nblk = (N + 15) // 16
-    key = ("argmax_parts", M, nblk, A.device.index)
-    buf = _argmax_parts.get(key)
-    if buf is None:
-        buf = _argmax_parts[key] = (torch.empty((M, nblk), dtype=torch.float32, device=A.device),
-                                    torch.empty((M, nblk), dtype=torch.int32, device=A.device))
-    L.check(L.lib().mvlt_gemm_argmax_greedy(C.byref(p), _p(buf[0]), _p(buf[1]), C.byref(state), _stream()), "mvlt_gemm_argmax_greedy")
-
-
-_argmax_parts = {}
+    # A.stride(0), not _ld(A): the head reads the [MASK] rows in place, at row stride 2 H of the step's hidden states
+    p, M, N = _head_gemm(A, W, bias, lda=A.stride(0))
+    pv, pi = _head_parts(1, M, N, A.device)
+    L.check(L.lib().mvlt_gemm_argmax_greedy(C.byref(p), _p(pv), _p(pi), C.byref(state), _stream()), "mvlt_gemm_argmax_greedy")
 
 
 def _sample_parts(M, N, device):
-    nblk = (N + 15) // 16
-    key = ("sample_parts", M, nblk, device.index, _stream_cache[1])      # a captured graph keeps its own (addresses are recorded)
-    buf = _argmax_parts.get(key)
-    if buf is None:
-        buf = _argmax_parts[key] = (torch.empty((4, M, nblk), dtype=torch.float32, device=device),
-                                    torch.empty((M, nblk), dtype=torch.int32, device=device))
-    return buf
-
-
-def _sample_gemm(A, W, bias):
-    _need_cuda(A, W)
-    M, K = A.shape
-    N = W.shape[0]
-    p = L.MvltGemm()
-    p.dtype, p.M, p.N, p.K = _dt(A), M, N, K
-    p.A, p.lda, p.B, p.ldb = _p(A), _ld(A), _p(W), _ld(W)
-    if bias is not None:
-        assert bias.dtype == torch.float32 and bias.numel() == N
-        p.epilogue, p.bias = L.EPI_BIAS, _p(bias)
-    return p, M, N
+    # keyed by the stream tag: a captured graph keeps a scratch of its own (it records addresses)
+    return _head_parts(4, M, N, device, tag=_stream_cache[1])
 
 
 def gemm_sample(A, W, bias, seed, tag, temperature=1.0):
     """One draw per row from softmax((A @ W^T + bias) / temperature) by Gumbel-max and its log-probability, without
     materialising the logits (mvlt_gemm_sample; the noise is a pure function of (seed, tag, row, column)).
     A: [M <= 64, K] (rows may be strided), W: [N, K] -> (int64 [M], f32 [M])."""
-    p, M, N = _sample_gemm(A, W, bias)
+    p, M, N = _head_gemm(A, W, bias)
     pv, pi = _sample_parts(M, N, A.device)
     idx = torch.empty(M, dtype=torch.int64, device=A.device)
     lp = torch.empty(M, dtype=torch.float32, device=A.device)
@@ -395,7 +386,7 @@ def gemm_sample(A, W, bias, seed, tag, temperature=1.0):
 def gemm_sample_step(A, W, bias, state):
     """Decoder GEMM + sampled pick + the per-token bookkeeping of greedy_search in two launches (mvlt_gemm_sample_step).
     ``state``: a prepared ``L.MvltSampleState`` (decode._GreedyGraph, mode 'sample')."""
-    p, M, N = _sample_gemm(A, W, bias)
+    p, M, N = _head_gemm(A, W, bias)
     pv, pi = _sample_parts(M, N, A.device)
     L.check(L.lib().mvlt_gemm_sample_step(C.byref(p), _p(pv), _p(pi), C.byref(state), _stream()), "mvlt_gemm_sample_step")
 
