@@ -36,7 +36,7 @@ enum { MVLT_OK = 0, MVLT_ERR_ARG = -1, MVLT_ERR_LAUNCH = -2, MVLT_ERR_UNSUPPORTE
  * signature; a binding compiles / hard-codes the value it was written against and compares it with what the
  * loaded library returns.  mvlt_sizeof(MVLT_STRUCT_*) lets a binding that mirrors the structs by hand (ctypes,
  * cgo, JNI) prove that its mirror has the size the library was compiled with (0 for an unknown id). */
-#define MVLT_ABI_VERSION 10
+#define MVLT_ABI_VERSION 11
 int mvlt_version(void);            /* MVLT_ABI_VERSION of the loaded library */
 const char* mvlt_arch(void);       /* "gfx950" */
 enum { MVLT_STRUCT_GEMM = 0, MVLT_STRUCT_LAYERNORM = 1, MVLT_STRUCT_LAYERNORM_BWD = 2, MVLT_STRUCT_LN_REDUCE_ITEM = 3,
@@ -103,6 +103,37 @@ int mvlt_gemm(const MvltGemm* p, void* stream);
 size_t mvlt_gemm_workspace_bytes(const MvltGemm* p);
 /* introspection: tile (= kernel instantiation gemm_kernel<dtype,bm,bn,a_kmajor,b_kmajor>) and split-K chosen for p */
 int mvlt_gemm_plan(const MvltGemm* p, int* bm, int* bn, int* split_k);
+/* The kernel family mvlt_gemm / mvlt_gemm_group would launch for these arguments (and the environment switches the dispatch
+ * reads per call), without launching anything: the dispatch itself runs in a no-launch mode, so the answer cannot drift from
+ * what a call does.  Returns MVLT_GEMM_ROUTE_KIND (an MvltGemmRoute) in the low bits and the number of k-slices
+ * (MVLT_GEMM_ROUTE_SLICES, >= 1) above them, or the negative MVLT_ERR_* the call itself would answer.  For tests that must
+ * know which kernel they check (the plan says tile and split, not LDS-DMA / register-staged / row streaming / 8-wave). */
+enum MvltGemmRoute {
+    MVLT_GEMM_ROUTE_SKINNY = 1,               /* skinny.hip, M <= 64 */
+    MVLT_GEMM_ROUTE_ROWSTREAM_0 = 2,          /* rowstream.hip, + the shape's bit of MVLT_ROWSTREAM (0 .. 8) */
+    MVLT_GEMM_ROUTE_ROWSTREAM_8 = 10,
+    MVLT_GEMM_ROUTE_G8_22_NARROW = 11,        /* gemm8.hip forward / dgrad: 256 x 256 or 128 x 256 tiles, 8- or 16-byte epilogue */
+    MVLT_GEMM_ROUTE_G8_22_WIDE = 12,
+    MVLT_GEMM_ROUTE_G8_12_NARROW = 13,
+    MVLT_GEMM_ROUTE_G8_12_WIDE = 14,
+    MVLT_GEMM_ROUTE_GLDS = 15,                /* gemm_glds_kernel at the planned tile (split-K: + splitk_reduce_kernel) */
+    MVLT_GEMM_ROUTE_REG = 16,                 /* gemm_kernel (register-staged) at the planned tile */
+    MVLT_GEMM_ROUTE_GROUP_GLDS_128x128 = 17,  /* gemm_group_glds_kernel<128, 128, 2> */
+    MVLT_GEMM_ROUTE_GROUP_GLDS_64x128_S3 = 18,
+    MVLT_GEMM_ROUTE_GROUP_GLDS_64x128_S2 = 19,
+    MVLT_GEMM_ROUTE_GROUP_REG_128x128 = 20,   /* gemm_group_kernel, no k-slices (bf16 or f32) */
+    MVLT_GEMM_ROUTE_GROUP_REG_64x128 = 21,
+    MVLT_GEMM_ROUTE_GROUP_REG_64x96 = 22,
+    MVLT_GEMM_ROUTE_GROUP_ATOMIC = 23,        /* gemm_group_kernel, k-slices that meet through atomicAdd in the zeroed output */
+    MVLT_GEMM_ROUTE_GROUP_G8_22 = 24,         /* gemm8.hip group form: 256 x 256 / 128 x 256 / 128 x 128 tiles, slices through slabs */
+    MVLT_GEMM_ROUTE_GROUP_G8_12 = 25,
+    MVLT_GEMM_ROUTE_GROUP_G8_11 = 26
+};
+#define MVLT_GEMM_ROUTE_KIND_BITS 8
+#define MVLT_GEMM_ROUTE_KIND(r) ((r) & ((1 << MVLT_GEMM_ROUTE_KIND_BITS) - 1))
+#define MVLT_GEMM_ROUTE_SLICES(r) ((r) >> MVLT_GEMM_ROUTE_KIND_BITS)
+int mvlt_gemm_route(const MvltGemm* p);
+int mvlt_gemm_group_route(const MvltGemm* items, int n);
 /* n (<= 8) independent products in ONE launch -- the weight gradients of one layer (dW_i = dY_i^T X_i, the
  * backward of the nn.Linear calls of one SwinTransformerBlock / BertLayer).  All items must have both operands
  * k-major, the same dtype and output widths that are all multiples of 128 or all multiples of 96; the tile

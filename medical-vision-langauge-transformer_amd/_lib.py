@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(_HERE, "libmvlt_hip.so")
 
 F32, BF16 = 0, 1
 OK = 0
-ABI_VERSION = 10         # == MVLT_ABI_VERSION of the include/mvlt_hip.h these mirrors were written against
+ABI_VERSION = 11         # == MVLT_ABI_VERSION of the include/mvlt_hip.h these mirrors were written against
 ERRORS = {-1: "MVLT_ERR_ARG", -2: "MVLT_ERR_LAUNCH", -3: "MVLT_ERR_UNSUPPORTED"}
 
 EPI_BIAS, EPI_GELU, EPI_SAVE_PRE, EPI_DROPOUT = 1, 2, 4, 8
@@ -22,6 +22,19 @@ ATTN_SWIN, ATTN_BIDIR, ATTN_SEQ2SEQ = 0, 1, 2
 ATTN_ROUTES = ("UNSUPPORTED", "SWIN_FWD", "BERT_FWD_KT5", "BERT_FWD_KT9", "BERT_FWD_KT13", "SWIN_BWD_KS0", "SWIN_BWD_KS3",
                "SWIN_BWD_KS6", "SWIN_BWD_KS12", "SWIN_BWD", "BERT_BWD2_NW5", "BERT_BWD2_NW6", "BERT_BWD_SPLIT_KT5",
                "BERT_BWD_SPLIT_KT9", "BERT_BWD_SPLIT_KT13", "BERT_BWD_KT5", "BERT_BWD_KT9")
+# enum MvltGemmRoute (mvlt_gemm_route / mvlt_gemm_group_route): the low 8 bits of the answer, the k-slice count above them
+GEMM_ROUTES = ("", "SKINNY") + tuple(f"ROWSTREAM_{i}" for i in range(9)) + (
+    "G8_22_NARROW", "G8_22_WIDE", "G8_12_NARROW", "G8_12_WIDE", "GLDS", "REG", "GROUP_GLDS_128x128", "GROUP_GLDS_64x128_S3",
+    "GROUP_GLDS_64x128_S2", "GROUP_REG_128x128", "GROUP_REG_64x128", "GROUP_REG_64x96", "GROUP_ATOMIC", "GROUP_G8_22",
+    "GROUP_G8_12", "GROUP_G8_11")
+
+
+def gemm_route_name(r):
+    """(name, k-slices) of a non-negative mvlt_gemm_route / mvlt_gemm_group_route answer; a negative one raises."""
+    if r < 0:
+        raise RuntimeError(f"mvlt_gemm_route: {ERRORS.get(r, r)}")
+    return GEMM_ROUTES[r & 255], r >> 8
+
 
 vp, i32, i64, u64, u32, f32, sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_uint32, C.c_float, C.c_size_t
 
@@ -136,6 +149,8 @@ SYMBOLS = {
     "mvlt_gemm": (i32, [C.POINTER(MvltGemm), vp]),
     "mvlt_gemm_workspace_bytes": (sz, [C.POINTER(MvltGemm)]),
     "mvlt_gemm_plan": (i32, [C.POINTER(MvltGemm), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+    "mvlt_gemm_route": (i32, [C.POINTER(MvltGemm)]),
+    "mvlt_gemm_group_route": (i32, [C.POINTER(MvltGemm), i32]),
     "mvlt_gemm_group": (i32, [C.POINTER(MvltGemm), i32, vp]),
     "mvlt_gemm_group_workspace_bytes": (sz, [C.POINTER(MvltGemm), i32]),
     "mvlt_gemm_argmax": (i32, [C.POINTER(MvltGemm), vp, vp, vp, vp, vp]),

@@ -18,10 +18,10 @@
 
 // gemm8.hip: 8-wave ping-pong kernel; takes the filled kernel argument block, returns 1 if it launched
 extern "C" __attribute__((visibility("hidden"))) int mvlt_gemm8_try(const void* dev_blocks, int n, int a_kmajor, int b_kmajor, int big_only,
-                                                                    float* const* colsum, void* ws, size_t ws_bytes, void* stream);
+                                                                    float* const* colsum, void* ws, size_t ws_bytes, void* stream, int* route);
 extern "C" __attribute__((visibility("hidden"))) size_t mvlt_gemm8_group_workspace(const void* dev_blocks, int n);
 // row-streaming kernel for the HBM-bound Swin stage-0 / 1 products (rowstream.hip): 1 = taken, 0 = not eligible, -1 = error
-extern "C" __attribute__((visibility("hidden"))) int mvlt_rowstream_try(const void* dev_block, int b_kmajor, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int mvlt_rowstream_try(const void* dev_block, int b_kmajor, void* stream, int* route);
 // MVLT_G8: unset / 2 = automatic (single products that fill the chip with 256 x 256 tiles: MLM decoder, large batches),
 // 0 = never, 1 = wherever it is eligible, weight-gradient groups included (experiments: slower than the 4-wave kernels on
 // the B=32 step's mid-size products)
@@ -926,17 +926,19 @@ static int fill_dev(const MvltGemm* p, const Plan& pl, GemmDev& d) {
     return MVLT_OK;
 }
 
+// route (gemm_host.h): null = launch; non-null = the same decisions, *route = the kernel family that would run, nothing launched
 template <typename T>
-static int gemm_dispatch(const MvltGemm* p, hipStream_t s) {
+static int gemm_dispatch(const MvltGemm* p, hipStream_t s, int* route = nullptr) {
     Plan pl = choose_plan(p);
     const bool skinny = is_skinny<T>(p);
     if (skinny) pl.split = 1;          // (no workspace was requested for it)
     GemmDev d;
     { const int rc = fill_dev<T>(p, pl, d); if (rc != MVLT_OK) return rc; }
     if (skinny) {          // M <= 64: skinny.hip, unless the operands cannot be loaded 16 bytes at a time
-        const int rcs = mvlt_skinny_try(p, &d, s);
+        const int rcs = mvlt_skinny_try(p, &d, s, route);
         if (rcs < 0) return MVLT_ERR_LAUNCH;
         if (rcs > 0) {
+            if (route) return MVLT_OK;
             if (p->event_after_main) (void)hipEventRecord(reinterpret_cast<hipEvent_t>(p->event_after_main), s);
             return MVLT_OK;
         }
@@ -946,9 +948,10 @@ static int gemm_dispatch(const MvltGemm* p, hipStream_t s) {
     if constexpr (sizeof(T) == 2) {
         // weight-stationary row streaming for the HBM-bound Swin stage-0 / 1 products (100 k / 25 k rows, K, N <= 384)
         if (!ak && d.split_k <= 1 && p->M >= 16384 && p->N <= 768 && p->K <= 384) {
-            const int rcs = mvlt_rowstream_try(&d, bk ? 1 : 0, s);
+            const int rcs = mvlt_rowstream_try(&d, bk ? 1 : 0, s, route);
             if (rcs < 0) return MVLT_ERR_LAUNCH;
             if (rcs > 0) {
+                if (route) return MVLT_OK;
                 if (p->event_after_main) (void)hipEventRecord(reinterpret_cast<hipEvent_t>(p->event_after_main), s);
                 return MVLT_OK;
             }
@@ -956,9 +959,10 @@ static int gemm_dispatch(const MvltGemm* p, hipStream_t s) {
         // 8-wave ping-pong engine (gemm8.hip) for wide outputs: MVLT_G8 = 0 never / 1 wherever it is eligible
         const int g8m = g8_mode();
         if (g8m && !ak && d.split_k <= 1) {
-            const int rc8 = mvlt_gemm8_try(&d, 1, 0, bk ? 1 : 0, g8m == 2, nullptr, nullptr, 0, s);
+            const int rc8 = mvlt_gemm8_try(&d, 1, 0, bk ? 1 : 0, g8m == 2, nullptr, nullptr, 0, s, route);
             if (rc8 < 0) return MVLT_ERR_LAUNCH;
             if (rc8 > 0) {
+                if (route) return MVLT_OK;
                 if (p->event_after_main) (void)hipEventRecord(reinterpret_cast<hipEvent_t>(p->event_after_main), s);
                 return MVLT_OK;
             }
@@ -972,10 +976,11 @@ static int gemm_dispatch(const MvltGemm* p, hipStream_t s) {
         const bool bkm_ok = !bk || ((pl.bn == 64 || pl.bn == 128) && p->N % 8 == 0 && p->N >= 8);
         if (glds_on && !ak && bkm_ok && p->K % 64 == 0 && kspan % 64 == 0 && d.a_vec && d.b_vec) {
             bool done = true;
-#define GLDS_GO(BM_, BN_, BKM_) do { if (d.wide) hipLaunchKernelGGL((gemm_glds_kernel<BM_, BN_, BKM_, true>), grid, dim3(256), 0, s, d); \
+            // (route probe: every branch below launches through one of these two macros, which report instead)
+#define GLDS_GO(BM_, BN_, BKM_) do { if (route) break; if (d.wide) hipLaunchKernelGGL((gemm_glds_kernel<BM_, BN_, BKM_, true>), grid, dim3(256), 0, s, d); \
                                      else hipLaunchKernelGGL((gemm_glds_kernel<BM_, BN_, BKM_, false>), grid, dim3(256), 0, s, d); } while (0)
             // 160-row tiles (72 KB of dynamic LDS, two workgroups per CU): wide epilogue only
-#define GLDS_GO_DYN(BM_, BN_, BKM_) do { constexpr int sh_ = 2 * (BM_ + BN_) * 64 * 2; \
+#define GLDS_GO_DYN(BM_, BN_, BKM_) do { if (route) break; constexpr int sh_ = 2 * (BM_ + BN_) * 64 * 2; \
                 static const bool ok_ = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_glds_kernel<BM_, BN_, BKM_, true>), \
                                                            hipFuncAttributeMaxDynamicSharedMemorySize, sh_) == hipSuccess; \
                 if (!ok_) return MVLT_ERR_LAUNCH; \
@@ -990,7 +995,8 @@ static int gemm_dispatch(const MvltGemm* p, hipStream_t s) {
                 if (bk) GLDS_GO_DYN(160, 128, true); else GLDS_GO_DYN(160, 128, false);
             }
             else if (st3 && pl.bm == 64 && pl.bn == 64 && d.wide && kspan >= 768 && (st3 == 2 || (!bk && tiles64 <= 400))) {
-                if (bk) hipLaunchKernelGGL((gemm_glds_kernel<64, 64, true, true, 3>), grid, dim3(256), 0, s, d);
+                if (route) {}
+                else if (bk) hipLaunchKernelGGL((gemm_glds_kernel<64, 64, true, true, 3>), grid, dim3(256), 0, s, d);
                 else hipLaunchKernelGGL((gemm_glds_kernel<64, 64, false, true, 3>), grid, dim3(256), 0, s, d);
             }
             else if (bk) {
@@ -1007,6 +1013,7 @@ static int gemm_dispatch(const MvltGemm* p, hipStream_t s) {
             else done = false;
 #undef GLDS_GO
 #undef GLDS_GO_DYN
+            if (done && route) { *route = gemm_route_code(MVLT_GEMM_ROUTE_GLDS, d.split_k); return MVLT_OK; }
             if (done) {
                 MVLT_LAUNCH_CHECK();
                 if (p->event_after_main) (void)hipEventRecord(reinterpret_cast<hipEvent_t>(p->event_after_main), s);
@@ -1022,6 +1029,7 @@ static int gemm_dispatch(const MvltGemm* p, hipStream_t s) {
         }
     }
     if (pl.bm == 160) return MVLT_ERR_UNSUPPORTED;          // (tile160_ok and the conditions above disagree: never launch a mis-sized grid)
+    if (route) { *route = gemm_route_code(MVLT_GEMM_ROUTE_REG, d.split_k); return MVLT_OK; }
     if (pl.bm == 128 && pl.bn == 128) launch_layout<T, 128, 128>(d, ak, bk, grid, s);
     else if (pl.bm == 128 && pl.bn == 96) launch_layout<T, 128, 96>(d, ak, bk, grid, s);
     else if (pl.bm == 64 && pl.bn == 128) launch_layout<T, 64, 128>(d, ak, bk, grid, s);
@@ -1058,7 +1066,7 @@ static int check_gemm_args(const MvltGemm* p) {
 
 // Grouped launch: weight gradients only (both operands k-major), 64-row tiles, no split-K.
 template <typename T>
-static int gemm_group_dispatch(const MvltGemm* items, int n, hipStream_t s) {
+static int gemm_group_dispatch(const MvltGemm* items, int n, hipStream_t s, int* route = nullptr) {
     GemmGroupDev g{};
     g.n = n;
     bool all128 = true, all96 = true;
@@ -1117,7 +1125,7 @@ static int gemm_group_dispatch(const MvltGemm* items, int n, hipStream_t s) {
                 ok = ok && tmp[i].epi == MVLT_EPI_OUT_F32;
             }
             if (ok) {
-                const int rc8 = mvlt_gemm8_try(tmp, n, 1, 1, 0, outs, items[0].workspace, items[0].workspace_bytes, s);
+                const int rc8 = mvlt_gemm8_try(tmp, n, 1, 1, 0, outs, items[0].workspace, items[0].workspace_bytes, s, route);
                 if (rc8 < 0) return MVLT_ERR_LAUNCH;
                 if (rc8 > 0) return MVLT_OK;
             }
@@ -1135,10 +1143,11 @@ static int gemm_group_dispatch(const MvltGemm* items, int n, hipStream_t s) {
         }
     }
     if (split > 1) {
+        for (int i = 0; i < n; ++i) MVLT_CHECK(items[i].ldc == items[i].N, MVLT_ERR_UNSUPPORTED);          // contiguous outputs (gradient arena views)
+        if (route) { *route = gemm_route_code(MVLT_GEMM_ROUTE_GROUP_ATOMIC, split); return MVLT_OK; }
         MvltZeroItem z[2 * GROUP_MAX];
         int nz = 0;
         for (int i = 0; i < n; ++i) {
-            MVLT_CHECK(items[i].ldc == items[i].N, MVLT_ERR_UNSUPPORTED);          // contiguous outputs (gradient arena views)
             z[nz++] = MvltZeroItem{reinterpret_cast<float*>(items[i].C), (int64_t)items[i].M * items[i].N};
             if (items[i].a_colsum) z[nz++] = MvltZeroItem{items[i].a_colsum, (int64_t)items[i].M};
         }
@@ -1152,6 +1161,8 @@ static int gemm_group_dispatch(const MvltGemm* items, int n, hipStream_t s) {
     static const int per_cu = [] { const char* e = getenv("MVLT_WGRAD_PER_CU"); const int v = e ? atoi(e) : 2; return v >= 1 && v <= 3 ? v : 2; }();
     if (total > per_cu * 256) total = per_cu * 256;
     // bf16: two LDS stages + two register sets, one barrier per k-tile (the single-stage form measured 1.3 % slower in the step)
+    const int reg_route = gemm_route_code(bn == 96 ? MVLT_GEMM_ROUTE_GROUP_REG_64x96
+                                                   : (bm == 128 ? MVLT_GEMM_ROUTE_GROUP_REG_128x128 : MVLT_GEMM_ROUTE_GROUP_REG_64x128), 1);
 #define GROUP_LAUNCH(BM_, BN_, D_) hipLaunchKernelGGL((gemm_group_kernel<T, BM_, BN_, true, true, D_>), dim3(total), dim3(256), 0, s, g)
     if constexpr (sizeof(T) == 2) {
         // LDS-DMA form (round 6; MVLT_WGRAD_GLDS=0: the register-staged kernel): bf16, no k-slices, 128-wide column tiles, every
@@ -1171,6 +1182,11 @@ static int gemm_group_dispatch(const MvltGemm* items, int n, hipStream_t s) {
             ok = d.a_vec && d.b_vec && d.epi_vec && (d.M % 8 == 0) && (d.N % 8 == 0) && d.M >= 8 && d.N >= 8 &&
                  (d.epi & ~(MVLT_EPI_OUT_F32 | MVLT_EPI_ACCUM)) == 0 && (d.epi & MVLT_EPI_OUT_F32) && !d.atomic_out && d.split_k <= 1;
         }
+        if (ok && route) {
+            *route = gemm_route_code(bm == 128 ? MVLT_GEMM_ROUTE_GROUP_GLDS_128x128
+                                               : (glds_mode == 3 ? MVLT_GEMM_ROUTE_GROUP_GLDS_64x128_S3 : MVLT_GEMM_ROUTE_GROUP_GLDS_64x128_S2), 1);
+            return MVLT_OK;
+        }
         if (ok) {
             if (bm == 128) hipLaunchKernelGGL((gemm_group_glds_kernel<128, 128, 2>), dim3(total), dim3(256), 0, s, g);
             else if (glds_mode == 3) {          // 64 x 128 with three stages (72 KB of dynamic LDS: two k-tiles in flight for a lone workgroup)
@@ -1184,8 +1200,10 @@ static int gemm_group_dispatch(const MvltGemm* items, int n, hipStream_t s) {
             MVLT_LAUNCH_CHECK();
             return MVLT_OK;
         }
+        if (route) { *route = reg_route; return MVLT_OK; }
         if (bn == 128 && bm == 128) GROUP_LAUNCH(128, 128, 2); else if (bn == 128) GROUP_LAUNCH(64, 128, 2); else GROUP_LAUNCH(64, 96, 2);
     } else {
+        if (route) { *route = reg_route; return MVLT_OK; }
         if (bn == 128 && bm == 128) GROUP_LAUNCH(128, 128, 0); else if (bn == 128) GROUP_LAUNCH(64, 128, 0); else GROUP_LAUNCH(64, 96, 0);
     }
 #undef GROUP_LAUNCH
@@ -1215,6 +1233,24 @@ extern "C" int mvlt_gemm_group(const MvltGemm* items, int n, void* stream) {
     if (items[0].dtype == MVLT_F32) return gemm_group_dispatch<float>(items, n, s);
     if (items[0].dtype == MVLT_BF16) return gemm_group_dispatch<bf16_t>(items, n, s);
     return MVLT_ERR_UNSUPPORTED;
+}
+
+// The routes, from the dispatch functions themselves in their no-launch mode
+extern "C" int mvlt_gemm_route(const MvltGemm* p) {
+    { const int rc = check_gemm_args(p); if (rc != MVLT_OK) return rc; }
+    int route = 0;
+    const int rc = p->dtype == MVLT_F32 ? gemm_dispatch<float>(p, nullptr, &route)
+                                        : (p->dtype == MVLT_BF16 ? gemm_dispatch<bf16_t>(p, nullptr, &route) : MVLT_ERR_UNSUPPORTED);
+    return rc != MVLT_OK ? rc : route;
+}
+
+extern "C" int mvlt_gemm_group_route(const MvltGemm* items, int n) {
+    MVLT_CHECK(items && n >= 1 && n <= GROUP_MAX, MVLT_ERR_ARG);
+    for (int i = 0; i < n; ++i) { const int rc = check_gemm_args(items + i); if (rc != MVLT_OK) return rc; }
+    int route = 0;
+    const int rc = items[0].dtype == MVLT_F32 ? gemm_group_dispatch<float>(items, n, nullptr, &route)
+                                              : (items[0].dtype == MVLT_BF16 ? gemm_group_dispatch<bf16_t>(items, n, nullptr, &route) : MVLT_ERR_UNSUPPORTED);
+    return rc != MVLT_OK ? rc : route;
 }
 
 extern "C" int mvlt_gemm(const MvltGemm* p, void* stream) {

@@ -28,6 +28,7 @@
 // more (a few dozen KB of L2 hits per workgroup buy a loop body without a tail version).
 #include "common.h"
 #include "gemm_dev.h"
+#include "gemm_host.h"
 #include <cstdlib>
 
 namespace {
@@ -704,7 +705,14 @@ int g8_wgrad_cap() {
     return wcap;
 }
 template <int MH, int NH, bool AKM, bool BKM, int EPI, bool WIDE = false>
-int g8_launch1(const G8Group& gp, long units, hipStream_t s) {
+int g8_launch1(const G8Group& gp, long units, hipStream_t s, int* route) {
+    if (route) {          // (gemm_host.h: the route this instantiation is, nothing launched)
+        constexpr int kind = (AKM && BKM) ? (MH == 2 ? MVLT_GEMM_ROUTE_GROUP_G8_22 : (NH == 2 ? MVLT_GEMM_ROUTE_GROUP_G8_12 : MVLT_GEMM_ROUTE_GROUP_G8_11))
+                                          : (MH == 2 ? (WIDE ? MVLT_GEMM_ROUTE_G8_22_WIDE : MVLT_GEMM_ROUTE_G8_22_NARROW)
+                                                     : (WIDE ? MVLT_GEMM_ROUTE_G8_12_WIDE : MVLT_GEMM_ROUTE_G8_12_NARROW));
+        *route = gemm_route_code(kind, gp.split);
+        return 1;
+    }
     constexpr int sh = G8Cfg<MH, NH>::LDS + 64;                           // ring + the products' effective sizes + ticket
     static const bool attr = [] { return hipFuncSetAttribute(reinterpret_cast<const void*>(gemm8_kernel<MH, NH, AKM, BKM, EPI, WIDE>),
                                                              hipFuncAttributeMaxDynamicSharedMemorySize, sh) == hipSuccess; }();
@@ -716,14 +724,14 @@ int g8_launch1(const G8Group& gp, long units, hipStream_t s) {
 }
 // forward / dgrad products with bf16 rows out: the 16-byte epilogue when EVERY product of the list qualifies (GemmDev.wide)
 template <int MH, int NH, bool AKM, bool BKM, int EPI>
-int g8_launch(const G8Group& gp, long units, hipStream_t s) {
+int g8_launch(const G8Group& gp, long units, hipStream_t s, int* route) {
     if constexpr (!AKM && (EPI & MVLT_EPI_OUT_F32) == 0) {
         const char* we = getenv("MVLT_G8_WIDE"); const bool wide_on = !we || atoi(we) != 0;   // (A/B switch)
         bool wide = wide_on;
         for (int i = 0; i < gp.n; ++i) wide = wide && gp.g[i].wide;
-        if (wide) return g8_launch1<MH, NH, AKM, BKM, EPI, true>(gp, units, s);
+        if (wide) return g8_launch1<MH, NH, AKM, BKM, EPI, true>(gp, units, s, route);
     }
-    return g8_launch1<MH, NH, AKM, BKM, EPI, false>(gp, units, s);
+    return g8_launch1<MH, NH, AKM, BKM, EPI, false>(gp, units, s, route);
 }
 
 const void* g8_zero_ptr() {
@@ -732,25 +740,25 @@ const void* g8_zero_ptr() {
 }
 
 template <int MH, int NH>
-int g8_dispatch(const G8Group& gp, bool akm, bool bkm, int epi, long units, hipStream_t s) {
+int g8_dispatch(const G8Group& gp, bool akm, bool bkm, int epi, long units, hipStream_t s, int* route) {
     constexpr int B_ = MVLT_EPI_BIAS, G_ = MVLT_EPI_GELU, P_ = MVLT_EPI_SAVE_PRE, X_ = MVLT_EPI_MUL_GELU_GRAD,
                   R_ = MVLT_EPI_RESIDUAL, F_ = MVLT_EPI_OUT_F32;
-    if (akm && bkm && epi == F_) return g8_launch<MH, NH, true, true, F_>(gp, units, s);
+    if (akm && bkm && epi == F_) return g8_launch<MH, NH, true, true, F_>(gp, units, s, route);
     if constexpr (MH + NH > 2) {
         if (!akm && !bkm) {
             switch (epi) {
-                case 0: return g8_launch<MH, NH, false, false, 0>(gp, units, s);
-                case B_: return g8_launch<MH, NH, false, false, B_>(gp, units, s);
-                case B_ | G_: return g8_launch<MH, NH, false, false, B_ | G_>(gp, units, s);
-                case B_ | G_ | P_: return g8_launch<MH, NH, false, false, B_ | G_ | P_>(gp, units, s);
+                case 0: return g8_launch<MH, NH, false, false, 0>(gp, units, s, route);
+                case B_: return g8_launch<MH, NH, false, false, B_>(gp, units, s, route);
+                case B_ | G_: return g8_launch<MH, NH, false, false, B_ | G_>(gp, units, s, route);
+                case B_ | G_ | P_: return g8_launch<MH, NH, false, false, B_ | G_ | P_>(gp, units, s, route);
                 default: return 0;
             }
         }
         if (!akm && bkm) {
             switch (epi) {
-                case 0: return g8_launch<MH, NH, false, true, 0>(gp, units, s);
-                case X_: return g8_launch<MH, NH, false, true, X_>(gp, units, s);
-                case R_: return g8_launch<MH, NH, false, true, R_>(gp, units, s);
+                case 0: return g8_launch<MH, NH, false, true, 0>(gp, units, s, route);
+                case X_: return g8_launch<MH, NH, false, true, X_>(gp, units, s, route);
+                case R_: return g8_launch<MH, NH, false, true, R_>(gp, units, s, route);
                 default: return 0;
             }
         }
@@ -826,6 +834,7 @@ extern "C" int mvlt_gemm8_trace_buffer(void* buf) {
 // of 64 unless both operands are k-major (weight gradients: the reduction runs over activation rows, any count, also
 // read from m_dev).  Weight-gradient groups: `colsum[i]` (may be null) receives the bias gradient of product i;
 // `ws` / `ws_bytes`: workspace for the k-slices (mvlt_gemm8_group_workspace says how much; too little: no slices).
+// `route` (gemm_host.h): non-null = decide only, report the instantiation and the slice count, launch and clear nothing.
 extern "C" __attribute__((visibility("hidden"))) size_t mvlt_gemm8_group_workspace(const void* dev_blocks, int n) {
     if (n < 1 || n > G8_GROUP_MAX) return 0;
     return g8_plan_kk(reinterpret_cast<const GemmDev*>(dev_blocks), n).ws_bytes;
@@ -833,7 +842,7 @@ extern "C" __attribute__((visibility("hidden"))) size_t mvlt_gemm8_group_workspa
 
 extern "C" __attribute__((visibility("hidden"))) int mvlt_gemm8_try(const void* dev_blocks, int n, int a_kmajor, int b_kmajor,
                                                                     int big_only, float* const* colsum, void* ws, size_t ws_bytes,
-                                                                    void* stream) {
+                                                                    void* stream, int* route) {
     const GemmDev* d = reinterpret_cast<const GemmDev*>(dev_blocks);
     if (n < 1 || n > G8_GROUP_MAX) return 0;
     G8Group gp{};
@@ -862,16 +871,16 @@ extern "C" __attribute__((visibility("hidden"))) int mvlt_gemm8_try(const void* 
             gp.slabs = reinterpret_cast<float*>(w);
             gp.cs_slabs = reinterpret_cast<float*>(w + (size_t)pl.units * bm * bn * 4);
             gp.counters = reinterpret_cast<int*>(w + (size_t)pl.units * bm * bn * 4 + (size_t)pl.units * bm * 4);
-            if (hipMemsetAsync(gp.counters, 0, (size_t)pl.tiles * 4, s) != hipSuccess) return -1;          // tickets: re-initialised every call
+            if (!route && hipMemsetAsync(gp.counters, 0, (size_t)pl.tiles * 4, s) != hipSuccess) return -1;          // tickets: re-initialised every call
         }
-        if (pl.mode == 22) return g8_dispatch<2, 2>(gp, true, true, d[0].epi, pl.units, s);
-        if (pl.mode == 12) return g8_dispatch<1, 2>(gp, true, true, d[0].epi, pl.units, s);
-        if (pl.mode == 11) return g8_dispatch<1, 1>(gp, true, true, d[0].epi, pl.units, s);
+        if (pl.mode == 22) return g8_dispatch<2, 2>(gp, true, true, d[0].epi, pl.units, s, route);
+        if (pl.mode == 12) return g8_dispatch<1, 2>(gp, true, true, d[0].epi, pl.units, s, route);
+        if (pl.mode == 11) return g8_dispatch<1, 1>(gp, true, true, d[0].epi, pl.units, s, route);
         return 0;
     }
     long tiles = 0;
     const int mode = g8_choose(d, n, big_only != 0, &tiles);
-    if (mode == 22) return g8_dispatch<2, 2>(gp, a_kmajor != 0, b_kmajor != 0, d[0].epi, tiles, s);
-    if (mode == 12) return g8_dispatch<1, 2>(gp, a_kmajor != 0, b_kmajor != 0, d[0].epi, tiles, s);
+    if (mode == 22) return g8_dispatch<2, 2>(gp, a_kmajor != 0, b_kmajor != 0, d[0].epi, tiles, s, route);
+    if (mode == 12) return g8_dispatch<1, 2>(gp, a_kmajor != 0, b_kmajor != 0, d[0].epi, tiles, s, route);
     return 0;
 }

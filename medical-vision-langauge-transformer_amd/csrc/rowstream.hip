@@ -29,6 +29,7 @@
 // under the weight image join the ring (two extra barriers in the prologue).
 #include "common.h"
 #include "gemm_dev.h"
+#include "gemm_host.h"
 #include <cstdlib>
 
 namespace {
@@ -305,16 +306,18 @@ __global__ __launch_bounds__((2 * WN + 2) * 64) void rowstream_kernel(const RsAr
     }
 }
 
+// bit: the shape's bit in MVLT_ROWSTREAM (= MVLT_GEMM_ROUTE_ROWSTREAM_0 + bit); route: gemm_host.h
 template <int K, int N, int WN, bool BKM, bool X2>
-int rs_launch(const RsArgs& a, hipStream_t s) {
+int rs_launch(const RsArgs& a, hipStream_t s, int bit, int* route) {
     using Cfg = RsCfg<K, N, WN, BKM, X2>;
     auto k = rowstream_kernel<K, N, WN, BKM, X2>;
-    static const bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS) == hipSuccess;
-    if (!attr) return -1;
     static const int ncu = [] { int dev = 0, n = 256; if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev); return n; }();
     const int unit = 8 * a.n_chunks;
     const int grid = ncu / unit * unit;
     if (grid < unit) return 0;
+    if (route) { *route = gemm_route_code(MVLT_GEMM_ROUTE_ROWSTREAM_0 + bit, 1); return 1; }
+    static const bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS) == hipSuccess;
+    if (!attr) return -1;
     hipLaunchKernelGGL(k, dim3(grid), dim3(Cfg::NT), Cfg::LDS, s, a);
     return hipGetLastError() == hipSuccess ? 1 : -1;
 }
@@ -325,7 +328,7 @@ int rs_launch(const RsArgs& a, hipStream_t s) {
 // Eligible: bf16, A [M, K] contiguous rows (lda == K), one of the Swin stage-0 / 1 shapes below, enough rows (fewer leave the
 // 256 persistent workgroups without work: the tile kernels win), 16-byte aligned operands, an epilogue made of
 // bias / GELU (+ saved pre-activation) / DropPath row scale / gelu' operand / residual only.
-extern "C" __attribute__((visibility("hidden"))) int mvlt_rowstream_try(const void* dev_block, int b_kmajor, void* stream) {
+extern "C" __attribute__((visibility("hidden"))) int mvlt_rowstream_try(const void* dev_block, int b_kmajor, void* stream, int* route) {
     const GemmDev& d = *reinterpret_cast<const GemmDev*>(dev_block);
     constexpr int ALLOWED = MVLT_EPI_BIAS | MVLT_EPI_GELU | MVLT_EPI_SAVE_PRE | MVLT_EPI_ROWSCALE | MVLT_EPI_MUL_GELU_GRAD | MVLT_EPI_RESIDUAL;
     if ((d.epi & ~ALLOWED) || d.m_dev || d.split_k > 1 || d.a_colsum || d.a_kmajor) return 0;
@@ -349,16 +352,16 @@ extern "C" __attribute__((visibility("hidden"))) int mvlt_rowstream_try(const vo
     if (!env && d.M < 49152) return 0;
     auto on = [&](int bit) { return (mask >> bit) & 1u; };
     if (!b_kmajor) {
-        if (K == 96 && N == 384 && !x2 && on(0)) return rs_launch<96, 384, 4, false, false>(a, s);
-        if (K == 384 && N == 96 && x2 && on(1)) return rs_launch<384, 96, 3, false, true>(a, s);
-        if (K == 192 && N == 768 && !x2 && on(2)) { a.n_chunks = 4; return rs_launch<192, 192, 3, false, false>(a, s); }
+        if (K == 96 && N == 384 && !x2 && on(0)) return rs_launch<96, 384, 4, false, false>(a, s, 0, route);
+        if (K == 384 && N == 96 && x2 && on(1)) return rs_launch<384, 96, 3, false, true>(a, s, 1, route);
+        if (K == 192 && N == 768 && !x2 && on(2)) { a.n_chunks = 4; return rs_launch<192, 192, 3, false, false>(a, s, 2, route); }
     } else {
-        if (K == 96 && N == 384 && x2 && on(3)) return rs_launch<96, 384, 4, true, true>(a, s);
-        if (K == 384 && N == 96 && !x2 && on(4)) return rs_launch<384, 96, 3, true, false>(a, s);
-        if (K == 96 && N == 96 && !x2 && on(5)) return rs_launch<96, 96, 3, true, false>(a, s);
-        if (K == 288 && N == 96 && !x2 && on(6)) return rs_launch<288, 96, 3, true, false>(a, s);
-        if (K == 192 && N == 768 && x2 && on(7)) { a.n_chunks = 4; return rs_launch<192, 192, 3, true, true>(a, s); }
-        if (K == 192 && N == 192 && !x2 && on(8)) return rs_launch<192, 192, 3, true, false>(a, s);
+        if (K == 96 && N == 384 && x2 && on(3)) return rs_launch<96, 384, 4, true, true>(a, s, 3, route);
+        if (K == 384 && N == 96 && !x2 && on(4)) return rs_launch<384, 96, 3, true, false>(a, s, 4, route);
+        if (K == 96 && N == 96 && !x2 && on(5)) return rs_launch<96, 96, 3, true, false>(a, s, 5, route);
+        if (K == 288 && N == 96 && !x2 && on(6)) return rs_launch<288, 96, 3, true, false>(a, s, 6, route);
+        if (K == 192 && N == 768 && x2 && on(7)) { a.n_chunks = 4; return rs_launch<192, 192, 3, true, true>(a, s, 7, route); }
+        if (K == 192 && N == 192 && !x2 && on(8)) return rs_launch<192, 192, 3, true, false>(a, s, 8, route);
     }
     return 0;
 }

@@ -554,12 +554,13 @@ template <typename S> int greedy_state(const S* g, GreedyState& st) {
 
 }  // namespace
 
-extern "C" __attribute__((visibility("hidden"))) int mvlt_skinny_try(const MvltGemm* p, const void* dev_block, void* stream) {
+extern "C" __attribute__((visibility("hidden"))) int mvlt_skinny_try(const MvltGemm* p, const void* dev_block, void* stream, int* route) {
     const GemmDev& d = *reinterpret_cast<const GemmDev*>(dev_block);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int rc = by_dtype(p->dtype, [&](auto t) -> int {
         using T = decltype(t);
         if (!skinny_ok<T>(p)) return 0;
+        if (route) { *route = gemm_route_code(MVLT_GEMM_ROUTE_SKINNY, 1); return 1; }
         hipLaunchKernelGGL((gemm_skinny_kernel<T, false>), dim3(ceil_div(p->N, 16)), dim3(64 * SKINNY_WAVES), 0, s, d, ArgmaxOut{nullptr, nullptr});
         return hipGetLastError() == hipSuccess ? 1 : -1;
     });

@@ -21,12 +21,12 @@ int main(int argc, char** argv) {
     if (cs == 0) { d.epi = MVLT_EPI_BIAS | MVLT_EPI_GELU | MVLT_EPI_SAVE_PRE; d.bias = bias; d.pre = P; }
     if (cs == 1) { d.epi = MVLT_EPI_MUL_GELU_GRAD; d.aux = X; }
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-    for (int i = 0; i < 3; ++i) if (mvlt_rowstream_try(&d, cs != 0, nullptr) != 1) { printf("not taken\n"); return 1; }
+    for (int i = 0; i < 3; ++i) if (mvlt_rowstream_try(&d, cs != 0, nullptr, nullptr) != 1) { printf("not taken\n"); return 1; }
     hipDeviceSynchronize();
     float best = 1e9f;
     for (int r = 0; r < 5; ++r) {
         hipEventRecord(e0);
-        for (int i = 0; i < 10; ++i) mvlt_rowstream_try(&d, cs != 0, nullptr);
+        for (int i = 0; i < 10; ++i) mvlt_rowstream_try(&d, cs != 0, nullptr, nullptr);
         hipEventRecord(e1); hipEventSynchronize(e1);
         float ms; hipEventElapsedTime(&ms, e0, e1); ms /= 10;
         if (ms < best) best = ms;
