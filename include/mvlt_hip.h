@@ -36,13 +36,13 @@ enum { MVLT_OK = 0, MVLT_ERR_ARG = -1, MVLT_ERR_LAUNCH = -2, MVLT_ERR_UNSUPPORTE
  * signature; a binding compiles / hard-codes the value it was written against and compares it with what the
  * loaded library returns.  mvlt_sizeof(MVLT_STRUCT_*) lets a binding that mirrors the structs by hand (ctypes,
  * cgo, JNI) prove that its mirror has the size the library was compiled with (0 for an unknown id). */
-#define MVLT_ABI_VERSION 11
+#define MVLT_ABI_VERSION 12
 int mvlt_version(void);            /* MVLT_ABI_VERSION of the loaded library */
 const char* mvlt_arch(void);       /* "gfx950" */
 enum { MVLT_STRUCT_GEMM = 0, MVLT_STRUCT_LAYERNORM = 1, MVLT_STRUCT_LAYERNORM_BWD = 2, MVLT_STRUCT_LN_REDUCE_ITEM = 3,
        MVLT_STRUCT_ATTN = 4, MVLT_STRUCT_SWIN_WMSA = 5, MVLT_STRUCT_EMBED = 6, MVLT_STRUCT_ATTN_CACHED = 7,
        MVLT_STRUCT_ZERO_ITEM = 8, MVLT_STRUCT_RANGE = 9, MVLT_STRUCT_MLM_MASK = 10, MVLT_STRUCT_GREEDY_STATE = 11, MVLT_STRUCT_SWIN_DBIAS_ITEM = 12,
-       MVLT_STRUCT_SAMPLE_STATE = 13, MVLT_STRUCT_COUNT = 14 };
+       MVLT_STRUCT_SAMPLE_STATE = 13, MVLT_STRUCT_SAMPLE_FILTER = 14, MVLT_STRUCT_COUNT = 15 };
 size_t mvlt_sizeof(int struct_id);
 
 /* ------------------------------------------------------------------ GEMM
@@ -187,6 +187,31 @@ typedef struct MvltSampleState {
     const uint64_t* seed; uint32_t tag0; float inv_temperature;
 } MvltSampleState;
 int mvlt_gemm_sample_step(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltSampleState* g, void* stream);
+/* The sampled pick behind a top-k / top-p filter (HF TopKLogitsWarper, then TopPLogitsWarper; sample_mode = 'sample' with
+ * top_k / top_p).  A filter is a set function of a whole row, so the product writes x (as above, bit for bit) into the caller's
+ * workspace `x` ([M, ldx] f32, ldx >= N) and a second launch, one workgroup per row, selects and draws.  Per row m:
+ *   top-k  (1 <= top_k < N; 0 or >= N: off)  tau_k = the k-th largest x counted with multiplicity, K1 = {n : x_n >= tau_k}:
+ *          ties at the threshold are ALL kept (HF's `scores < kth` rule), |K1| >= k
+ *   top-p  (0 < top_p < 1; >= 1: off), applied after top-k: w_n = exp(x_n - max x), S = sum_K1 w, A(v) = sum_{j in K1, x_j > v} w_j,
+ *          K = {n in K1 : A(x_n) < top_p S} -- a token is kept while the mass strictly above it has not reached top_p.  HF's
+ *          nucleus rule without a dependence on the sort order: tie-inclusive, the row maximum is always kept
+ *          (min_tokens_to_keep = 1).  K = {x_n >= tau} for one threshold per row.
+ *   G_n = the Gumbel noise of mvlt_gemm_sample at index (row0 + m) * N + n (row0: the call's first row within a larger batch,
+ *         so a batch issued in row chunks draws what one call would), y_n = x_n + G_n (f32)
+ *   out_idx[m] = first argmax_{n in K} y_n,  out_logprob[m] = x[out_idx[m]] - log sum_{n in K} exp(x_n)   (renormalised)
+ * With both filters off the token is mvlt_gemm_sample's, bit for bit.  Deterministic: integer histograms, masses as 64-bit fixed
+ * point (rint(2^32 w), relative error of a mass sum <= E_MASS(N) = (3 ln N + 4) 2^-24 + N 2^-33 + 2^-51, csrc/skinny.hip),
+ * no float atomics -- the same operands give the same set, token and score.
+ * Refusals: those of mvlt_gemm_sample (part_val / part_idx are checked like there; this version keeps the row in `x` and leaves
+ * them unwritten), and MVLT_ERR_ARG for filter or filter->x NULL, ldx < N, top_k < 0, top_p <= 0 or NaN,
+ * (row0 + M) * N >= 2^32.  A refused call launches nothing and writes nothing. */
+typedef struct MvltSampleFilter { int32_t top_k; float top_p; float* x; int64_t ldx; uint32_t row0; } MvltSampleFilter;
+int mvlt_gemm_sample_filtered(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltSampleFilter* filter,
+                              int64_t* out_idx, float* out_logprob, uint64_t seed, uint32_t tag, float inv_temperature,
+                              void* stream);
+/* The graph form: mvlt_gemm_sample_step (same state, same seed / tag0 + column convention) with the filtered pick. */
+int mvlt_gemm_sample_filtered_step(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltSampleFilter* filter,
+                                   const MvltSampleState* g, void* stream);
 
 /* Decode step (model.py:82-108: 2 new tokens per sample): skinny product with the reduction split over workgroups:
  * acc[s][M][N] (f32, k_splits slabs) = A[:, k-slice s] B[:, k-slice s]^T, M <= 64, both operands k-contiguous, no epilogue;

@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(_HERE, "libmvlt_hip.so")
 
 F32, BF16 = 0, 1
 OK = 0
-ABI_VERSION = 11         # == MVLT_ABI_VERSION of the include/mvlt_hip.h these mirrors were written against
+ABI_VERSION = 12         # == MVLT_ABI_VERSION of the include/mvlt_hip.h these mirrors were written against
 ERRORS = {-1: "MVLT_ERR_ARG", -2: "MVLT_ERR_LAUNCH", -3: "MVLT_ERR_UNSUPPORTED"}
 
 EPI_BIAS, EPI_GELU, EPI_SAVE_PRE, EPI_DROPOUT = 1, 2, 4, 8
@@ -141,6 +141,10 @@ class MvltSampleState(C.Structure):
     _fields_ = MvltGreedyState._fields_ + [("seed", vp), ("tag0", u32), ("inv_temperature", f32)]
 
 
+class MvltSampleFilter(C.Structure):
+    _fields_ = [("top_k", i32), ("top_p", f32), ("x", vp), ("ldx", i64), ("row0", u32)]
+
+
 # every symbol include/mvlt_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "mvlt_version": (i32, []),
@@ -157,6 +161,8 @@ SYMBOLS = {
     "mvlt_gemm_argmax_greedy": (i32, [C.POINTER(MvltGemm), vp, vp, C.POINTER(MvltGreedyState), vp]),
     "mvlt_gemm_sample": (i32, [C.POINTER(MvltGemm), vp, vp, vp, vp, u64, u32, f32, vp]),
     "mvlt_gemm_sample_step": (i32, [C.POINTER(MvltGemm), vp, vp, C.POINTER(MvltSampleState), vp]),
+    "mvlt_gemm_sample_filtered": (i32, [C.POINTER(MvltGemm), vp, vp, C.POINTER(MvltSampleFilter), vp, vp, u64, u32, f32, vp]),
+    "mvlt_gemm_sample_filtered_step": (i32, [C.POINTER(MvltGemm), vp, vp, C.POINTER(MvltSampleFilter), C.POINTER(MvltSampleState), vp]),
     "mvlt_gemm_skinny_accum": (i32, [C.POINTER(MvltGemm), vp, i32, vp]),
     "mvlt_layernorm_acc_fwd": (i32, [i32, vp, i32, vp, vp, vp, vp, f32, i32, i32, vp, vp]),
     "mvlt_colsum": (i32, [i32, vp, i64, i32, i32, vp, i32, vp, vp]),
@@ -218,7 +224,7 @@ SYMBOLS = {
 # ctypes mirror of every struct, in the order of the MVLT_STRUCT_* ids of the header
 STRUCTS = [MvltGemm, MvltLayerNorm, MvltLayerNormBwd, MvltLnReduceItem, MvltAttn, MvltSwinWmsa, MvltEmbed,
            MvltAttnCached, MvltZeroItem, MvltRange, MvltMlmMask, MvltGreedyState, MvltSwinDbiasItem,
-           MvltSampleState]
+           MvltSampleState, MvltSampleFilter]
 
 _lib = None
 

@@ -723,6 +723,7 @@ extern "C" size_t mvlt_sizeof(int struct_id) {
         case MVLT_STRUCT_GREEDY_STATE: return sizeof(MvltGreedyState);
         case MVLT_STRUCT_SWIN_DBIAS_ITEM: return sizeof(MvltSwinDbiasItem);
         case MVLT_STRUCT_SAMPLE_STATE: return sizeof(MvltSampleState);
+        case MVLT_STRUCT_SAMPLE_FILTER: return sizeof(MvltSampleFilter);
         default: return 0;
     }
 }

@@ -1,6 +1,7 @@
 // Everything the decode path runs at M <= 64 (see include/mvlt_hip.h): the skinny product behind mvlt_gemm, its K-split form
 // (mvlt_gemm_skinny_accum), and the MLM head fused with the pick of the next token -- greedy (mvlt_gemm_argmax,
-// mvlt_gemm_argmax_greedy) and sampled (mvlt_gemm_sample, mvlt_gemm_sample_step).  No LDS staging anywhere: the weight matrix is
+// mvlt_gemm_argmax_greedy), sampled (mvlt_gemm_sample, mvlt_gemm_sample_step) and sampled behind a top-k / top-p filter
+// (mvlt_gemm_sample_filtered, mvlt_gemm_sample_filtered_step).  No LDS staging in the products: the weight matrix is
 // read once and nothing is reused inside a workgroup, so every wave loads its MFMA fragments straight from global memory.
 // Same argument block as the tile kernels of gemm.hip (gemm_dev.h); gemm.hip reaches the plain product through mvlt_skinny_try.
 #include "common.h"
@@ -470,6 +471,217 @@ __global__ __launch_bounds__(256) void sample_pick_kernel(const float* part_val,
     }
 }
 
+// FILTERED sampled pick (top-k / top-p, mvlt_gemm_sample_filtered / _step).  A filter is a set function of a whole row of x, so
+// the row has to exist: the product writes x[m, n] (f32, [M, ldx]) into a workspace and a finishing kernel per row selects the
+// threshold and draws.  The product is a SIBLING of gemm_sample128_kernel (a third copy of the main loop, for the reason given
+// there; gemm_sample128_kernel itself is untouched): the same loads and MFMAs in the same order and the same two rounded
+// epilogue operations, so x is bit for bit the value that kernel forms.  It computes no noise.
+// vec: ldx % 4 == 0 and a 16-byte aligned workspace (whole 4-column groups go out as one 16-byte store).
+template <typename T, int NRT>
+__global__ __launch_bounds__(64 * SKINNY_WAVES) void gemm_logits128_kernel(const GemmDev p, float* xout, long ldx, int vec, float inv_t) {
+    using M_ = Mma<T>;
+    using Frag = typename M_::Frag;
+    constexpr int KB = M_::KB, E = TypeInfo<T>::E, UNR = NRT <= 2 ? 12 : 8;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), r15 = lane & 15, g = lane >> 4;
+    const int n0 = (blockIdx.x * SKINNY_WAVES + wave) * 16;
+    if (n0 >= p.N) return;
+    const T* A = reinterpret_cast<const T*>(p.A);
+    const T* brow = reinterpret_cast<const T*>(p.B) + (long)min(n0 + r15, p.N - 1) * p.ldb + g * E;
+    const T* arow[NRT];
+#pragma unroll
+    for (int i = 0; i < NRT; ++i) arow[i] = A + (long)min(16 * i + r15, p.M - 1) * p.lda + g * E;
+    f32x4 acc[NRT];
+#pragma unroll
+    for (int i = 0; i < NRT; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int nkb = p.K / KB;
+    for (int kb0 = 0; kb0 < nkb; kb0 += UNR) {
+        Frag fb[UNR], fa[UNR][NRT];
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            const int k = min(kb0 + u, nkb - 1) * KB;          // past the end: reload the last block, never multiplied
+            fb[u] = skinny_wload(reinterpret_cast<const Frag*>(brow + k));
+#pragma unroll
+            for (int i = 0; i < NRT; ++i) fa[u][i] = *reinterpret_cast<const Frag*>(arow[i] + k);
+        }
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            if (kb0 + u < nkb) {
+#pragma unroll
+                for (int i = 0; i < NRT; ++i) M_::mma(acc[i], fb[u], fa[u][i]);
+            }
+        }
+    }
+    // acc[i][r] <-> n = n0 + 4 g + r, m = 16 i + r15
+    f32x4 bias4{0.f, 0.f, 0.f, 0.f};
+    if (p.epi & MVLT_EPI_BIAS) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bias4[r] = p.bias[min(n0 + 4 * g + r, p.N - 1)];
+    }
+#pragma unroll
+    for (int i = 0; i < NRT; ++i) {
+        const int m = 16 * i + r15, n = n0 + 4 * g;
+        if (m >= p.M) continue;
+        f32x4 x;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) x[r] = __fmul_rn(__fadd_rn(acc[i][r], bias4[r]), inv_t);
+        float* o = xout + (long)m * ldx + n;
+        if (vec && n + 4 <= p.N) store4f(o, x);
+        else
+#pragma unroll
+            for (int r = 0; r < 4; ++r) if (n + r < p.N) o[r] = x[r];
+    }
+}
+
+// Finish of the filtered pick, one workgroup of 1024 threads per row (thread t owns the columns t, t + 1024, ...: a fixed map).
+//   key(x)   the order-preserving 32-bit image of x (-0 counts as +0), so every comparison below is an integer one
+//   tau_k    k-th largest key: exact radix select, four 8-bit digits from the top.  A digit pass histograms the candidates (keys
+//            that match the digits chosen so far) by integer LDS adds and one wave walks the 256 bins from the top:
+//            tau = the largest v with #{key >= v} >= k.  Ties at tau are all kept.
+//   tau_p    over K1 = {key >= tau_k}: the SAME select with the count replaced by the mass q_n = rint(2^32 exp(x_n - max x)), a
+//            64-bit integer, and k by P = ceil(top_p S), S = sum_K1 q: the largest v whose inclusive mass C(v) = sum_{key >= v} q
+//            reaches P.  Then the mass strictly above tau_p is < P (tau_p is kept: A(x_n) < top_p S) and every smaller value has
+//            A >= C(tau_p) >= P (not kept), which is the issue's rule K = {n in K1 : A(x_n) < top_p S}; the row maximum has
+//            A = 0 and is always kept.
+//   pick     over {key >= max(tau_k, tau_p)} only: y = x + gumbel_noise(seed, tag, (row0 + m) N + n), first index of the largest y,
+//            and the kept sum of exp(x - max x) in f32 by a fixed tree (per thread four accumulators over its own columns in
+//            ascending order, the wave's xor tree, the 16 wave sums in wave order) -> score = x_tok - (max x + logf(sum)).
+// Determinism: histograms are integer adds (order-free), the f32 sum has a fixed shape, no float atomics; the same operands
+// give the same set, token and score run to run and graph against eager.
+// The row is RE-READ from the workspace in every pass (up to ten: max, 4 + 4 digits, pick) instead of being held in LDS: 64 rows
+// x 119 KiB stay in L2 after the first pass, a pass is 30 coalesced dword loads per thread, and nothing caps N -- an LDS copy
+// needs a > 64 KiB dynamic allocation that stops at N = 40 K and ties the launch to one vocabulary size.
+// Mass arithmetic, relative to a sum that holds the row maximum (q = 2^32; every S, P, A(v) != 0 and C(v) does):
+//   __expf(d), d = x - max <= 0: rounding of d (2^-24 |d|), d log2 e with a rounded constant (1.5 2^-24 |d|), v_exp_f32 <= 1 ulp
+//   (2^-23) -> (2.5 |d| + 2) 2^-24 per term, taken as (3 |d| + 4) 2^-24; mass-weighted, mean |d| <= ln N (entropy <= ln N and the
+//   sum is >= 1), so (3 ln N + 4) 2^-24 for the sum.  Quantisation: <= 1/2 per term against a sum >= 2^32: N 2^-33.  Summation:
+//   integers, exact (N < 2^32 terms <= 2^32 fit 64 bits).  P = ceil(top_p S) in f64 with S converted once: 2^-51.
+//       E_MASS(N) = (3 ln N + 4) 2^-24 + N 2^-33 + 2^-51          (5.6e-6 at N = 30522; tests/sample_filter_ref.py restates it)
+constexpr int FILT_THREADS = 1024, FILT_COPIES = 16;
+MVLT_DEV uint32_t filt_key(float x) {
+    uint32_t u = __float_as_uint(x);
+    if (u == 0x80000000u) u = 0u;
+    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+MVLT_DEV unsigned long long filt_mass(float x, float xmax) {
+    return (unsigned long long)__float2ull_rn(__expf(__fadd_rn(x, -xmax)) * 4294967296.0f);
+}
+struct FilterIn { const float* x; long ldx; int top_k; float top_p; uint32_t row0; };
+template <bool STEP>
+__global__ __launch_bounds__(FILT_THREADS) void sample_filter_pick_kernel(const FilterIn f, int M, int N, const SampleIn si, const GreedyState st,
+                                                                           int64_t* out_idx, float* out_logprob) {
+    __shared__ unsigned long long hist[256 * FILT_COPIES];          // [bin][copy]: the copies of a bin lie in different banks
+    __shared__ unsigned long long s_above;
+    __shared__ int s_bin;
+    __shared__ float s_val[16], s_x[16], s_f[16];
+    __shared__ int s_idx[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, m = blockIdx.x;
+    const long col = STEP ? st.col[0] : 0;
+    const uint64_t seed = si.seed_dev ? si.seed_dev[0] : si.seed;
+    const uint32_t tag = si.tag0 + (si.col ? (uint32_t)si.col[0] : 0u);
+    const float* x = f.x + (long)m * f.ldx;
+    // ---- row maximum
+    float xmax = -3.0e38f;
+    for (int n = tid; n < N; n += FILT_THREADS) xmax = fmaxf(xmax, x[n]);
+    xmax = wave_max(xmax);
+    if (lane == 0) s_f[wave] = xmax;
+    __syncthreads();
+    xmax = s_f[0];
+#pragma unroll
+    for (int w = 1; w < 16; ++w) xmax = fmaxf(xmax, s_f[w]);
+    __syncthreads();          // (s_f is written again by the pick)
+    // ---- the two selects: mode 0 = top-k (weight 1, target k), mode 1 = top-p over key >= tau_k (weight q, target ceil(top_p S))
+    uint32_t tau = 0u;          // keep key >= tau; 0 keeps everything
+    const bool use_k = f.top_k >= 1 && f.top_k < N, use_p = f.top_p < 1.0f;
+    for (int mode = use_k ? 0 : 1; mode < (use_p ? 2 : 1); ++mode) {
+        const uint32_t floor_key = tau;
+        uint32_t prefix = 0u;
+        unsigned long long above = 0ull, target = (unsigned long long)f.top_k;          // (target: wave 0 only)
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            for (int i = tid; i < 256 * FILT_COPIES; i += FILT_THREADS) hist[i] = 0ull;
+            __syncthreads();
+            const uint32_t pmask = shift == 24 ? 0u : 0xFFFFFFFFu << (shift + 8);
+            for (int n = tid; n < N; n += FILT_THREADS) {
+                const float v = x[n];
+                const uint32_t key = filt_key(v);
+                if ((key & pmask) == prefix && key >= floor_key) {
+                    const unsigned long long w = mode == 0 ? 1ull : filt_mass(v, xmax);
+                    atomicAdd(&hist[((key >> shift) & 255u) * FILT_COPIES + (tid & (FILT_COPIES - 1))], w);
+                }
+            }
+            __syncthreads();
+            if (wave == 0) {          // lane l: bins 4 l .. 4 l + 3; higher lanes hold higher bins
+                unsigned long long t[4], s = 0ull;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    t[j] = 0ull;
+#pragma unroll
+                    for (int c = 0; c < FILT_COPIES; ++c) t[j] += hist[(4 * lane + j) * FILT_COPIES + c];
+                    s += t[j];
+                }
+                unsigned long long inc = s;          // -> sum over the lanes >= this one
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) {
+                    const unsigned long long v = __shfl_down(inc, o, 64);
+                    if (lane + o < 64) inc += v;
+                }
+                if (mode == 1 && shift == 24) {          // S = the mass of K1; P = ceil(top_p S) (top_p <= 1 - 2^-24 and S >= 2^32: P <= S)
+                    const unsigned long long S = __shfl(inc, 0, 64);
+                    target = (unsigned long long)ceil((double)f.top_p * (double)S);
+                    if (target < 1ull) target = 1ull;
+                    if (target > S) target = S;
+                }
+                const unsigned long long hi = above + (inc - s);          // weight of everything above this lane's bins
+                if (hi < target && hi + s >= target) {          // exactly one lane: above < target <= above + the candidates' total
+                    unsigned long long a = hi; int b = 4 * lane;
+#pragma unroll
+                    for (int j = 3; j >= 1; --j) {
+                        if (b == 4 * lane) { if (a + t[j] >= target) b = 4 * lane + j; else a += t[j]; }
+                    }
+                    s_bin = b; s_above = a;
+                }
+            }
+            __syncthreads();
+            prefix |= (uint32_t)s_bin << shift;
+            above = s_above;
+            __syncthreads();
+        }
+        tau = prefix;
+    }
+    // ---- the pick over the kept columns
+    float best = -3.0e38f, bx = 0.f, se[4] = {0.f, 0.f, 0.f, 0.f}; int bi = 0x7fffffff;
+    const uint32_t idx0 = (f.row0 + (uint32_t)m) * (uint32_t)N;
+    int j = 0;
+    for (int n = tid; n < N; n += FILT_THREADS, ++j) {
+        const float v = x[n];
+        if (filt_key(v) >= tau) {
+            const float y = __fadd_rn(v, gumbel_noise(seed, tag, idx0 + (uint32_t)n));
+            if (y > best) { best = y; bi = n; bx = v; }          // ascending n: ties keep the first index
+            se[j & 3] += __expf(__fadd_rn(v, -xmax));
+        }
+    }
+    float sum = (se[0] + se[1]) + (se[2] + se[3]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64), ox = __shfl_xor(bx, o, 64); const int oi = __shfl_xor(bi, o, 64);
+        if (BEATS(ov, oi, best, bi)) { best = ov; bi = oi; bx = ox; }
+        sum += __shfl_xor(sum, o, 64);
+    }
+    if (lane == 0) { s_val[wave] = best; s_idx[wave] = bi; s_x[wave] = bx; s_f[wave] = sum; }
+    __syncthreads();
+    if (tid == 0) {
+        sum = s_f[0];
+        for (int w = 1; w < 16; ++w) {
+            const float ov = s_val[w]; const int oi = s_idx[w];
+            if (BEATS(ov, oi, best, bi)) { best = ov; bi = oi; bx = s_x[w]; }
+            sum += s_f[w];
+        }
+        const float lse = __fadd_rn(xmax, logf(sum));
+        const float score = __fadd_rn(bx, -lse);
+        if (STEP) pick_bookkeeping(st, m, M, col, bi, score);
+        else { out_idx[m] = bi; out_logprob[m] = score; }
+    }
+}
+
 // --------------------------------------------------------------------------------------------------------------- host
 // run f(T{}) for the product's element type
 template <typename F> int by_dtype(const int dtype, F&& f) {
@@ -615,6 +827,54 @@ extern "C" int mvlt_gemm_sample_step(const MvltGemm* p, float* part_val, int32_t
     hipLaunchKernelGGL(sample_pick_kernel<true>, dim3(p->M), dim3(256), 0, s, part_val, part_idx, parts_of(p), p->M, st, (int64_t*)nullptr, (float*)nullptr);
     MVLT_LAUNCH_CHECK();
     return MVLT_OK;
+}
+
+// the two launches of the filtered pick: x = the product (bit for bit gemm_sample128_kernel's), then a workgroup per row
+namespace {
+int filter_check(const MvltGemm* p, const MvltSampleFilter* f) {
+    MVLT_CHECK(f && f->x && f->ldx >= p->N && f->top_k >= 0 && f->top_p > 0.f, MVLT_ERR_ARG);          // (a NaN top_p fails > 0)
+    MVLT_CHECK(((long)f->row0 + p->M) * p->N < (1L << 32), MVLT_ERR_ARG);
+    return MVLT_OK;
+}
+template <bool STEP>
+int filtered_launch(const MvltGemm* p, const MvltSampleFilter* f, const SampleIn& si, const GreedyState& st, int64_t* out_idx, float* out_logprob,
+                    hipStream_t s) {
+    const int rc = by_dtype(p->dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        MVLT_CHECK(skinny_ok<T>(p), MVLT_ERR_UNSUPPORTED);
+        const GemmDev d = skinny_dev(p);
+        const int vec = (f->ldx % 4 == 0 && aligned16(f->x)) ? 1 : 0;
+        LAUNCH_NRT(gemm_logits128_kernel, T, p->M, dim3(ceil_div(parts_of(p), SKINNY_WAVES)), dim3(64 * SKINNY_WAVES), s, d, f->x, (long)f->ldx, vec,
+                   si.inv_t);
+        return (int)MVLT_OK;
+    });
+    if (rc != MVLT_OK) return rc;
+    const FilterIn fi{f->x, (long)f->ldx, f->top_k, f->top_p, f->row0};
+    hipLaunchKernelGGL(sample_filter_pick_kernel<STEP>, dim3(p->M), dim3(FILT_THREADS), 0, s, fi, p->M, p->N, si, st, out_idx, out_logprob);
+    MVLT_LAUNCH_CHECK();
+    return MVLT_OK;
+}
+}  // namespace
+
+extern "C" int mvlt_gemm_sample_filtered(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltSampleFilter* filter, int64_t* out_idx,
+                                         float* out_logprob, uint64_t seed, uint32_t tag, float inv_temperature, void* stream) {
+    { const int rc = sample_check(p, part_val, part_idx, inv_temperature); if (rc != MVLT_OK) return rc; }
+    { const int rc = filter_check(p, filter); if (rc != MVLT_OK) return rc; }
+    MVLT_CHECK(out_idx && out_logprob, MVLT_ERR_ARG);
+    const SampleIn si{nullptr, seed, nullptr, tag, inv_temperature};
+    return filtered_launch<false>(p, filter, si, GreedyState{}, out_idx, out_logprob, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int mvlt_gemm_sample_filtered_step(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltSampleFilter* filter,
+                                              const MvltSampleState* g, void* stream) {
+    MVLT_CHECK(g, MVLT_ERR_ARG);
+    { const int rc = sample_check(p, part_val, part_idx, g->inv_temperature); if (rc != MVLT_OK) return rc; }
+    { const int rc = filter_check(p, filter); if (rc != MVLT_OK) return rc; }
+    MVLT_CHECK(g->seed, MVLT_ERR_ARG);
+    GreedyState st;
+    { const int rc = greedy_state(g, st); if (rc != MVLT_OK) return rc; }
+    const SampleIn si{g->seed, 0, g->col, g->tag0, g->inv_temperature};
+    return filtered_launch<true>(p, filter, si, st, nullptr, nullptr, reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int mvlt_gemm_skinny_accum(const MvltGemm* p, float* acc, int k_splits, void* stream) {

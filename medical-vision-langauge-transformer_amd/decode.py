@@ -13,6 +13,10 @@ output column and finished flags live on the device; ``MVLT_DECODE_GRAPH=0`` sel
 the eager loop).  'sample' mode (B <= 64) is the same graph with the Gumbel-max pick of ``mvlt_gemm_sample_step`` as
 its head: the token of output column c is ``argmax_n (logit_n / T + G_n)`` with the noise a pure function of
 ``(seed, SAMPLE_TAG0 + c, row * V + n)``, so the graph loop and the eager loop draw the same tokens from the same seed.
+``top_k`` / ``top_p`` ('sample' mode only) put ``mvlt_gemm_sample_filtered_step`` in the head's place: the logits of the row go
+through a workspace, a workgroup per row selects the threshold (top-k with ties kept, then the nucleus over what is left) and
+draws among the kept tokens with the same noise; the score is the log-probability under the renormalised distribution.  The
+eager loop calls the stand-alone entry point, for B > 64 in row chunks of 64 whose noise is indexed by the row of the batch.
 Beam search (``beam_search``): same cached steps over B*beams rows, cache rows gathered by beam
 index, scorer bookkeeping restated from HF transformers 4.16 (parity with the reference unpinned).
 """
@@ -146,7 +150,7 @@ class _GreedyGraph:
     def __reduce__(self):                 # captured graphs do not survive pickling: rebuilt on the next call
         return (_no_graph, ())
 
-    def __init__(self, model, B, n_img, max_length, cd, pad, eos, mask_id, key, mode='greedy', temperature=1.0):
+    def __init__(self, model, B, n_img, max_length, cd, pad, eos, mask_id, key, mode='greedy', temperature=1.0, top_k=0, top_p=1.0):
         mv, cfg = model.MVLBert, model.config
         dev = next(model.parameters()).device
         H, nH = cfg.hidden_size, cfg.num_attention_heads
@@ -169,7 +173,7 @@ class _GreedyGraph:
         # device-side state of the greedy loop, handed to mvlt_gemm_argmax_greedy: the pick, PAD for finished samples, the
         # EOS flags, the ids / scores columns, the next input id, `past` and `col` are all advanced by its finishing launch
         # (mode 'sample': mvlt_gemm_sample_step, the same state plus the seed cell the loop fills before the first replay)
-        self.mode = mode
+        self.mode, self.top_k, self.top_p = mode, top_k, top_p          # (top_k, top_p) = (0, 1.0): no filter
         self.seed = torch.zeros(1, dtype=torch.int64, device=dev)
         st = self.state = L.MvltGreedyState() if mode == 'greedy' else L.MvltSampleState()
         if mode != 'greedy':
@@ -188,8 +192,12 @@ class _GreedyGraph:
         hd = model.MLM_head_seq2seq
         _, _, t2, _, _ = hd._transform(ar, self.hlast, False)
         # decoder GEMM fused with the greedy pick and its bookkeeping: the [B, 30522] logits are never written
+        W, bias = ar.compute(hd.predictions.decoder.weight), hd.predictions.decoder.bias.data
+        if self.mode != 'greedy' and (self.top_k, self.top_p) != (0, 1.0):
+            ops.gemm_sample_filtered_step(t2, W, bias, self.state, self.top_k, self.top_p)
+            return
         pick = ops.gemm_argmax_greedy if self.mode == 'greedy' else ops.gemm_sample_step
-        pick(t2, ar.compute(hd.predictions.decoder.weight), hd.predictions.decoder.bias.data, self.state)
+        pick(t2, W, bias, self.state)
 
     def forward2(self):
         """2-token cached forward of [last token, MASK] at positions past, past+1 (model.py:82-108).  `past` was advanced by
@@ -215,7 +223,7 @@ class _GreedyGraph:
         self.graph = g
 
 
-def _greedy_graph_loop(model, feat, max_length, pad, eos, mask_id, cd, mode='greedy', seed=0, temperature=1.0):
+def _greedy_graph_loop(model, feat, max_length, pad, eos, mask_id, cd, mode='greedy', seed=0, temperature=1.0, top_k=0, top_p=1.0):
     mv, cfg = model.MVLBert, model.config
     B, n_img, H = feat.shape
     nH = cfg.num_attention_heads
@@ -225,9 +233,11 @@ def _greedy_graph_loop(model, feat, max_length, pad, eos, mask_id, cd, mode='gre
     slot = "_mvlt_greedy_graph"
     if mode != 'greedy':          # a graph of its own beside the greedy one: neither recaptures the other
         key, slot = key + (mode, float(temperature)), "_mvlt_sample_graph"
+        if (top_k, top_p) != (0, 1.0):          # a filtered graph takes the sampled graph's slot, like a new temperature
+            key = key + (top_k, top_p)
     gg = model.__dict__.get(slot)
     if gg is None or gg.key != key:
-        gg = _GreedyGraph(model, B, n_img, max_length, cd, pad, eos, mask_id, key, mode, temperature)
+        gg = _GreedyGraph(model, B, n_img, max_length, cd, pad, eos, mask_id, key, mode, temperature, top_k, top_p)
         gg.capture()
         model.__dict__[slot] = gg
     gg.seed.fill_(ops.s64(int(seed) & ((1 << 64) - 1)))
@@ -262,12 +272,18 @@ def _greedy_graph_loop(model, feat, max_length, pad, eos, mask_id, cd, mode='gre
 
 @torch.no_grad()
 def greedy_search(model, image_feature, learning_strategy='unilm', sample_mode='greedy', max_length=None,
-                  pad_token_id=None, eos_token_id=None, seed=None, temperature=1.0):
+                  pad_token_id=None, eos_token_id=None, seed=None, temperature=1.0, top_k=0, top_p=1.0):
     """Returns ``(input_ids [B, n_steps], token_scores)`` like the reference
     (model.py:984: scores of all but the final step, concatenated along dim -1).
     ``sample_mode='sample'``, B <= 64: Gumbel-max draws from softmax(logits / temperature), reproducible from ``seed``
     (None: a 63-bit seed from torch's default CPU generator, so torch.manual_seed makes a run reproducible); the graph
-    loop and the eager loop give the same tokens.  B > 64 samples with torch.multinomial (seed / temperature unused)."""
+    loop and the eager loop give the same tokens.  B > 64 without a filter samples with torch.multinomial (seed / temperature
+    unused).
+    ``top_k`` (0 = off) / ``top_p`` (1.0 = off), 'sample' mode only: keep the top_k largest logits (ties at the threshold all
+    kept), then the tokens whose probability mass strictly above them is below top_p of what is left; draw among those, score =
+    log-probability under the renormalised distribution.  Any B (rows in chunks of 64 beyond that, same draws); a filter in
+    another mode, top_k < 0, top_p <= 0 or a NaN raises ValueError."""
+    top_k, top_p = ops.check_sample_filter(top_k, top_p)
     if learning_strategy != 'unilm':
         raise NotImplementedError("only learning_strategy='unilm' is coherent with the KV cache (SURVEY.md 3.3)")
     mv, cfg = model.MVLBert, model.config
@@ -280,24 +296,28 @@ def greedy_search(model, image_feature, learning_strategy='unilm', sample_mode='
     tok = getattr(model, "tokenizer", None)
     mask_id = tok.mask_token_id if tok is not None else cfg.mask_token_id
     feat = image_feature.to(cd).contiguous()
+    V = model.MLM_head_seq2seq.predictions.decoder.out_features
+    top_k, top_p = (top_k if top_k < V else 0), min(top_p, 1.0)          # the values that mean "off" in one spelling each
+    filtered = (top_k, top_p) != (0, 1.0)
+    if filtered and sample_mode != 'sample':
+        raise ValueError("top_k / top_p filter the sampled pick: they need sample_mode='sample'")
     # (the fused decoder-GEMM + argmax of the graph path holds the whole batch in one 64-row tile)
     if sample_mode == 'greedy' and os.environ.get("MVLT_DECODE_GRAPH", "1") == "1" and feat.shape[0] <= 64:
         return _greedy_graph_loop(model, feat, max_length, pad, eos, mask_id, cd)
-    fused_sample = sample_mode == 'sample' and feat.shape[0] <= 64
+    fused_sample = sample_mode == 'sample' and (feat.shape[0] <= 64 or filtered)
     if fused_sample:
         if not float(temperature) > 0.0:
             raise ValueError("temperature must be positive")
         if seed is None:
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
-        if os.environ.get("MVLT_DECODE_GRAPH", "1") == "1":
-            return _greedy_graph_loop(model, feat, max_length, pad, eos, mask_id, cd, 'sample', seed, temperature)
+        if os.environ.get("MVLT_DECODE_GRAPH", "1") == "1" and feat.shape[0] <= 64:
+            return _greedy_graph_loop(model, feat, max_length, pad, eos, mask_id, cd, 'sample', seed, temperature, top_k, top_p)
     B, n_img, H = feat.shape
     nH = cfg.num_attention_heads
     hd = H // nH
     nl = len(mv.encoder.layer)
     dev = feat.device
     head = model.MLM_head_seq2seq
-    V = head.predictions.decoder.out_features
     cap = n_img + 2 + max_length + 1
     kc = [torch.zeros((B, nH, cap, hd), dtype=cd, device=dev) for _ in range(nl)]
     vc = [torch.zeros((B, nH, cap, hd), dtype=cd, device=dev) for _ in range(nl)]
@@ -307,6 +327,11 @@ def greedy_search(model, image_feature, learning_strategy='unilm', sample_mode='
         pre, t1, t2, _, _ = head._transform(ar, hlast.contiguous(), False)
         if sample_mode == 'greedy' and t2.shape[0] <= 64:
             return ops.gemm_argmax(t2, ar.compute(head.predictions.decoder.weight), head.predictions.decoder.bias.data)
+        if filtered:                  # stand-alone filtered pick; rows beyond 64 in chunks, the noise indexed by the batch row
+            W, bias = ar.compute(head.predictions.decoder.weight), head.predictions.decoder.bias.data
+            parts = [ops.gemm_sample_filtered(t2[r0:r0 + 64], W, bias, seed, SAMPLE_TAG0 + len(ids_cols), temperature, top_k, top_p, row0=r0)
+                     for r0 in range(0, t2.shape[0], 64)]
+            return torch.cat([a for a, _ in parts]), torch.cat([b for _, b in parts])
         if fused_sample:              # the pick of the graph loop, stand-alone: same seed, tag and column -> same tokens
             return ops.gemm_sample(t2, ar.compute(head.predictions.decoder.weight), head.predictions.decoder.bias.data,
                                    seed, SAMPLE_TAG0 + len(ids_cols), temperature)

@@ -686,7 +686,7 @@ class MVLBertForImageCaption(MVLBertPretrainedModel):
         self.tokenizer = tokenizer
         self.MLM_head_seq2seq = BertOnlyMLMHead(config)
 
-    def forward(self, image, caption, num_beams, learning_strategy, sample_mode='greedy', seed=None, temperature=1.0):
+    def forward(self, image, caption, num_beams, learning_strategy, sample_mode='greedy', seed=None, temperature=1.0, top_k=0, top_p=1.0):
         Arena.of(self, compute_dtype_of(self))
         image_feature = self.conv(image)
         if num_beams > 1:
@@ -695,7 +695,7 @@ class MVLBertForImageCaption(MVLBertPretrainedModel):
         if num_beams == 1:
             from .decode import greedy_search
             return greedy_search(self, image_feature, learning_strategy=learning_strategy, sample_mode=sample_mode,
-                                 seed=seed, temperature=temperature)
+                                 seed=seed, temperature=temperature, top_k=top_k, top_p=top_p)
         return self.encode_forward(image_feature, caption, learning_strategy)
 
     def encode_forward(self, image_feature, caption, learning_strategy):

@@ -391,6 +391,62 @@ def gemm_sample_step(A, W, bias, state):
     L.check(L.lib().mvlt_gemm_sample_step(C.byref(p), _p(pv), _p(pi), C.byref(state), _stream()), "mvlt_gemm_sample_step")
 
 
+def check_sample_filter(top_k, top_p):
+    """(int top_k, float top_p) of a sampled pick, or ValueError: top_k >= 0 (0 = off), top_p > 0 (>= 1 = off), no NaN."""
+    if isinstance(top_k, float) and top_k != top_k:
+        raise ValueError("top_k must be a non-negative integer")
+    k, p = int(top_k), float(top_p)
+    if k < 0 or k != top_k:
+        raise ValueError("top_k must be a non-negative integer (0 switches the filter off)")
+    if not p > 0.0:
+        raise ValueError("top_p must lie in (0, 1] (1 switches the filter off)")
+    return k, p
+
+
+_filter_ws_cache = {}
+
+
+def _sample_filter(M, N, device, top_k, top_p, row0):
+    """MvltSampleFilter with its [M, ldx] f32 logit workspace, keyed like the part buffers by the stream tag (a captured graph
+    keeps a workspace of its own: it records the address)."""
+    ldx = (N + 3) // 4 * 4
+    key = (M, ldx, device.index, _stream_cache[1])
+    ws = _filter_ws_cache.get(key)
+    if ws is None:
+        ws = _filter_ws_cache[key] = torch.empty((M, ldx), dtype=torch.float32, device=device)
+    f = L.MvltSampleFilter()
+    f.top_k, f.top_p, f.x, f.ldx, f.row0 = min(int(top_k), 2 ** 31 - 1), float(top_p), _p(ws), ldx, int(row0)
+    return f, ws
+
+
+def gemm_sample_filtered(A, W, bias, seed, tag, temperature=1.0, top_k=0, top_p=1.0, row0=0):
+    """gemm_sample behind a top-k / top-p filter (mvlt_gemm_sample_filtered): per row, keep the top_k largest logits (ties at
+    the threshold all kept; 0 = off), then the tokens whose mass strictly above is below top_p of what is left (1.0 = off), draw
+    among them by Gumbel-max and return the log-probability under the renormalised distribution.  ``row0``: index of row 0
+    within the batch the noise is indexed by, so a batch issued in row chunks draws what one call would.
+    A: [M <= 64, K], W: [N, K] -> (int64 [M], f32 [M])."""
+    top_k, top_p = check_sample_filter(top_k, top_p)
+    p, M, N = _head_gemm(A, W, bias)
+    pv, pi = _sample_parts(M, N, A.device)
+    f, _ = _sample_filter(M, N, A.device, top_k, top_p, row0)
+    idx = torch.empty(M, dtype=torch.int64, device=A.device)
+    lp = torch.empty(M, dtype=torch.float32, device=A.device)
+    L.check(L.lib().mvlt_gemm_sample_filtered(C.byref(p), _p(pv), _p(pi), C.byref(f), _p(idx), _p(lp), int(seed) & ((1 << 64) - 1),
+                                              int(tag) & 0xFFFFFFFF, 1.0 / float(temperature), _stream()), "mvlt_gemm_sample_filtered")
+    return idx, lp
+
+
+def gemm_sample_filtered_step(A, W, bias, state, top_k=0, top_p=1.0):
+    """gemm_sample_step with the filtered pick as its finish (mvlt_gemm_sample_filtered_step); ``state``: a prepared
+    ``L.MvltSampleState`` (decode._GreedyGraph, mode 'sample' with a filter)."""
+    top_k, top_p = check_sample_filter(top_k, top_p)
+    p, M, N = _head_gemm(A, W, bias)
+    pv, pi = _sample_parts(M, N, A.device)
+    f, _ = _sample_filter(M, N, A.device, top_k, top_p, 0)
+    L.check(L.lib().mvlt_gemm_sample_filtered_step(C.byref(p), _p(pv), _p(pi), C.byref(f), C.byref(state), _stream()),
+            "mvlt_gemm_sample_filtered_step")
+
+
 def gumbel_noise(seed, tag, rows, N, device):
     """The noise of gemm_sample as the kernel computes it, f32 [rows, N] (tests)."""
     out = torch.empty((rows, N), dtype=torch.float32, device=device)
