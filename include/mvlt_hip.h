@@ -36,13 +36,14 @@ enum { MVLT_OK = 0, MVLT_ERR_ARG = -1, MVLT_ERR_LAUNCH = -2, MVLT_ERR_UNSUPPORTE
  * signature; a binding compiles / hard-codes the value it was written against and compares it with what the
  * loaded library returns.  mvlt_sizeof(MVLT_STRUCT_*) lets a binding that mirrors the structs by hand (ctypes,
  * cgo, JNI) prove that its mirror has the size the library was compiled with (0 for an unknown id). */
-#define MVLT_ABI_VERSION 12
+#define MVLT_ABI_VERSION 13
 int mvlt_version(void);            /* MVLT_ABI_VERSION of the loaded library */
 const char* mvlt_arch(void);       /* "gfx950" */
 enum { MVLT_STRUCT_GEMM = 0, MVLT_STRUCT_LAYERNORM = 1, MVLT_STRUCT_LAYERNORM_BWD = 2, MVLT_STRUCT_LN_REDUCE_ITEM = 3,
        MVLT_STRUCT_ATTN = 4, MVLT_STRUCT_SWIN_WMSA = 5, MVLT_STRUCT_EMBED = 6, MVLT_STRUCT_ATTN_CACHED = 7,
        MVLT_STRUCT_ZERO_ITEM = 8, MVLT_STRUCT_RANGE = 9, MVLT_STRUCT_MLM_MASK = 10, MVLT_STRUCT_GREEDY_STATE = 11, MVLT_STRUCT_SWIN_DBIAS_ITEM = 12,
-       MVLT_STRUCT_SAMPLE_STATE = 13, MVLT_STRUCT_SAMPLE_FILTER = 14, MVLT_STRUCT_COUNT = 15 };
+       MVLT_STRUCT_SAMPLE_STATE = 13, MVLT_STRUCT_SAMPLE_FILTER = 14, MVLT_STRUCT_BEAM_CAND = 15, MVLT_STRUCT_ATTN_CACHED_BEAM = 16,
+       MVLT_STRUCT_COUNT = 17 };
 size_t mvlt_sizeof(int struct_id);
 
 /* ------------------------------------------------------------------ GEMM
@@ -212,6 +213,30 @@ int mvlt_gemm_sample_filtered(const MvltGemm* p, float* part_val, int32_t* part_
 /* The graph form: mvlt_gemm_sample_step (same state, same seed / tag0 + column convention) with the filtered pick. */
 int mvlt_gemm_sample_filtered_step(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltSampleFilter* filter,
                                    const MvltSampleState* g, void* stream);
+/* Last-row MLM head fused with the candidate step of beam search (model.py:700-720: log_softmax + beam score, top 2 * beams over
+ * (beam, token)).  The M = G * num_beams rows of the product are the hypotheses of G samples, rows g * num_beams .. + num_beams
+ * the beams of sample g.  Per row m, all in f32 with no fused multiply-add:
+ *   x = (A W^T + bias)[m, n]                       bit for bit the x of mvlt_gemm_sample_filtered at inv_temperature = 1
+ *   lse_m = max_n x + logf(sum_n expf(x - max))    a fixed summation shape (csrc/skinny.hip beam_candidates_kernel)
+ *   s[m, n] = (x - lse_m) + beam_scores[m]         the two roundings log_softmax followed by `+` make
+ * Per sample g: the n_cand largest s over its num_beams * N entries, sorted descending, ties broken by the LOWER flat index
+ * beam * N + n (torch.topk leaves ties unspecified) -> cand_score (f32), cand_beam, cand_tok (int32), all [G, n_cand]; lse
+ * (f32 [M], optional).  The product writes x into the caller's workspace `x` ([M, ldx] f32, ldx >= N) in row chunks of at most 64
+ * (M may exceed 64); the selection is one launch, a workgroup per sample.  The selection compares integers only and uses no
+ * float atomics: the same operands give the same lists run to run.
+ * Preconditions of the product: those of mvlt_gemm_sample_filtered (K a whole number of k-blocks, k-contiguous 16-byte aligned
+ * operands, only MVLT_EPI_BIAS; C, m_dev unused) without its M <= 64.
+ * Refusals (nothing is launched, nothing written): MVLT_ERR_ARG for a NULL p / c / operand / beam_scores / x / output,
+ * num_beams < 1, n_cand < 1, M % num_beams != 0, ldx < N, n_cand > num_beams * N, num_beams * N >= 2^31; then
+ * MVLT_ERR_UNSUPPORTED for num_beams > 8, n_cand > 16 or a product the wide head kernels refuse. */
+typedef struct MvltBeamCand {
+    int32_t num_beams, n_cand;
+    const float* beam_scores;           /* [M] */
+    float* x; int64_t ldx;              /* logits workspace [M, ldx] */
+    float* cand_score; int32_t* cand_beam; int32_t* cand_tok;       /* [M / num_beams, n_cand] */
+    float* lse;                         /* [M] or NULL */
+} MvltBeamCand;
+int mvlt_gemm_beam_candidates(const MvltGemm* p, const MvltBeamCand* c, void* stream);
 
 /* Decode step (model.py:82-108: 2 new tokens per sample): skinny product with the reduction split over workgroups:
  * acc[s][M][N] (f32, k_splits slabs) = A[:, k-slice s] B[:, k-slice s]^T, M <= 64, both operands k-contiguous, no epilogue;
@@ -572,6 +597,30 @@ typedef struct MvltAttnCached {
                                            is replayed without host involvement keeps its position on the GPU) */
 } MvltAttnCached;
 int mvlt_attn_cached(const MvltAttnCached* p, void* stream);
+/* The same step for beam search, with a cache that is NEVER reordered: the rows are the hypotheses of rows / num_beams samples
+ * (rows g * num_beams .. + num_beams the beams of sample g) and a table says in which cache row each generated position of each
+ * hypothesis lives.  Key position k of row r, g = r / num_beams:
+ *   k < prefix            cache row g * num_beams            (the image prefix is stored once per sample, in its first row)
+ *   prefix <= k < past    cache row g * num_beams + slot[r, k - prefix]
+ *   k >= past             qkv_new of row r; also appended to row r's OWN cache row at position k, as mvlt_attn_cached does
+ * Every (row, position) cell is written by one launch and only read by later ones.  Slot values are clamped into
+ * [0, num_beams) and the column into [0, ld_slot): a bad table gives wrong attention, never a read outside the sample's rows.
+ * The walk over the keys, the online softmax and the 4-wave merge for bf16 are mvlt_attn_cached's; only the row address of a key
+ * differs, so with slot[r, :] = r % num_beams and the prefix present in every row the output is bit for bit mvlt_attn_cached's.
+ * MVLT_ERR_ARG: NULL pointers, rows % num_beams != 0, prefix < 0, ld_slot < 1, and with a host `past`: past < prefix,
+ * past + n_new > cache_cap, past - prefix > ld_slot (with past_dev the caller guarantees them).  MVLT_ERR_UNSUPPORTED:
+ * hd != 64, n_new > 4, operands not 16-byte aligned (there is no serial form). */
+typedef struct MvltAttnCachedBeam {
+    int dtype, rows, nH, hd, past, n_new, cache_cap;
+    const void* qkv_new;                /* [rows*n_new, 3*nH*hd] */
+    void* k_cache; void* v_cache;       /* [rows, nH, cache_cap, hd] */
+    void* out;                          /* [rows*n_new, nH*hd] */
+    float scale;
+    const int32_t* past_dev;            /* optional, as in MvltAttnCached */
+    int num_beams, prefix;
+    const int32_t* slot; int64_t ld_slot;       /* [rows, ld_slot] */
+} MvltAttnCachedBeam;
+int mvlt_attn_cached_beam(const MvltAttnCachedBeam* p, void* stream);
 /* argmax over V of logits [rows, ld] -> int64 ids (greedy_search, model.py:896-900) */
 int mvlt_argmax(int dtype, const void* logits, int64_t ld, int rows, int V, int64_t* out, void* stream);
 

@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(_HERE, "libmvlt_hip.so")
 
 F32, BF16 = 0, 1
 OK = 0
-ABI_VERSION = 12         # == MVLT_ABI_VERSION of the include/mvlt_hip.h these mirrors were written against
+ABI_VERSION = 13         # == MVLT_ABI_VERSION of the include/mvlt_hip.h these mirrors were written against
 ERRORS = {-1: "MVLT_ERR_ARG", -2: "MVLT_ERR_LAUNCH", -3: "MVLT_ERR_UNSUPPORTED"}
 
 EPI_BIAS, EPI_GELU, EPI_SAVE_PRE, EPI_DROPOUT = 1, 2, 4, 8
@@ -145,6 +145,16 @@ class MvltSampleFilter(C.Structure):
     _fields_ = [("top_k", i32), ("top_p", f32), ("x", vp), ("ldx", i64), ("row0", u32)]
 
 
+class MvltBeamCand(C.Structure):
+    _fields_ = [("num_beams", i32), ("n_cand", i32), ("beam_scores", vp), ("x", vp), ("ldx", i64),
+                ("cand_score", vp), ("cand_beam", vp), ("cand_tok", vp), ("lse", vp)]
+
+
+class MvltAttnCachedBeam(C.Structure):
+    _fields_ = MvltAttnCached._fields_[:1] + [("rows", i32)] + MvltAttnCached._fields_[2:] + [
+        ("num_beams", i32), ("prefix", i32), ("slot", vp), ("ld_slot", i64)]
+
+
 # every symbol include/mvlt_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "mvlt_version": (i32, []),
@@ -163,6 +173,7 @@ SYMBOLS = {
     "mvlt_gemm_sample_step": (i32, [C.POINTER(MvltGemm), vp, vp, C.POINTER(MvltSampleState), vp]),
     "mvlt_gemm_sample_filtered": (i32, [C.POINTER(MvltGemm), vp, vp, C.POINTER(MvltSampleFilter), vp, vp, u64, u32, f32, vp]),
     "mvlt_gemm_sample_filtered_step": (i32, [C.POINTER(MvltGemm), vp, vp, C.POINTER(MvltSampleFilter), C.POINTER(MvltSampleState), vp]),
+    "mvlt_gemm_beam_candidates": (i32, [C.POINTER(MvltGemm), C.POINTER(MvltBeamCand), vp]),
     "mvlt_gemm_skinny_accum": (i32, [C.POINTER(MvltGemm), vp, i32, vp]),
     "mvlt_layernorm_acc_fwd": (i32, [i32, vp, i32, vp, vp, vp, vp, f32, i32, i32, vp, vp]),
     "mvlt_colsum": (i32, [i32, vp, i64, i32, i32, vp, i32, vp, vp]),
@@ -214,6 +225,7 @@ SYMBOLS = {
     "mvlt_softmax_rows": (i32, [i32, vp, i64, i32, i32, vp, vp]),
     "mvlt_adamw": (i32, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp]),
     "mvlt_attn_cached": (i32, [C.POINTER(MvltAttnCached), vp]),
+    "mvlt_attn_cached_beam": (i32, [C.POINTER(MvltAttnCachedBeam), vp]),
     "mvlt_argmax": (i32, [i32, vp, i64, i32, i32, vp, vp]),
     "mvlt_zero_batch": (i32, [C.POINTER(MvltZeroItem), i32, vp]),
     "mvlt_prefetch": (i32, [C.POINTER(MvltRange), i32, vp]),
@@ -224,7 +236,7 @@ SYMBOLS = {
 # ctypes mirror of every struct, in the order of the MVLT_STRUCT_* ids of the header
 STRUCTS = [MvltGemm, MvltLayerNorm, MvltLayerNormBwd, MvltLnReduceItem, MvltAttn, MvltSwinWmsa, MvltEmbed,
            MvltAttnCached, MvltZeroItem, MvltRange, MvltMlmMask, MvltGreedyState, MvltSwinDbiasItem,
-           MvltSampleState, MvltSampleFilter]
+           MvltSampleState, MvltSampleFilter, MvltBeamCand, MvltAttnCachedBeam]
 
 _lib = None
 

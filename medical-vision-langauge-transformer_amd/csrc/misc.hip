@@ -576,6 +576,153 @@ __global__ __launch_bounds__(64 * NW) void attn_cached_kernel(const MvltAttnCach
     }
 }
 
+// Beam search (mvlt_attn_cached_beam): the kernel above with ONE change -- the cache row a key is read from.  The cache is never
+// reordered: positions < prefix (the image) come from the first row of the row's sample, generated positions from the row
+// slot[r, k - prefix] of the sample says (the hypothesis that wrote them), the new rows from qkv_new; the append goes to the row's
+// own cache row.  Same lanes, key blocks, online softmax and merge, so an identity table reproduces attn_cached_kernel bit for bit.
+template <typename T, int NW>
+__global__ __launch_bounds__(64 * NW) void attn_cached_beam_kernel(const MvltAttnCachedBeam p) {
+    constexpr int E = TypeInfo<T>::E, HD = 64, FC = HD / E, KG = 64 / FC;
+    using Vec = typename TypeInfo<T>::Vec;
+    __shared__ float wm[NW][CACHED_MAXNEW], wl[NW][CACHED_MAXNEW], wo[NW][CACHED_MAXNEW][HD];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, fc = lane % FC, kg = lane / FC;
+    const int h = blockIdx.x % p.nH, b = blockIdx.x / p.nH;
+    const int past = p.past_dev ? *p.past_dev : p.past;
+    const int C = p.nH * HD;
+    const T* qkv = reinterpret_cast<const T*>(p.qkv_new) + (long)b * p.n_new * 3 * C + h * HD + fc * E;
+    const long row_stride = (long)p.nH * p.cache_cap * HD;          // one cache row (all heads of a hypothesis)
+    const int b0 = b - b % p.num_beams;                             // first row of this row's sample
+    T* kc = reinterpret_cast<T*>(p.k_cache) + ((long)b * p.nH + h) * p.cache_cap * HD + fc * E;          // this row's own cache row (append)
+    T* vc = reinterpret_cast<T*>(p.v_cache) + ((long)b * p.nH + h) * p.cache_cap * HD + fc * E;
+    const T* kc0 = reinterpret_cast<const T*>(p.k_cache) + ((long)b0 * p.nH + h) * p.cache_cap * HD + fc * E;   // the sample's first row
+    const T* vc0 = reinterpret_cast<const T*>(p.v_cache) + ((long)b0 * p.nH + h) * p.cache_cap * HD + fc * E;
+    const int32_t* slot = p.slot + (long)b * p.ld_slot;
+    const int nk = past + p.n_new;
+    float q[CACHED_MAXNEW][E], o[CACHED_MAXNEW][E], m[CACHED_MAXNEW], l[CACHED_MAXNEW];
+#pragma unroll
+    for (int r = 0; r < CACHED_MAXNEW; ++r) {
+        m[r] = -3.0e38f; l[r] = 0.f;
+#pragma unroll
+        for (int e = 0; e < E; ++e) { q[r][e] = 0.f; o[r][e] = 0.f; }
+        if (r < p.n_new) {
+            const Vec qv = *reinterpret_cast<const Vec*>(qkv + (long)r * 3 * C);
+#pragma unroll
+            for (int e = 0; e < E; ++e) q[r][e] = to_f(qv[e]) * p.scale;
+            if (kg == 0 && wave == 0) {       // append this row's K/V chunk (the loop below reads new rows from qkv_new, not the cache)
+                *reinterpret_cast<Vec*>(kc + (long)(past + r) * HD) = *reinterpret_cast<const Vec*>(qkv + (long)r * 3 * C + C);
+                *reinterpret_cast<Vec*>(vc + (long)(past + r) * HD) = *reinterpret_cast<const Vec*>(qkv + (long)r * 3 * C + 2 * C);
+            }
+        }
+    }
+    for (int k0 = wave * KG * CACHED_U; k0 < nk; k0 += NW * KG * CACHED_U) {
+        Vec kv[CACHED_U], vv[CACHED_U];
+#pragma unroll
+        for (int u = 0; u < CACHED_U; ++u) {
+            const int k = k0 + u * KG + kg;
+            const int kk = k < nk ? k : 0;                                   // out of range: a valid row, masked below
+            // the one difference from attn_cached_kernel: a generated key lives in the cache row its ancestor wrote (clamped table)
+            long off = (long)kk * HD;
+            if (kk >= p.prefix && kk < past) off += row_stride * min(max(slot[min(kk - p.prefix, (int)p.ld_slot - 1)], 0), p.num_beams - 1);
+            const T* ks = kk < past ? kc0 + off : qkv + (long)(kk - past) * 3 * C + C;
+            const T* vs = kk < past ? vc0 + off : qkv + (long)(kk - past) * 3 * C + 2 * C;
+            kv[u] = *reinterpret_cast<const Vec*>(ks);
+            vv[u] = *reinterpret_cast<const Vec*>(vs);
+        }
+        float s[CACHED_U][CACHED_MAXNEW];
+#pragma unroll
+        for (int u = 0; u < CACHED_U; ++u) {
+            const int k = k0 + u * KG + kg;
+#pragma unroll
+            for (int r = 0; r < CACHED_MAXNEW; ++r) {
+                float part = 0.f;
+#pragma unroll
+                for (int e = 0; e < E; ++e) part += q[r][e] * to_f(kv[u][e]);
+#pragma unroll
+                for (int off = 1; off < FC; off <<= 1) part += __shfl_xor(part, off, 64);
+                // causal over the new tokens (model.py:97-104): key k is visible to new row r iff k <= past + r
+                s[u][r] = (k < nk && k <= past + r) ? part : -3.0e38f;
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < CACHED_MAXNEW; ++r) {
+            if (r >= p.n_new) break;
+            float mb = s[0][r];
+#pragma unroll
+            for (int u = 1; u < CACHED_U; ++u) mb = fmaxf(mb, s[u][r]);
+#pragma unroll
+            for (int off = FC; off < 64; off <<= 1) mb = fmaxf(mb, __shfl_xor(mb, off, 64));
+            const float mn = fmaxf(m[r], mb);
+            const float alpha = __expf(m[r] - mn);
+            m[r] = mn;
+            float ls = 0.f;
+#pragma unroll
+            for (int e = 0; e < E; ++e) o[r][e] *= alpha;
+#pragma unroll
+            for (int u = 0; u < CACHED_U; ++u) {
+                const float pr = __expf(s[u][r] - mn);                     // masked: exp(-3e38 - mn) = 0
+                ls += pr;
+#pragma unroll
+                for (int e = 0; e < E; ++e) o[r][e] += pr * to_f(vv[u][e]);
+            }
+            l[r] = l[r] * alpha + ls;
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < CACHED_MAXNEW; ++r) {
+        if (r >= p.n_new) break;
+        float lt = l[r];
+#pragma unroll
+        for (int off = FC; off < 64; off <<= 1) lt += __shfl_xor(lt, off, 64);
+        float ov[E];
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            float v = o[r][e];
+#pragma unroll
+            for (int off = FC; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
+            ov[e] = v;
+        }
+        if (NW == 1) {
+            const float inv = 1.0f / lt;
+            Vec ovv;
+#pragma unroll
+            for (int e = 0; e < E; ++e) ovv[e] = from_f<T>(ov[e] * inv);
+            if (kg == 0)
+                *reinterpret_cast<Vec*>(reinterpret_cast<T*>(p.out) + ((long)b * p.n_new + r) * C + h * HD + fc * E) = ovv;
+        } else if (kg == 0) {
+            if (fc == 0) { wm[wave][r] = m[r]; wl[wave][r] = lt; }
+#pragma unroll
+            for (int e = 0; e < E; ++e) wo[wave][r][fc * E + e] = ov[e];
+        }
+    }
+    if (NW > 1) {
+        __syncthreads();
+        if (wave == 0 && kg == 0) {
+#pragma unroll
+            for (int r = 0; r < CACHED_MAXNEW; ++r) {
+                if (r >= p.n_new) break;
+                float mx = wm[0][r];
+#pragma unroll
+                for (int w = 1; w < NW; ++w) mx = fmaxf(mx, wm[w][r]);
+                float lt = 0.f, acc[E];
+#pragma unroll
+                for (int e = 0; e < E; ++e) acc[e] = 0.f;
+#pragma unroll
+                for (int w = 0; w < NW; ++w) {
+                    const float a = __expf(wm[w][r] - mx);            // a wave that saw no key: exp(-3e38 - mx) = 0
+                    lt += wl[w][r] * a;
+#pragma unroll
+                    for (int e = 0; e < E; ++e) acc[e] += wo[w][r][fc * E + e] * a;
+                }
+                const float inv = 1.0f / lt;
+                Vec ovv;
+#pragma unroll
+                for (int e = 0; e < E; ++e) ovv[e] = from_f<T>(acc[e] * inv);
+                *reinterpret_cast<Vec*>(reinterpret_cast<T*>(p.out) + ((long)b * p.n_new + r) * C + h * HD + fc * E) = ovv;
+            }
+        }
+    }
+}
+
 // fallback (head_dim < 64 or more than 4 new rows): one wave per (b, head, new row), keys serial
 template <typename T>
 __global__ __launch_bounds__(64) void attn_cached_serial_kernel(const MvltAttnCached p) {
@@ -724,6 +871,8 @@ extern "C" size_t mvlt_sizeof(int struct_id) {
         case MVLT_STRUCT_SWIN_DBIAS_ITEM: return sizeof(MvltSwinDbiasItem);
         case MVLT_STRUCT_SAMPLE_STATE: return sizeof(MvltSampleState);
         case MVLT_STRUCT_SAMPLE_FILTER: return sizeof(MvltSampleFilter);
+        case MVLT_STRUCT_BEAM_CAND: return sizeof(MvltBeamCand);
+        case MVLT_STRUCT_ATTN_CACHED_BEAM: return sizeof(MvltAttnCachedBeam);
         default: return 0;
     }
 }
@@ -977,6 +1126,24 @@ extern "C" int mvlt_attn_cached(const MvltAttnCached* p, void* stream) {
         BY_DTYPE(p->dtype, hipLaunchKernelGGL(attn_cached_serial_kernel<float>, grid, dim3(64), 0, STREAM(stream), *p),
                  hipLaunchKernelGGL(attn_cached_serial_kernel<bf16_t>, grid, dim3(64), 0, STREAM(stream), *p));
     }
+    MVLT_LAUNCH_CHECK();
+    return MVLT_OK;
+}
+extern "C" int mvlt_attn_cached_beam(const MvltAttnCachedBeam* p, void* stream) {
+    MVLT_CHECK(p && p->qkv_new && p->k_cache && p->v_cache && p->out && p->slot, MVLT_ERR_ARG);
+    MVLT_CHECK(p->hd > 0 && p->rows > 0 && p->nH > 0 && p->n_new > 0 && p->num_beams > 0 && p->rows % p->num_beams == 0, MVLT_ERR_ARG);
+    MVLT_CHECK(p->prefix >= 0 && p->ld_slot >= 1 && p->ld_slot < (1L << 31), MVLT_ERR_ARG);
+    // with a device-side `past` the host cannot check the bounds: the caller guarantees them
+    MVLT_CHECK(p->past_dev || (p->past >= p->prefix && p->past + p->n_new <= p->cache_cap && p->past - p->prefix <= p->ld_slot), MVLT_ERR_ARG);
+    MVLT_CHECK(p->hd == 64 && p->n_new <= CACHED_MAXNEW && aligned16(p->qkv_new) && aligned16(p->k_cache) && aligned16(p->v_cache) &&
+               aligned16(p->out), MVLT_ERR_UNSUPPORTED);
+    MVLT_CHECK(p->dtype == MVLT_F32 || p->dtype == MVLT_BF16, MVLT_ERR_UNSUPPORTED);
+    dim3 grid(p->rows * p->nH);
+    if (p->cache_cap > 64 && p->dtype == MVLT_BF16)          // the same choice of waves as mvlt_attn_cached (bit-equality needs it)
+        hipLaunchKernelGGL((attn_cached_beam_kernel<bf16_t, 4>), grid, dim3(256), 0, STREAM(stream), *p);
+    else
+        BY_DTYPE(p->dtype, hipLaunchKernelGGL((attn_cached_beam_kernel<float, 1>), grid, dim3(64), 0, STREAM(stream), *p),
+                 hipLaunchKernelGGL((attn_cached_beam_kernel<bf16_t, 1>), grid, dim3(64), 0, STREAM(stream), *p));
     MVLT_LAUNCH_CHECK();
     return MVLT_OK;
 }

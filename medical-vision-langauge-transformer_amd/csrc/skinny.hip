@@ -1,7 +1,8 @@
 // Everything the decode path runs at M <= 64 (see include/mvlt_hip.h): the skinny product behind mvlt_gemm, its K-split form
 // (mvlt_gemm_skinny_accum), and the MLM head fused with the pick of the next token -- greedy (mvlt_gemm_argmax,
 // mvlt_gemm_argmax_greedy), sampled (mvlt_gemm_sample, mvlt_gemm_sample_step) and sampled behind a top-k / top-p filter
-// (mvlt_gemm_sample_filtered, mvlt_gemm_sample_filtered_step).  No LDS staging in the products: the weight matrix is
+// (mvlt_gemm_sample_filtered, mvlt_gemm_sample_filtered_step) -- and the candidate step of beam search
+// (mvlt_gemm_beam_candidates: log-softmax + beam score + top-n per sample).  No LDS staging in the products: the weight matrix is
 // read once and nothing is reused inside a workgroup, so every wave loads its MFMA fragments straight from global memory.
 // Same argument block as the tile kernels of gemm.hip (gemm_dev.h); gemm.hip reaches the plain product through mvlt_skinny_try.
 #include "common.h"
@@ -682,6 +683,173 @@ __global__ __launch_bounds__(FILT_THREADS) void sample_filter_pick_kernel(const 
     }
 }
 
+// BEAM candidates (mvlt_gemm_beam_candidates): the step of beam search between the head and the host scorer.  The product is
+// gemm_logits128_kernel at inv_t = 1 (a multiplication by 1 is exact: x is the value the sampled kernels form), issued in row
+// chunks of 64 into one workspace; then ONE workgroup of 1024 threads per sample g (thread t owns the columns t, t + 1024, ... of
+// every beam row: a fixed map) reads its num_beams rows three times:
+//   1  per thread and beam the largest x of its own columns, then the row maxima (wave tree, 16 wave values in LDS)
+//   2  per row sum expf(x - max) by the fixed tree of sample_filter_pick_kernel (four accumulators over the thread's columns in
+//      ascending order, (a0 + a1) + (a2 + a3), the wave's xor tree, the 16 wave sums in wave order) -> lse = max + logf(sum)
+//   3  s = (x - lse) + beam_score; every entry with key(s) >= tau goes into an LDS list as key << 32 | ~flat (flat = beam N + n):
+//      a larger word is a larger score or, at equal score, a lower flat index
+// tau is a lower bound of the n_cand-th largest key: rounding is monotone, so the largest s among a thread's entries of a row is
+// s(its largest x) -- known after pass 1 without a read -- and the n_cand-th largest of the 1024 thread maxima (exact rank by
+// counting in LDS) has at least n_cand entries at or above it.  The list holds the n_cand winners and a few more (every entry a
+// thread owns above tau); its rank order (count of larger words: words are distinct) gives the sorted output.  The order in which
+// the list is filled is the only thing that varies run to run and the ranks do not depend on it.
+// More than BEAM_LIST entries at or above tau (thousands of tied scores): n_cand rounds of "the largest word below the previous
+// winner" over the rows instead -- slow, exact, the same answer.
+// A workgroup per sample leaves most of the chip idle at small G (measured: profiles/beam_fused.md); splitting a sample over
+// several workgroups needs a second launch for the merge and was not built.
+constexpr int BEAM_THREADS = 1024, BEAM_MAXB = 8, BEAM_MAXC = 16, BEAM_LIST = 1024;
+struct BeamIn {
+    const float* x; long ldx; const float* beam_scores; int num_beams, n_cand, N;
+    float* cand_score; int32_t* cand_beam; int32_t* cand_tok; float* lse;
+};
+MVLT_DEV unsigned long long beam_word(float x, float lse, float bs, uint32_t flat) {
+    return ((unsigned long long)filt_key(__fadd_rn(__fadd_rn(x, -lse), bs)) << 32) | (unsigned long long)(0xFFFFFFFFu - flat);
+}
+MVLT_DEV void beam_emit(const BeamIn& f, const long o, const unsigned long long w) {
+    const uint32_t key = (uint32_t)(w >> 32), flat = 0xFFFFFFFFu - (uint32_t)w;
+    f.cand_score[o] = __uint_as_float(key ^ ((key >> 31) ? 0x80000000u : 0xFFFFFFFFu));
+    f.cand_beam[o] = (int32_t)(flat / (uint32_t)f.N);
+    f.cand_tok[o] = (int32_t)(flat % (uint32_t)f.N);
+}
+__global__ __launch_bounds__(BEAM_THREADS) void beam_candidates_kernel(const BeamIn f) {
+    __shared__ float s_f[BEAM_MAXB][16];
+    __shared__ float s_lse[BEAM_MAXB], s_bs[BEAM_MAXB];
+    __shared__ uint32_t s_tmax[BEAM_THREADS];
+    __shared__ unsigned long long s_list[BEAM_LIST], s_w[16];
+    __shared__ uint32_t s_tau;
+    __shared__ int s_count;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = blockIdx.x, nb = f.num_beams, N = f.N;
+    const float* x0 = f.x + (long)g * nb * f.ldx;
+    // ---- 1: thread and row maxima
+    float tmax[BEAM_MAXB], rmax[BEAM_MAXB];
+#pragma unroll
+    for (int b = 0; b < BEAM_MAXB; ++b) {
+        tmax[b] = -3.0e38f;
+        if (b < nb) {
+            const float* x = x0 + (long)b * f.ldx;
+            for (int n = tid; n < N; n += BEAM_THREADS) tmax[b] = fmaxf(tmax[b], x[n]);
+            const float wm = wave_max(tmax[b]);
+            if (lane == 0) s_f[b][wave] = wm;
+        }
+    }
+    if (tid == 0) s_count = 0;
+    __syncthreads();
+#pragma unroll
+    for (int b = 0; b < BEAM_MAXB; ++b) {
+        rmax[b] = -3.0e38f;
+        if (b < nb) {
+            rmax[b] = s_f[b][0];
+#pragma unroll
+            for (int w = 1; w < 16; ++w) rmax[b] = fmaxf(rmax[b], s_f[b][w]);
+        }
+    }
+    __syncthreads();          // (s_f is written again by the sums)
+    // ---- 2: sum expf(x - max) per row, fixed shape
+#pragma unroll
+    for (int b = 0; b < BEAM_MAXB; ++b) {
+        if (b < nb) {
+            const float* x = x0 + (long)b * f.ldx;
+            float se[4] = {0.f, 0.f, 0.f, 0.f};
+            int j = 0;
+            for (int n = tid; n < N; n += BEAM_THREADS, ++j) se[j & 3] += __expf(__fadd_rn(x[n], -rmax[b]));
+            float sum = (se[0] + se[1]) + (se[2] + se[3]);
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+            if (lane == 0) s_f[b][wave] = sum;
+        }
+    }
+    __syncthreads();
+    if (tid < nb) {
+        float sum = s_f[tid][0];
+        for (int w = 1; w < 16; ++w) sum += s_f[tid][w];
+        float mx = 0.f;          // (rmax[] lives in registers, indexed by a compile-time b)
+#pragma unroll
+        for (int b = 0; b < BEAM_MAXB; ++b) if (b == tid) mx = rmax[b];
+        const float lse = __fadd_rn(mx, logf(sum));
+        s_lse[tid] = lse;
+        s_bs[tid] = f.beam_scores[(long)g * nb + tid];
+        if (f.lse) f.lse[(long)g * nb + tid] = lse;
+    }
+    __syncthreads();
+    // ---- tau: the n_cand-th largest of the thread maxima (threads without a column hold 0, below every key)
+    uint32_t mine = 0u;
+    if (tid < N) {
+#pragma unroll
+        for (int b = 0; b < BEAM_MAXB; ++b)
+            if (b < nb) mine = max(mine, filt_key(__fadd_rn(__fadd_rn(tmax[b], -s_lse[b]), s_bs[b])));
+    }
+    s_tmax[tid] = mine;
+    __syncthreads();
+    {
+        int above = 0;
+        for (int j = 0; j < BEAM_THREADS; ++j) {
+            const uint32_t o = s_tmax[j];
+            above += (o > mine || (o == mine && j < tid)) ? 1 : 0;
+        }
+        if (above == f.n_cand - 1) s_tau = mine;
+    }
+    __syncthreads();
+    const uint32_t tau = s_tau;
+    // ---- 3: the list of entries at or above tau
+#pragma unroll
+    for (int b = 0; b < BEAM_MAXB; ++b) {
+        if (b < nb) {
+            const float* x = x0 + (long)b * f.ldx;
+            const float lse = s_lse[b], bs = s_bs[b];
+            for (int n = tid; n < N; n += BEAM_THREADS) {
+                const unsigned long long w = beam_word(x[n], lse, bs, (uint32_t)b * (uint32_t)N + (uint32_t)n);
+                if ((uint32_t)(w >> 32) >= tau) {
+                    const int pos = atomicAdd(&s_count, 1);
+                    if (pos < BEAM_LIST) s_list[pos] = w;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    const int count = s_count;
+    const long out0 = (long)g * f.n_cand;
+    if (count <= BEAM_LIST) {          // (count >= n_cand: tau is a lower bound of the n_cand-th largest key)
+        if (tid < count) {
+            const unsigned long long w = s_list[tid];
+            int rank = 0;
+            for (int j = 0; j < count; ++j) rank += s_list[j] > w ? 1 : 0;
+            if (rank < f.n_cand) beam_emit(f, out0 + rank, w);
+        }
+        return;
+    }
+    unsigned long long prev = ~0ull;
+    for (int c = 0; c < f.n_cand; ++c) {
+        unsigned long long best = 0ull;
+#pragma unroll
+        for (int b = 0; b < BEAM_MAXB; ++b) {
+            if (b < nb) {
+                const float* x = x0 + (long)b * f.ldx;
+                const float lse = s_lse[b], bs = s_bs[b];
+                for (int n = tid; n < N; n += BEAM_THREADS) {
+                    const unsigned long long w = beam_word(x[n], lse, bs, (uint32_t)b * (uint32_t)N + (uint32_t)n);
+                    if (w < prev && w > best) best = w;
+                }
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long ow = __shfl_xor(best, o, 64);
+            if (ow > best) best = ow;
+        }
+        if (lane == 0) s_w[wave] = best;
+        __syncthreads();
+        best = s_w[0];
+        for (int w = 1; w < 16; ++w) if (s_w[w] > best) best = s_w[w];
+        if (tid == 0) beam_emit(f, out0 + c, best);
+        prev = best;
+        __syncthreads();          // (s_w is written again by the next round)
+    }
+}
+
 // --------------------------------------------------------------------------------------------------------------- host
 // run f(T{}) for the product's element type
 template <typename F> int by_dtype(const int dtype, F&& f) {
@@ -875,6 +1043,40 @@ extern "C" int mvlt_gemm_sample_filtered_step(const MvltGemm* p, float* part_val
     { const int rc = greedy_state(g, st); if (rc != MVLT_OK) return rc; }
     const SampleIn si{g->seed, 0, g->col, g->tag0, g->inv_temperature};
     return filtered_launch<true>(p, filter, si, st, nullptr, nullptr, reinterpret_cast<hipStream_t>(stream));
+}
+
+// The beam candidates: the product in row chunks of <= 64 into the one workspace, then the selection.  Every chunk is checked
+// before the first launch: a refused call launches nothing.
+extern "C" int mvlt_gemm_beam_candidates(const MvltGemm* p, const MvltBeamCand* c, void* stream) {
+    MVLT_CHECK(p && c && p->A && p->B && c->beam_scores && c->x && c->cand_score && c->cand_beam && c->cand_tok, MVLT_ERR_ARG);
+    MVLT_CHECK(p->M > 0 && p->N > 0 && p->K > 0 && p->lda > 0 && p->ldb > 0, MVLT_ERR_ARG);
+    MVLT_CHECK(c->num_beams >= 1 && c->n_cand >= 1 && p->M % c->num_beams == 0 && c->ldx >= p->N, MVLT_ERR_ARG);
+    MVLT_CHECK((long)c->num_beams * p->N < (1L << 31) && (long)c->n_cand <= (long)c->num_beams * p->N, MVLT_ERR_ARG);
+    if (p->epilogue & MVLT_EPI_BIAS) MVLT_CHECK(p->bias, MVLT_ERR_ARG);
+    MVLT_CHECK(c->num_beams <= BEAM_MAXB && c->n_cand <= BEAM_MAXC, MVLT_ERR_UNSUPPORTED);
+    MVLT_CHECK(!p->a_kmajor && !p->b_kmajor && (p->epilogue & ~(MVLT_EPI_BIAS)) == 0, MVLT_ERR_UNSUPPORTED);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int vec = (c->ldx % 4 == 0 && aligned16(c->x)) ? 1 : 0;
+    const int rc = by_dtype(p->dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        for (int pass = 0; pass < 2; ++pass) {          // 0: check every chunk, 1: launch
+            for (int r0 = 0; r0 < p->M; r0 += 64) {
+                MvltGemm q = *p;
+                q.M = p->M - r0 < 64 ? p->M - r0 : 64;
+                q.A = reinterpret_cast<const T*>(p->A) + (long)r0 * p->lda;
+                q.m_dev = nullptr;
+                if (pass == 0) { MVLT_CHECK(skinny_ok<T>(&q), MVLT_ERR_UNSUPPORTED); continue; }
+                LAUNCH_NRT(gemm_logits128_kernel, T, q.M, dim3(ceil_div(parts_of(&q), SKINNY_WAVES)), dim3(64 * SKINNY_WAVES), s, skinny_dev(&q),
+                           c->x + (long)r0 * c->ldx, (long)c->ldx, vec, 1.0f);
+            }
+        }
+        return (int)MVLT_OK;
+    });
+    if (rc != MVLT_OK) return rc;
+    const BeamIn bi{c->x, (long)c->ldx, c->beam_scores, c->num_beams, c->n_cand, p->N, c->cand_score, c->cand_beam, c->cand_tok, c->lse};
+    hipLaunchKernelGGL(beam_candidates_kernel, dim3(p->M / c->num_beams), dim3(BEAM_THREADS), 0, s, bi);
+    MVLT_LAUNCH_CHECK();
+    return MVLT_OK;
 }
 
 extern "C" int mvlt_gemm_skinny_accum(const MvltGemm* p, float* acc, int k_splits, void* stream) {

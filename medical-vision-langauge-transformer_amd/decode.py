@@ -17,8 +17,13 @@ its head: the token of output column c is ``argmax_n (logit_n / T + G_n)`` with 
 through a workspace, a workgroup per row selects the threshold (top-k with ties kept, then the nucleus over what is left) and
 draws among the kept tokens with the same noise; the score is the log-probability under the renormalised distribution.  The
 eager loop calls the stand-alone entry point, for B > 64 in row chunks of 64 whose noise is indexed by the row of the batch.
-Beam search (``beam_search``): same cached steps over B*beams rows, cache rows gathered by beam
-index, scorer bookkeeping restated from HF transformers 4.16 (parity with the reference unpinned).
+Beam search (``beam_search``): same cached steps over B*beams rows, scorer bookkeeping on the host restated from HF
+transformers 4.16 (parity with the reference unpinned).  Default route (beams <= 8, head_dim 64): the candidates of a token come
+from ``mvlt_gemm_beam_candidates`` (head + log-softmax + beam score + top 2*beams per sample, f32 logits through a workspace) and
+the cache is never reordered -- ``mvlt_attn_cached_beam`` follows an int32 table [rows, max_length] that names, per hypothesis and
+generated position, the cache row (within the sample) that holds it; the image prefix is stored once per sample.
+``MVLT_BEAM_FUSED=0`` (and any other shape) takes the route of the reference: bf16 logits, ``log_softmax``, ``topk`` and a
+gather of every layer's cache by beam index per token.
 """
 from __future__ import annotations
 
@@ -42,8 +47,9 @@ _SPLITS = (2, 4)      # reduction splits of (attention output, FFN-out) projecti
 SAMPLE_TAG0 = 0x53000000
 
 
-def _layers_cached(mv, ar, x, kc, vc, past, n_new, out_last=None):
-    """x: [B*n_new, H] embeddings of the new tokens -> last hidden [B*n_new, H] (written into ``out_last`` when given)."""
+def _layers_cached(mv, ar, x, kc, vc, past, n_new, out_last=None, beam=None):
+    """x: [B*n_new, H] embeddings of the new tokens -> last hidden [B*n_new, H] (written into ``out_last`` when given).
+    ``beam`` = (num_beams, prefix, slot table): the attention follows beam ancestry through the table (ops.attn_cached_beam)."""
     cfg = mv.config
     H = cfg.hidden_size
     nH = cfg.num_attention_heads
@@ -63,7 +69,10 @@ def _layers_cached(mv, ar, x, kc, vc, past, n_new, out_last=None):
         last_out = out_last if i == nl - 1 else None
         sa, so = layer.attention.self, layer.attention.output
         qkv = ops.gemm(x, ar.compute(sa.query.weight, 3 * H), bias=ar.master_span(sa.query.bias, 3 * H))
-        ctx = ops.attn_cached(qkv, kc[i], vc[i], past, (H // nH) ** -0.5)
+        if beam is None:
+            ctx = ops.attn_cached(qkv, kc[i], vc[i], past, (H // nH) ** -0.5)
+        else:
+            ctx = ops.attn_cached_beam(qkv, kc[i], vc[i], past, (H // nH) ** -0.5, beam[0], beam[1], beam[2])
         if split:
             ops.gemm_skinny_accum(ctx, ar.compute(so.dense.weight), acc[:_SPLITS[0]], _SPLITS[0])
             x1 = ops.layernorm_acc_fwd(acc[:_SPLITS[0]], so.dense.bias.data, x, so.LayerNorm.weight.data, so.LayerNorm.bias.data,
@@ -518,11 +527,58 @@ def beam_search(model, image_feature, num_beams, learning_strategy='unilm', max_
         logits, _ = head._logits(ar, t2)
         return torch.log_softmax(logits[:, :V].float(), dim=-1)
 
-    # ---- step 0 on the B images; caches replicated to the beams afterwards
     mask_col = torch.full((B, 1), mask_id, dtype=torch.int64, device=dev)
-    hidden, _, saved = mv._forward(feat, mask_col, mask_col, None, True, True)
+    mask2 = torch.full((B * nb, 1), mask_id, dtype=torch.int64, device=dev)
     L0 = n_img + 3
     past = L0 - 1
+    input_ids = [[mask_id] for _ in range(B * nb)]        # what the reference hands the scorer at step 0 (:701-702)
+    cur_len = 0
+    # the fused route needs what its two entry points need; everything else decodes the way the reference does
+    fused = os.environ.get("MVLT_BEAM_FUSED", "1") != "0" and 1 <= nb <= ops.BEAM_MAX_BEAMS and 2 * nb <= ops.BEAM_MAX_CAND and hd == 64
+    if fused:
+        W, bias = ar.compute(head.predictions.decoder.weight), head.predictions.decoder.bias.data
+
+        def candidates(hlast, scores, beams):
+            """-> (scores, tokens, beams) of the 2 * nb candidates per sample as host lists: one read-back."""
+            _, _, t2, _, _ = head._transform(ar, hlast.contiguous(), False)
+            out, _ = ops.gemm_beam_candidates(t2, W, bias, scores, beams, 2 * nb)
+            host = out.cpu()
+            return host[0].view(torch.float32).tolist(), host[2].tolist(), host[1].tolist()
+
+        # ---- step 0 on the B images: only beam 0 of a sample carries score 0 (:681-682), so its candidates are those of ONE row
+        hidden, _, saved = mv._forward(feat, mask_col, mask_col, None, True, True)
+        kc = [torch.zeros((B * nb, nH, cap, hd), dtype=cd, device=dev) for _ in range(nl)]
+        vc = [torch.zeros((B * nb, nH, cap, hd), dtype=cd, device=dev) for _ in range(nl)]
+        for i in range(nl):                                  # the prefix lives in the first row of every sample, once
+            _fill_cache_from_qkv(saved["layers"][i][1], B, L0, nH, hd, kc[i][::nb], vc[i][::nb], past)
+        del saved
+        prefix = past
+        own = (torch.arange(B * nb, device=dev) % nb).to(torch.int32)
+        slot = torch.zeros((B * nb, max_length), dtype=torch.int32, device=dev)      # [row, generated position] -> cache row in the sample
+        top_s, top_t, top_i = candidates(hidden[:, -1], torch.zeros(B, dtype=torch.float32, device=dev), 1)
+        while cur_len < max_length:
+            s_l, t_l, i_l = scorer.process(input_ids, top_s, top_t, top_i, pad, eos)
+            beam_scores = torch.tensor(s_l, dtype=torch.float32, device=dev)
+            beam_tok = torch.tensor(t_l, dtype=torch.int64, device=dev)
+            beam_idx = torch.tensor(i_l, dtype=torch.int64, device=dev)
+            input_ids = [[t] for t in t_l] if cur_len == 0 else [input_ids[i] + [t] for i, t in zip(i_l, t_l)]
+            cur_len += 1
+            if scorer.is_done or cur_len >= max_length:
+                break
+            # the beam reorder (model.py:758-763) moves table rows, not cache rows.  A finished sample gets beam_idx 0 (a row of
+            # sample 0): only the slot VALUES travel, and the kernel clamps them into the sample
+            slot = slot.index_select(0, beam_idx)
+            new_ids = torch.cat([beam_tok[:, None], mask2], dim=1)
+            x = _embed_new(mv, new_ids, past, cd).view(B * nb * 2, H)
+            h = _layers_cached(mv, ar, x, kc, vc, past, 2, beam=(nb, prefix, slot)).view(B * nb, 2, H)
+            slot[:, past - prefix] = own                     # position `past` of every hypothesis now lives in its own row
+            past += 1
+            top_s, top_t, top_i = candidates(h[:, -1], beam_scores, nb)
+        seqs = scorer.finalize(input_ids, beam_scores.tolist(), cfg.max_length, pad, eos)
+        return torch.tensor(seqs, dtype=torch.int64, device=dev)
+
+    # ---- step 0 on the B images; caches replicated to the beams afterwards
+    hidden, _, saved = mv._forward(feat, mask_col, mask_col, None, True, True)
     rep = torch.arange(B, device=dev).repeat_interleave(nb)
     kc, vc = [], []
     for i in range(nl):
@@ -535,9 +591,6 @@ def beam_search(model, image_feature, num_beams, learning_strategy='unilm', max_
     beam_scores = torch.zeros((B, nb), dtype=torch.float32, device=dev)
     beam_scores[:, 1:] = -1e9
     beam_scores = beam_scores.view(-1)
-    input_ids = [[mask_id] for _ in range(B * nb)]        # what the reference hands the scorer at step 0 (:701-702)
-    mask2 = torch.full((B * nb, 1), mask_id, dtype=torch.int64, device=dev)
-    cur_len = 0
     while cur_len < max_length:
         scores = (logp + beam_scores[:, None]).view(B, nb * V)
         top_s, top_t = torch.topk(scores, 2 * nb, dim=1, largest=True, sorted=True)

@@ -447,6 +447,29 @@ def gemm_sample_filtered_step(A, W, bias, state, top_k=0, top_p=1.0):
             "mvlt_gemm_sample_filtered_step")
 
 
+BEAM_MAX_BEAMS, BEAM_MAX_CAND = 8, 16          # limits of mvlt_gemm_beam_candidates (csrc/skinny.hip BEAM_MAXB / BEAM_MAXC)
+
+
+def gemm_beam_candidates(A, W, bias, beam_scores, num_beams, n_cand, want_lse=False):
+    """The candidate step of beam search without the logits round trip (mvlt_gemm_beam_candidates): A: [G * num_beams, K] (the
+    beams of sample g are the rows g * num_beams .. + num_beams; any number of rows), W: [N, K], beam_scores f32 [G * num_beams].
+    Per sample the n_cand largest log_softmax(A @ W^T + bias) + beam score over (beam, token), sorted descending, ties by the
+    lower beam * N + token.  Returns ``(out, lse)``: ``out`` one int32 tensor [3, G, n_cand] -- out[0] viewed as f32 holds the
+    scores, out[1] the beams, out[2] the tokens (one buffer: one read-back) -- and lse f32 [rows] or None."""
+    p, M, N = _head_gemm(A, W, bias)
+    assert beam_scores.dtype == torch.float32 and beam_scores.is_contiguous() and beam_scores.numel() == M
+    ldx = (N + 3) // 4 * 4
+    ws = workspace("beam_logits", M * ldx * 4, A.device)
+    G = M // max(int(num_beams), 1)
+    out = torch.empty((3, G, n_cand), dtype=torch.int32, device=A.device)
+    lse = torch.empty(M, dtype=torch.float32, device=A.device) if want_lse else None
+    c = L.MvltBeamCand()
+    c.num_beams, c.n_cand, c.beam_scores, c.x, c.ldx = int(num_beams), int(n_cand), _p(beam_scores), _p(ws), ldx
+    c.cand_score, c.cand_beam, c.cand_tok, c.lse = _p(out[0]), _p(out[1]), _p(out[2]), (_p(lse) if want_lse else None)
+    L.check(L.lib().mvlt_gemm_beam_candidates(C.byref(p), C.byref(c), _stream()), "mvlt_gemm_beam_candidates")
+    return out, lse
+
+
 def gumbel_noise(seed, tag, rows, N, device):
     """The noise of gemm_sample as the kernel computes it, f32 [rows, N] (tests)."""
     out = torch.empty((rows, N), dtype=torch.float32, device=device)
@@ -1301,6 +1324,28 @@ def attn_cached(qkv_new, k_cache, v_cache, past, scale, out=None):
         p.past = past
     p.qkv_new, p.k_cache, p.v_cache, p.out, p.scale = _p(qkv_new), _p(k_cache), _p(v_cache), _p(out), float(scale)
     L.check(L.lib().mvlt_attn_cached(C.byref(p), _stream()), "mvlt_attn_cached")
+    return out
+
+
+def attn_cached_beam(qkv_new, k_cache, v_cache, past, scale, num_beams, prefix, slot, out=None):
+    """attn_cached over the hypotheses of a beam search whose cache is never reordered (mvlt_attn_cached_beam): key positions
+    < prefix come from the first cache row of the row's sample, generated positions from the row ``slot[r, k - prefix]`` (int32
+    [rows, ld]) names within the sample, the new rows are appended to the row's own cache row.  hd = 64, n_new <= 4."""
+    rows, nH, cap, hd = k_cache.shape
+    n_new = qkv_new.shape[0] // rows
+    assert slot.dtype == torch.int32 and slot.is_cuda and slot.dim() == 2 and slot.shape[0] == rows and slot.stride(1) == 1
+    if out is None:
+        out = torch.empty((rows * n_new, nH * hd), dtype=qkv_new.dtype, device=qkv_new.device)
+    p = L.MvltAttnCachedBeam()
+    p.dtype, p.rows, p.nH, p.hd, p.n_new, p.cache_cap = _dt(qkv_new), rows, nH, hd, n_new, cap
+    if torch.is_tensor(past):
+        assert past.dtype == torch.int32 and past.is_cuda
+        p.past_dev = _p(past)
+    else:
+        p.past = past
+    p.qkv_new, p.k_cache, p.v_cache, p.out, p.scale = _p(qkv_new), _p(k_cache), _p(v_cache), _p(out), float(scale)
+    p.num_beams, p.prefix, p.slot, p.ld_slot = int(num_beams), int(prefix), _p(slot), slot.stride(0)
+    L.check(L.lib().mvlt_attn_cached_beam(C.byref(p), _stream()), "mvlt_attn_cached_beam")
     return out
 
 

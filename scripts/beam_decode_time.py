@@ -1,0 +1,117 @@
+"""Beam search at the report-generation shape (Swin-S + BERT-base, bf16, beams = 5, max_length = 150, eos_token_id = None so every
+run has the same length), B = 8 and 32: the fused route (mvlt_gemm_beam_candidates + mvlt_attn_cached_beam, the default) next to
+MVLT_BEAM_FUSED=0 (log_softmax + topk + a gather of every layer's cache per token: what beam_search did before the fused route
+existed), interleaved round by round in ONE process after a warm-up round.  Prints per batch size and route the median ms per
+batch with min / max over the rounds, then -- from one extra instrumented run per route -- the per-token split: head (device time
+from the head product to the candidates), attention (the cached-attention launches), cache gather (plain route only), scorer
+(host time in BeamScorer.process) and host sync (host time waiting in the read-back).
+BATCHES ("8,32"), ROUNDS (5), MAXLEN (150), BEAMS (5)."""
+import os, statistics, sys, time
+import torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import mvlt_amd as M
+from mvlt_amd import decode, ops
+
+torch.manual_seed(0)
+BEAMS, MAXLEN, ROUNDS = int(os.environ.get("BEAMS", 5)), int(os.environ.get("MAXLEN", 150)), int(os.environ.get("ROUNDS", 5))
+cfg = M.MVLBertConfigForImageCaption(); cfg.max_length = MAXLEN; cfg.eos_token_id = None
+tok = type("Tok", (), {"mask_token_id": 103, "sep_token_id": 102})()
+model = M.MVLBertForImageCaption(cfg, tokenizer=tok).cuda().eval()
+ROUTES = (("fused", "1"), ("plain", "0"))
+
+
+def run(img, flag):
+    os.environ["MVLT_BEAM_FUSED"] = flag
+    torch.cuda.synchronize(); t = time.time()
+    out = model(img, None, BEAMS, "unilm")
+    torch.cuda.synchronize()
+    return (time.time() - t) * 1e3, out
+
+
+class Split:
+    """Device segments by event pairs, host segments by wall clock, for ONE run."""
+
+    def __init__(self):
+        self.ev, self.host = {"head": [], "attention": [], "cache gather": []}, {"scorer": 0.0, "host sync": 0.0}
+        self.saved = []
+
+    def device(self, name, fn):
+        def wrapped(*a, **kw):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); out = fn(*a, **kw); e1.record()
+            self.ev[name].append((e0, e1))
+            return out
+        return wrapped
+
+    def wall(self, name, fn):
+        def wrapped(*a, **kw):
+            t = time.time(); out = fn(*a, **kw); self.host[name] += time.time() - t
+            return out
+        return wrapped
+
+    def patch(self, obj, attr, new):
+        self.saved.append((obj, attr, getattr(obj, attr)))
+        setattr(obj, attr, new)
+
+    def __enter__(self):
+        head = model.MLM_head_seq2seq
+        self.patch(ops, "gemm_beam_candidates", self.device("head", ops.gemm_beam_candidates))
+        self.patch(ops, "attn_cached_beam", self.device("attention", ops.attn_cached_beam))
+        self.patch(ops, "attn_cached", self.device("attention", ops.attn_cached))
+        # plain route: the head segment runs from the logits product to the end of topk
+        self.t0 = None
+        real_logits, real_topk, real_sel = head._logits, torch.topk, torch.Tensor.index_select
+
+        def logits(*a, **kw):
+            self.t0 = torch.cuda.Event(enable_timing=True); self.t0.record()
+            return real_logits(*a, **kw)
+
+        def topk(*a, **kw):
+            out = real_topk(*a, **kw)
+            if self.t0 is not None:
+                e1 = torch.cuda.Event(enable_timing=True); e1.record()
+                self.ev["head"].append((self.t0, e1)); self.t0 = None
+            return out
+
+        def sel(t, *a, **kw):
+            return (self.device("cache gather", real_sel) if t.dim() == 4 else real_sel)(t, *a, **kw)
+
+        self.patch(head, "_logits", logits)
+        self.patch(torch, "topk", topk)
+        self.patch(torch.Tensor, "index_select", sel)
+        self.patch(decode.BeamScorer, "process", self.wall("scorer", decode.BeamScorer.process))
+        self.patch(torch.Tensor, "cpu", self.wall("host sync", torch.Tensor.cpu))
+        self.patch(torch.Tensor, "tolist", self.wall("host sync", torch.Tensor.tolist))
+        return self
+
+    def __exit__(self, *exc):
+        for obj, attr, old in reversed(self.saved):
+            setattr(obj, attr, old)
+        torch.cuda.synchronize()
+
+    def per_token(self):
+        out = {k: 1e3 * sum(a.elapsed_time(b) for a, b in v) / MAXLEN for k, v in self.ev.items()}
+        out.update({k: 1e6 * v / MAXLEN for k, v in self.host.items()})
+        return out
+
+
+for B in [int(b) for b in os.environ.get("BATCHES", "8,32").split(",")]:
+    img = torch.randn(B, 3, 224, 224, device="cuda")
+    times, outs = {name: [] for name, _ in ROUTES}, {}
+    for r in range(ROUNDS + 1):                       # round 0 warms up
+        for name, flag in ROUTES:
+            ms, outs[name] = run(img, flag)
+            if r:
+                times[name].append(ms)
+    same = outs["fused"].shape == outs["plain"].shape and bool((outs["fused"] == outs["plain"]).all())
+    for name, _ in ROUTES:
+        v = times[name]
+        print(f"B={B:3d} beams={BEAMS} {name:6s} median {statistics.median(v):8.2f} ms/batch  (min {min(v):.2f} max {max(v):.2f}, spread "
+              f"{max(v) - min(v):.2f} over {len(v)} rounds)", flush=True)
+    gain = statistics.median(times["plain"]) - statistics.median(times["fused"])
+    print(f"B={B:3d} fused is {gain:+.2f} ms/batch ({1e3 * gain / MAXLEN:+.1f} us/token) against a plain-route spread of "
+          f"{max(times['plain']) - min(times['plain']):.2f} ms; same sequences on both routes (random weights, bf16 against f32 logits): {same}", flush=True)
+    for name, flag in ROUTES:
+        with Split() as sp:
+            run(img, flag)
+        print(f"B={B:3d} {name:6s} per token [us]: " + "  ".join(f"{k} {v:7.1f}" for k, v in sp.per_token().items()), flush=True)
