@@ -36,14 +36,14 @@ enum { MVLT_OK = 0, MVLT_ERR_ARG = -1, MVLT_ERR_LAUNCH = -2, MVLT_ERR_UNSUPPORTE
  * signature; a binding compiles / hard-codes the value it was written against and compares it with what the
  * loaded library returns.  mvlt_sizeof(MVLT_STRUCT_*) lets a binding that mirrors the structs by hand (ctypes,
  * cgo, JNI) prove that its mirror has the size the library was compiled with (0 for an unknown id). */
-#define MVLT_ABI_VERSION 13
+#define MVLT_ABI_VERSION 14
 int mvlt_version(void);            /* MVLT_ABI_VERSION of the loaded library */
 const char* mvlt_arch(void);       /* "gfx950" */
 enum { MVLT_STRUCT_GEMM = 0, MVLT_STRUCT_LAYERNORM = 1, MVLT_STRUCT_LAYERNORM_BWD = 2, MVLT_STRUCT_LN_REDUCE_ITEM = 3,
        MVLT_STRUCT_ATTN = 4, MVLT_STRUCT_SWIN_WMSA = 5, MVLT_STRUCT_EMBED = 6, MVLT_STRUCT_ATTN_CACHED = 7,
        MVLT_STRUCT_ZERO_ITEM = 8, MVLT_STRUCT_RANGE = 9, MVLT_STRUCT_MLM_MASK = 10, MVLT_STRUCT_GREEDY_STATE = 11, MVLT_STRUCT_SWIN_DBIAS_ITEM = 12,
        MVLT_STRUCT_SAMPLE_STATE = 13, MVLT_STRUCT_SAMPLE_FILTER = 14, MVLT_STRUCT_BEAM_CAND = 15, MVLT_STRUCT_ATTN_CACHED_BEAM = 16,
-       MVLT_STRUCT_COUNT = 17 };
+       MVLT_STRUCT_HEAD_CE = 17, MVLT_STRUCT_COUNT = 18 };
 size_t mvlt_sizeof(int struct_id);
 
 /* ------------------------------------------------------------------ GEMM
@@ -237,6 +237,36 @@ typedef struct MvltBeamCand {
     float* lse;                         /* [M] or NULL */
 } MvltBeamCand;
 int mvlt_gemm_beam_candidates(const MvltGemm* p, const MvltBeamCand* c, void* stream);
+/* MLM decoder product with the forward of F.cross_entropy(ignore_index = -100) in its epilogue (csrc/headce.hip): the training
+ * loss and per-token log-probabilities without a pass over stored logits, and with C == NULL without any logits at all.
+ * p: A = the transformed hidden rows [M, K], B = W [N = V, K] (torch-Linear layout), bias f32 [V] (MVLT_EPI_BIAS, the only epilogue
+ * bit honoured), dtype bf16 or f32, m_dev optional (only the first *m_dev rows exist), C optional ([M, ldc >= V], storage dtype).
+ * Per element x = round_to_dtype(acc + bias[n]) -- the value the plain product stores, and the value every statistic below is
+ * computed from, so exp(x - lse) in mvlt_ce_bwd_ragged sees the numbers the forward saw.  Per row m < min(M, *m_dev):
+ *   lse[m] = max_n x + logf(sum_n __expf(x - max)) over n < V    (f32; every row, labelled or not)
+ *   x_label[m] = x[m, labels[m]]                                 (f32; written only for 0 <= labels[m] < V)
+ *   acc[0] = sum of (lse[m] - x_label[m]) over rows with labels[m] >= 0,  acc[1] = their number
+ * (the layout mvlt_ce_fwd_ragged fills: acc[0] / acc[1] is the mean, mvlt_ce_bwd_ragged takes lse and acc + 1 unchanged).  A label
+ * >= V makes acc[0] NaN.  Rows at or beyond *m_dev leave lse / x_label / C unwritten; *m_dev = 0 gives acc = (0, 0).
+ * Summation shape (fixed: the same operands give the same bits, no float atomics): 64 x 128 tiles of the register-staged main
+ * loop; per row and wave (max, sum) over its 64 columns -- 16 per lane in column order, then across the 4 lane groups by
+ * xor-16 / xor-32 exchanges --, the two waves of a row meet in LDS, one (max, sum) pair per row and column tile goes to
+ * `workspace`; a second launch (one wave per row) folds the ceil(V / 128) pairs, lane-strided in tile order and then by a
+ * butterfly; a third, single-workgroup launch adds the rows' terms: thread t rows t, t + 1024, ..., then a tree in LDS.
+ * workspace: mvlt_mlm_head_ce_workspace_bytes(M, V) bytes, 16-byte aligned.
+ * Refusals (MVLT_ERR_ARG, nothing launched, nothing written): NULL p / h / A / B / bias / labels / lse / x_label / acc / workspace,
+ * M, V or K < 1, ldc < V with C given, a workspace that is too small, a k-major operand, an epilogue bit other than
+ * BIAS; operands the loop and the epilogue read or write in vectors: A / B / C / workspace not 16-byte aligned, lda or ldb not a
+ * multiple of 16 bytes, ldc not a multiple of 4, bias / lse / x_label / acc not 4-byte and labels not 8-byte aligned.
+ * MVLT_ERR_UNSUPPORTED: a dtype other than bf16 / f32. */
+typedef struct MvltHeadCE {
+    const int64_t* labels;              /* [M]; negative = ignored */
+    float* lse; float* x_label;         /* [M] */
+    float* acc;                         /* [2] */
+    void* workspace; size_t workspace_bytes;
+} MvltHeadCE;
+int mvlt_mlm_head_ce(const MvltGemm* p, const MvltHeadCE* h, void* stream);
+size_t mvlt_mlm_head_ce_workspace_bytes(int M, int V);
 
 /* Decode step (model.py:82-108: 2 new tokens per sample): skinny product with the reduction split over workgroups:
  * acc[s][M][N] (f32, k_splits slabs) = A[:, k-slice s] B[:, k-slice s]^T, M <= 64, both operands k-contiguous, no epilogue;

@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(_HERE, "libmvlt_hip.so")
 
 F32, BF16 = 0, 1
 OK = 0
-ABI_VERSION = 13         # == MVLT_ABI_VERSION of the include/mvlt_hip.h these mirrors were written against
+ABI_VERSION = 14         # == MVLT_ABI_VERSION of the include/mvlt_hip.h these mirrors were written against
 ERRORS = {-1: "MVLT_ERR_ARG", -2: "MVLT_ERR_LAUNCH", -3: "MVLT_ERR_UNSUPPORTED"}
 
 EPI_BIAS, EPI_GELU, EPI_SAVE_PRE, EPI_DROPOUT = 1, 2, 4, 8
@@ -155,6 +155,10 @@ class MvltAttnCachedBeam(C.Structure):
         ("num_beams", i32), ("prefix", i32), ("slot", vp), ("ld_slot", i64)]
 
 
+class MvltHeadCE(C.Structure):
+    _fields_ = [("labels", vp), ("lse", vp), ("x_label", vp), ("acc", vp), ("workspace", vp), ("workspace_bytes", sz)]
+
+
 # every symbol include/mvlt_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "mvlt_version": (i32, []),
@@ -174,6 +178,8 @@ SYMBOLS = {
     "mvlt_gemm_sample_filtered": (i32, [C.POINTER(MvltGemm), vp, vp, C.POINTER(MvltSampleFilter), vp, vp, u64, u32, f32, vp]),
     "mvlt_gemm_sample_filtered_step": (i32, [C.POINTER(MvltGemm), vp, vp, C.POINTER(MvltSampleFilter), C.POINTER(MvltSampleState), vp]),
     "mvlt_gemm_beam_candidates": (i32, [C.POINTER(MvltGemm), C.POINTER(MvltBeamCand), vp]),
+    "mvlt_mlm_head_ce": (i32, [C.POINTER(MvltGemm), C.POINTER(MvltHeadCE), vp]),
+    "mvlt_mlm_head_ce_workspace_bytes": (sz, [i32, i32]),
     "mvlt_gemm_skinny_accum": (i32, [C.POINTER(MvltGemm), vp, i32, vp]),
     "mvlt_layernorm_acc_fwd": (i32, [i32, vp, i32, vp, vp, vp, vp, f32, i32, i32, vp, vp]),
     "mvlt_colsum": (i32, [i32, vp, i64, i32, i32, vp, i32, vp, vp]),
@@ -236,7 +242,7 @@ SYMBOLS = {
 # ctypes mirror of every struct, in the order of the MVLT_STRUCT_* ids of the header
 STRUCTS = [MvltGemm, MvltLayerNorm, MvltLayerNormBwd, MvltLnReduceItem, MvltAttn, MvltSwinWmsa, MvltEmbed,
            MvltAttnCached, MvltZeroItem, MvltRange, MvltMlmMask, MvltGreedyState, MvltSwinDbiasItem,
-           MvltSampleState, MvltSampleFilter, MvltBeamCand, MvltAttnCachedBeam]
+           MvltSampleState, MvltSampleFilter, MvltBeamCand, MvltAttnCachedBeam, MvltHeadCE]
 
 _lib = None
 

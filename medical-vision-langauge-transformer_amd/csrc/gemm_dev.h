@@ -403,4 +403,292 @@ MVLT_DEV unsigned prefetch_lines(const GemmDev& p) {
     return acc;
 }
 
+// k-major bf16 tiles of 64 / 96 / 128 rows are stored (96: in 128-wide rows) with their 32-byte column chunks XOR-swizzled by a function
+// of k: a ds_read_b64_tr_b16 group of 32 lanes reads 8 k-rows {k0..k0+3, k0+8..k0+11} x 32 bytes, which padding alone
+// cannot spread over the 64 banks (rows k and k+8 alias for every pad that keeps 32-byte chunks aligned: 2-way conflicts,
+// 32 % of the LDS cycles of the weight-gradient kernels, profiles/r2_dominant_kernel_pmc.txt).
+template <int R> MVLT_DEV int kswz(int k) {
+    return R >= 96 ? ((k & 3) | ((k >> 1) & 4)) : (((k >> 1) & 1) | ((k >> 2) & 2));
+}
+template <typename T, int R, bool KMAJOR> struct TileGeom {
+    static constexpr int E = TypeInfo<T>::E;
+    static constexpr int BKE = 128 / (int)sizeof(T);          // k elements per tile
+    static constexpr bool SWZ = KMAJOR && sizeof(T) == 2 && (R == 64 || R == 96 || R == 128);
+    static constexpr int PAD = KMAJOR ? (SWZ ? (R == 96 ? 32 : 0) : (sizeof(T) == 2 ? 16 : 4)) : 0;   // 96: six chunks swizzled inside eight
+    static constexpr int LD = KMAJOR ? (R + PAD) : BKE;        // elements per LDS row
+    static constexpr int ELEMS = KMAJOR ? BKE * LD : R * BKE;
+    static constexpr int CHUNKS = R * 8;                        // 16-byte chunks per tile
+    static constexpr int PER_THREAD = CHUNKS / 256;
+    static constexpr int CPR = KMAJOR ? (R / E) : 8;            // chunks per LDS row
+};
+
+template <typename T, int R, bool KMAJOR>
+MVLT_DEV void tile_load(typename TypeInfo<T>::Vec* __restrict__ regs, const T* base,
+                        long ld, int row0, int row_lim, int k0, int k_lim, bool vec_ok) {
+    using G = TileGeom<T, R, KMAJOR>;
+#pragma unroll
+    for (int i = 0; i < G::PER_THREAD; ++i) {
+        const int idx = threadIdx.x + 256 * i;
+        const int lr = idx / G::CPR, ch = idx % G::CPR;
+        if (KMAJOR) regs[i] = load_chunk<T>(base, ld, k0 + lr, row0 + ch * G::E, k_lim, row_lim, vec_ok);
+        else        regs[i] = load_chunk<T>(base, ld, row0 + lr, k0 + ch * G::E, row_lim, k_lim, vec_ok);
+    }
+}
+
+// Fast path of the k-loop: per-thread source pointers are computed ONCE (rows /
+// columns beyond the matrix edge are clamped to the last valid one: they only
+// feed output rows/columns that are never stored), then every full k-tile is
+// PER_THREAD unpredicated 16-byte loads and a pointer bump.
+template <typename T, int R, bool KMAJOR> struct FastLoader {
+    using G = TileGeom<T, R, KMAJOR>;
+    using Vec = typename TypeInfo<T>::Vec;
+    const T* ptr[G::PER_THREAD];
+    long step;
+    MVLT_DEV void init(const T* base, long ld, int row0, int row_lim, int k0) {
+#pragma unroll
+        for (int i = 0; i < G::PER_THREAD; ++i) {
+            const int idx = threadIdx.x + 256 * i;
+            const int lr = idx / G::CPR, ch = idx % G::CPR;
+            if (KMAJOR) {
+                int col = row0 + ch * G::E;
+                col = min(col, max(row_lim - G::E, 0));
+                ptr[i] = base + (long)(k0 + lr) * ld + col;
+            } else {
+                const int row = min(row0 + lr, row_lim - 1);
+                ptr[i] = base + (long)row * ld + k0 + ch * G::E;
+            }
+        }
+        step = KMAJOR ? (long)G::BKE * ld : (long)G::BKE;
+    }
+    MVLT_DEV void load(Vec* __restrict__ regs) {
+#pragma unroll
+        for (int i = 0; i < G::PER_THREAD; ++i) { regs[i] = *reinterpret_cast<const Vec*>(ptr[i]); ptr[i] += step; }
+    }
+};
+
+template <typename T, int R, bool KMAJOR>
+MVLT_DEV void tile_store(const typename TypeInfo<T>::Vec* __restrict__ regs, T* lds) {
+    using G = TileGeom<T, R, KMAJOR>;
+    using Vec = typename TypeInfo<T>::Vec;
+#pragma unroll
+    for (int i = 0; i < G::PER_THREAD; ++i) {
+        const int idx = threadIdx.x + 256 * i;
+        const int lr = idx / G::CPR, ch = idx % G::CPR;
+        if (KMAJOR && G::SWZ) *reinterpret_cast<Vec*>(lds + lr * G::LD + ((((ch >> 1) ^ kswz<R>(lr)) << 4) | ((ch & 1) << 3))) = regs[i];
+        else if (KMAJOR) *reinterpret_cast<Vec*>(lds + lr * G::LD + ch * G::E) = regs[i];
+        else        *reinterpret_cast<Vec*>(lds + lr * G::BKE + ((ch ^ (lr & 7)) * G::E)) = regs[i];
+    }
+}
+
+// fragment for rows [row0,row0+16) and k-block kb (0/1) of the tile
+template <typename T, int R, bool KMAJOR>
+MVLT_DEV typename Mma<T>::Frag tile_frag(const T* lds, int row0, int kb) {
+    using G = TileGeom<T, R, KMAJOR>;
+    if constexpr (KMAJOR && G::SWZ) {
+        const int l = threadIdx.x & 63;
+        const int g = l >> 4, i = l & 15, q = i >> 2, pp = i & 3;
+        const int k = kb * 32 + 8 * g + q, c = row0 >> 4;
+        const bf16_t* p0 = lds + k * G::LD + ((c ^ kswz<R>(k)) << 4) + 4 * pp;
+        const bf16_t* p1 = lds + (k + 4) * G::LD + ((c ^ kswz<R>(k + 4)) << 4) + 4 * pp;
+        bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)p0);
+        bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)p1);
+        bf16x8 r;
+        r[0] = lo[0]; r[1] = lo[1]; r[2] = lo[2]; r[3] = lo[3];
+        r[4] = hi[0]; r[5] = hi[1]; r[6] = hi[2]; r[7] = hi[3];
+        return r;
+    } else if constexpr (KMAJOR) {
+        return frag_kmajor(lds, G::LD, row0, kb * Mma<T>::KB);
+    } else {
+    const int l = threadIdx.x & 63;
+    const int row = row0 + (l & 15);
+    const int ch = (kb * 4 + (l >> 4)) ^ (row & 7);
+    return *reinterpret_cast<const typename Mma<T>::Frag*>(lds + row * G::BKE + ch * G::E);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Register-staged tile main loop (256 threads = 2 x 2 waves, k-tiles of 128 bytes per row through LDS): the accumulators of output
+// tile (bx, by), k-slice bz, of the EFFECTIVE problem p (the caller has left already when by * BM >= p.M).  acc[i][j][r] <->
+// m = by BM + wm BM/2 + 16 i + (lane & 15), n = bx BN + wn BN/2 + 16 j + 4 (lane >> 4) + r.  Ends on a barrier: sA / sB are free.
+// Shared by gemm.hip (every epilogue of MvltGemm) and headce.hip (the cross-entropy statistics).
+template <typename T, int BM, int BN, bool AK, bool BK_, bool PF2, int DEEP = 0>
+MVLT_DEV void gemm_mainloop(const GemmDev& p, const int bx, const int by, const int bz, T* sA, T* sB, f32x4 (&acc)[BM / 32][BN / 32]) {
+    using GA = TileGeom<T, BM, AK>;
+    using GB = TileGeom<T, BN, BK_>;
+    using Vec = typename TypeInfo<T>::Vec;
+    constexpr int FM = BM / 32, FN = BN / 32;
+    const int m0 = by * BM, n0 = bx * BN;
+    const int ks = bz * p.k_per_split;
+    const int ke = min(p.K, ks + p.k_per_split);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int wm = wave >> 1, wn = wave & 1;
+    const T* A = reinterpret_cast<const T*>(p.A);
+    const T* B = reinterpret_cast<const T*>(p.B);
+
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+        for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    // Single LDS stage (so 3-4 workgroups fit per CU and hide each other's HBM latency);
+    // the next tile's global loads are in flight in registers while this tile is multiplied.
+    Vec ra[GA::PER_THREAD], rb[GB::PER_THREAD];
+    const int nkt = (ke - ks + GA::BKE - 1) / GA::BKE;
+    // number of k-tiles that lie fully inside [ks, ke) and can use unpredicated vector loads.  Not for a k-major operand
+    // whose extent (M / N) ends inside a 16-byte chunk behind a padded stride (the MLM decoder's weight gradient: M = 30522,
+    // lda = 30528): FastLoader clamps that chunk back inside the extent, which loads other columns into its place
+    // (wrong output rows 30520, 30521); the predicated loads below zero its tail instead.  Only the last row / column tile
+    // holds that chunk: the other workgroups keep the fast loop.
+    const bool ragged = (AK && p.M % GA::E != 0 && m0 + BM > p.M) || (BK_ && p.N % GB::E != 0 && n0 + BN > p.N);
+    const int nfast = (p.a_vec && p.b_vec && !ragged) ? (ke - ks) / GA::BKE : 0;
+    FastLoader<T, BM, AK> la;
+    FastLoader<T, BN, BK_> lb;
+    la.init(A, p.lda, m0, p.M, ks);
+    lb.init(B, p.ldb, n0, p.N, ks);
+    // fused bias gradient: workgroups of the first output-column tile also sum their A tile over k.  The sums are
+    // taken from the staging REGISTERS (a thread's chunks of a k-major tile all lie in one 16-byte column group:
+    // 256 % CPR == 0), a few adds per k-tile spread over all 256 threads, and meet in LDS once at the end; summing
+    // the LDS image instead (64 dependent ds_reads per k-tile in 64-128 threads while the other waves wait at the
+    // barrier) cost 35-50 % of the weight-gradient launches (profiles/r2_wgrad_colsum.txt).
+    constexpr int EA = GA::E;
+    static_assert(!AK || (256 % GA::CPR == 0 && (size_t)GA::ELEMS * sizeof(T) >= 256 * EA * sizeof(float)), "colsum layout");
+    float cs[EA];
+#pragma unroll
+    for (int e = 0; e < EA; ++e) cs[e] = 0.f;
+    const bool do_colsum = AK && p.a_colsum != nullptr && bx == 0;
+    auto colsum_regs = [&](const Vec* r) {
+        if (AK && do_colsum) {
+#pragma unroll
+            for (int i = 0; i < GA::PER_THREAD; ++i)
+#pragma unroll
+                for (int e = 0; e < EA; ++e) cs[e] += to_f(r[i][e]);
+        }
+    };
+    auto compute_tile = [&]() {
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) {
+            typename Mma<T>::Frag fa[FM], fb[FN];
+#pragma unroll
+            for (int i = 0; i < FM; ++i) fa[i] = tile_frag<T, BM, AK>(sA, wm * (BM / 2) + i * 16, kb);
+#pragma unroll
+            for (int j = 0; j < FN; ++j) fb[j] = tile_frag<T, BN, BK_>(sB, wn * (BN / 2) + j * 16, kb);
+#pragma unroll
+            for (int i = 0; i < FM; ++i)
+#pragma unroll
+                for (int j = 0; j < FN; ++j) Mma<T>::mma(acc[i][j], fb[j], fa[i]);
+        }
+    };
+    // ---- hot loop: full k-tiles only, no predication, nothing but loads / ds_write / ds_read / MFMA
+    if constexpr (DEEP == 2) {
+        // weight gradients (1-2 workgroups per CU, thousands of k rows): two register sets AND two LDS stages, one
+        // barrier per k-tile.  Tile t+1 (loaded a whole iteration ago) is written to the other LDS stage at the top of
+        // iteration t, so its ds_writes, the global loads of tile t+2 and the ds_reads + MFMAs of tile t all overlap;
+        // with one stage every k-tile was a chain load-wait -> ds_write -> barrier -> ds_read -> MFMA -> barrier.
+        Vec qa[2][GA::PER_THREAD], qb[2][GB::PER_THREAD];
+        T* const sA1 = sA + GA::ELEMS;
+        T* const sB1 = sB + GB::ELEMS;
+        auto compute_stage = [&](const T* a_, const T* b_) {
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb) {
+                typename Mma<T>::Frag fa[FM], fb[FN];
+#pragma unroll
+                for (int i = 0; i < FM; ++i) fa[i] = tile_frag<T, BM, AK>(a_, wm * (BM / 2) + i * 16, kb);
+#pragma unroll
+                for (int j = 0; j < FN; ++j) fb[j] = tile_frag<T, BN, BK_>(b_, wn * (BN / 2) + j * 16, kb);
+#pragma unroll
+                for (int i = 0; i < FM; ++i)
+#pragma unroll
+                    for (int j = 0; j < FN; ++j) Mma<T>::mma(acc[i][j], fb[j], fa[i]);
+            }
+        };
+        if (nfast > 0) {
+            la.load(qa[0]); lb.load(qb[0]);
+            if (nfast > 1) { la.load(qa[1]); lb.load(qb[1]); }
+            tile_store<T, BM, AK>(qa[0], sA);
+            tile_store<T, BN, BK_>(qb[0], sB);
+            colsum_regs(qa[0]);
+            __syncthreads();
+            for (int kt = 0; kt < nfast; kt += 2) {
+                // even tile kt lives in stage 0, registers set 0 is free again
+                if (kt + 1 < nfast) { tile_store<T, BM, AK>(qa[1], sA1); tile_store<T, BN, BK_>(qb[1], sB1); colsum_regs(qa[1]); }
+                if (kt + 2 < nfast) { la.load(qa[0]); lb.load(qb[0]); }
+                compute_stage(sA, sB);
+                __syncthreads();
+                if (kt + 1 < nfast) {
+                    if (kt + 2 < nfast) { tile_store<T, BM, AK>(qa[0], sA); tile_store<T, BN, BK_>(qb[0], sB); colsum_regs(qa[0]); }
+                    if (kt + 3 < nfast) { la.load(qa[1]); lb.load(qb[1]); }
+                    compute_stage(sA1, sB1);
+                    __syncthreads();
+                }
+            }
+        }
+    } else if (!PF2) {
+        if (nfast > 0) { la.load(ra); lb.load(rb); }
+        for (int kt = 0; kt < nfast; ++kt) {
+            tile_store<T, BM, AK>(ra, sA);
+            tile_store<T, BN, BK_>(rb, sB);
+            colsum_regs(ra);
+            __syncthreads();
+            if (kt + 1 < nfast) { la.load(ra); lb.load(rb); }
+            compute_tile();
+            __syncthreads();
+        }
+    } else {
+        // long reductions: prefetch distance 2 (two register sets) -- the loads of tile t+2 are in
+        // flight while tile t is multiplied (measured 8-17 % faster for K >= 1536)
+        Vec ra1[GA::PER_THREAD], rb1[GB::PER_THREAD];
+        if (nfast > 0) { la.load(ra); lb.load(rb); }
+        if (nfast > 1) { la.load(ra1); lb.load(rb1); }
+        for (int kt = 0; kt < nfast; kt += 2) {
+            tile_store<T, BM, AK>(ra, sA);
+            tile_store<T, BN, BK_>(rb, sB);
+            colsum_regs(ra);
+            __syncthreads();
+            if (kt + 2 < nfast) { la.load(ra); lb.load(rb); }
+            compute_tile();
+            __syncthreads();
+            if (kt + 1 < nfast) {
+                tile_store<T, BM, AK>(ra1, sA);
+                tile_store<T, BN, BK_>(rb1, sB);
+                colsum_regs(ra1);
+                __syncthreads();
+                if (kt + 3 < nfast) { la.load(ra1); lb.load(rb1); }
+                compute_tile();
+                __syncthreads();
+            }
+        }
+    }
+    // ---- K-tail (at most one tile when the operands are vector-aligned), generic predicated loads
+    for (int kt = nfast; kt < nkt; ++kt) {
+        const int k0 = ks + kt * GA::BKE;
+        tile_load<T, BM, AK>(ra, A, p.lda, m0, p.M, k0, ke, p.a_vec);
+        tile_load<T, BN, BK_>(rb, B, p.ldb, n0, p.N, k0, ke, p.b_vec);
+        tile_store<T, BM, AK>(ra, sA);
+        tile_store<T, BN, BK_>(rb, sB);
+        colsum_regs(ra);
+        __syncthreads();
+        compute_tile();
+        __syncthreads();
+    }
+    if (AK && do_colsum) {
+        float* red = reinterpret_cast<float*>(sA);           // free: the k-loop ended on a barrier
+#pragma unroll
+        for (int e = 0; e < EA; ++e) red[threadIdx.x * EA + e] = cs[e];
+        __syncthreads();
+        float csum = 0.f;
+        if (threadIdx.x < BM) {
+            const int ch = threadIdx.x / EA, e = threadIdx.x % EA;
+#pragma unroll 4
+            for (int g = 0; g < 256 / GA::CPR; ++g) csum += red[(g * GA::CPR + ch) * EA + e];
+        }
+        const int m = m0 + threadIdx.x;
+        if (threadIdx.x < BM && m < p.M) {
+            if (p.atomic_out) atomicAdd(&p.a_colsum[m], csum);
+            else if (p.split_k > 1) p.ws_colsum[(long)bz * p.M + m] = csum;
+            else p.a_colsum[m] = (p.epi & MVLT_EPI_ACCUM) ? p.a_colsum[m] + csum : csum;
+        }
+        __syncthreads();                                      // (persistent callers reuse sA)
+    }
+}
+
 }  // namespace

@@ -873,6 +873,7 @@ extern "C" size_t mvlt_sizeof(int struct_id) {
         case MVLT_STRUCT_SAMPLE_FILTER: return sizeof(MvltSampleFilter);
         case MVLT_STRUCT_BEAM_CAND: return sizeof(MvltBeamCand);
         case MVLT_STRUCT_ATTN_CACHED_BEAM: return sizeof(MvltAttnCachedBeam);
+        case MVLT_STRUCT_HEAD_CE: return sizeof(MvltHeadCE);
         default: return 0;
     }
 }

@@ -264,13 +264,21 @@ class _MlmLossFn(torch.autograd.Function):
     logits stay in one padded [rows, ld] buffer, CE backward overwrites it in place."""
 
     @staticmethod
-    def forward(ctx, token, x, head, labels, save, rd=None, label_sync=None):
+    def forward(ctx, token, x, head, labels, save, rd=None, label_sync=None, fused=False):
         ar = Arena.of(head, x.dtype)
         ar.refresh_shadow()
         with ops.pin_stream():
             pre, t1, t2, mean, rstd = head._transform(ar, x, save, rd)
-            logits, V = head._logits(ar, t2, rd)
-            acc, lse = ops.ce_fwd(logits, V, labels, rows_dev=rd)
+            if fused:
+                # decoder product with the loss statistics in its epilogue (mvlt_mlm_head_ce): no pass over stored logits, and
+                # no logits at all when nothing will be differentiated
+                dec = head.predictions.decoder
+                V = dec.out_features
+                acc, lse, _, logits = ops.mlm_head_ce(t2, ar.compute(dec.weight), dec.bias.data, labels, V, rows_dev=rd,
+                                                      want_logits=save)
+            else:
+                logits, V = head._logits(ar, t2, rd)
+                acc, lse = ops.ce_fwd(logits, V, labels, rows_dev=rd)
         if label_sync is not None:
             # data parallel: model.py:410 is a mean over the labelled tokens of the WHOLE batch.  label_sync all-reduces
             # the 4-byte label count and returns N_global / world; dividing this rank's nll sum by it makes the rank
@@ -290,7 +298,7 @@ class _MlmLossFn(torch.autograd.Function):
             dlogits = ops.ce_bwd(logits, V, labels, lse, acc, grad_scale=1.0, grad_scale_dev=gs, rows_dev=rd)
             dx = ctx.head._backward_from_dlogits(ar, dlogits, V, x, pre, t1, t2, mean, rstd, rd)
         ctx.saved = None
-        return None, dx, None, None, None, None, None
+        return None, dx, None, None, None, None, None, None
 
 
 class _GatherRowsFn(torch.autograd.Function):
@@ -451,6 +459,8 @@ class MVLBertPretrainedModel(nn.Module):
 
 # ----------------------------------------------------------------------------- heads
 _AUTO_PACK = os.environ.get("MVLT_AUTO_PACK", "1") != "0"
+# A/B only: MVLT_HEAD_CE=1 routes the pre-training loss through the fused head (mvlt_mlm_head_ce) that the caption model uses
+_HEAD_CE_AB = os.environ.get("MVLT_HEAD_CE", "0") == "1"
 
 
 
@@ -564,7 +574,8 @@ class MVLBertForPretraining(MVLBertPretrainedModel):
                                         # every rank runs and follows with backward()) takes it; no_grad forwards -- rank-0
                                         # validation, an uneven last evaluation batch -- keep the per-rank mean and never touch
                                         # the process group (GradReducer.no_label_sync() switches it off for grad-mode forwards too)
-                                        self.__dict__.get("_mvlt_label_sync") if torch.is_grad_enabled() else None)
+                                        self.__dict__.get("_mvlt_label_sync") if torch.is_grad_enabled() else None,
+                                        _HEAD_CE_AB)
             if compact:
                 mlm_loss = torch.where(valid.sum() > cap * B, torch.full_like(mlm_loss, float("nan")), mlm_loss)
             if packed:
@@ -686,9 +697,18 @@ class MVLBertForImageCaption(MVLBertPretrainedModel):
         self.tokenizer = tokenizer
         self.MLM_head_seq2seq = BertOnlyMLMHead(config)
 
-    def forward(self, image, caption, num_beams, learning_strategy, sample_mode='greedy', seed=None, temperature=1.0, top_k=0, top_p=1.0):
+    def forward(self, image, caption, num_beams, learning_strategy, sample_mode='greedy', seed=None, temperature=1.0, top_k=0, top_p=1.0,
+                labels=None):
+        """Reference signature (model.py:479) plus ``labels`` (int64 [B, T], -100 = ignored): with it and ``num_beams == 0`` the
+        call returns the scalar ``F.cross_entropy(logits, labels, ignore_index=-100)`` of the fine-tuning loop
+        (run_report_generation_cxr.py:469-471) instead of the logits -- the mean over the labelled positions, NaN when there
+        are none -- computed on the labelled rows only, with the loss inside the decoder product (loss_forward)."""
+        if labels is not None and num_beams >= 1:
+            raise ValueError("labels ask for the training loss: num_beams must be 0")
         Arena.of(self, compute_dtype_of(self))
         image_feature = self.conv(image)
+        if labels is not None:
+            return self.loss_forward(image_feature, caption, labels, learning_strategy)
         if num_beams > 1:
             from .decode import beam_search          # scorer restated from HF 4.16: parity unpinned (DESIGN.md section 8)
             return beam_search(self, image_feature, num_beams, learning_strategy=learning_strategy)
@@ -706,3 +726,61 @@ class MVLBertForImageCaption(MVLBertPretrainedModel):
         if learning_strategy == 'normal':
             return self.MLM_head_seq2seq(torch.cat([sep_out[:, None], text_out[:, :-1]], dim=1)).transpose(1, 2)
         raise NotImplementedError("learning_strategy:", learning_strategy, "is not implemented! Try 'unilm' or 'normal'.")
+
+    # ---- training loss and token scoring: the head runs on gathered rows and never hands logits to torch
+    def _head_rows(self, image_feature, caption, learning_strategy):
+        """(hidden [B * L, H], text_row int64 [B * T]): the encoder's rows and, per caption position (b, t), the row the MLM head
+        reads for it -- text token t for 'unilm', one row earlier ([SEP] for t = 0) for 'normal' (model.py:707 as a row table)."""
+        if learning_strategy not in ('unilm', 'normal'):
+            raise NotImplementedError("learning_strategy:", learning_strategy, "is not implemented! Try 'unilm' or 'normal'.")
+        out, _ = self.MVLBert(text_idx=caption, text_mask=None, image_feature=image_feature, image_mask=None, seq2seq_mask=True)
+        hidden = out.last_hidden_state
+        B, Lq, H = hidden.shape
+        T = caption.shape[1]
+        first = image_feature.shape[1] + (2 if learning_strategy == 'unilm' else 1)
+        key = (B, T, Lq, first, hidden.device)
+        cached = self.__dict__.get("_mvlt_text_row")
+        if cached is None or cached[0] != key:
+            dev = hidden.device
+            rows = (torch.arange(B, device=dev) * Lq + first)[:, None] + torch.arange(T, device=dev)[None, :]
+            cached = self.__dict__["_mvlt_text_row"] = (key, rows.reshape(-1).contiguous())
+        return hidden.reshape(B * Lq, H), cached[1]
+
+    def loss_forward(self, image_feature, caption, labels, learning_strategy):
+        if tuple(labels.shape) != tuple(caption.shape):
+            raise ValueError(f"labels {tuple(labels.shape)} must have the caption's shape {tuple(caption.shape)}")
+        flat = labels.reshape(-1).to(torch.int64).contiguous()
+        hidden, text_row = self._head_rows(image_feature, caption, learning_strategy)
+        with ops.pin_stream():
+            gather_row, sel_labels, rd = ops.label_plan(flat, text_row)
+        x = _GatherRowsFn.apply(hidden, gather_row, rd)
+        head = self.MLM_head_seq2seq
+        # (the label-count all-reduce is a collective: grad-mode forwards only, as in MVLBertForPretraining.forward)
+        return _MlmLossFn.apply(_token(head, hidden.device), x.contiguous(), head, sel_labels, torch.is_grad_enabled(), rd,
+                                self.__dict__.get("_mvlt_label_sync") if torch.is_grad_enabled() else None, True)
+
+    @torch.no_grad()
+    def caption_logprobs(self, image, caption, learning_strategy='unilm'):
+        """Teacher-forced token scores: f32 [B, T] with log p(caption[b, t] | image, caption[b, :t]) at every position with
+        ``caption > 0`` and 0 elsewhere (reranking, perplexity).  One pass of the fused head with the caption as its own
+        labels and no logits buffer: log p = x_label - lse."""
+        Arena.of(self, compute_dtype_of(self))
+        hidden, text_row = self._head_rows(self.conv(image), caption, learning_strategy)
+        B, T = caption.shape
+        ids = caption.reshape(-1).to(torch.int64)
+        flat = torch.where(ids > 0, ids, torch.full_like(ids, -100)).contiguous()
+        head = self.MLM_head_seq2seq
+        ar = Arena.of(head, hidden.dtype)
+        ar.refresh_shadow()
+        dec = head.predictions.decoder
+        with ops.pin_stream():
+            gather_row, sel_labels, rd = ops.label_plan(flat, text_row)
+            x = ops.rows_transform(hidden, rowmap=gather_row)
+            _, _, t2, _, _ = head._transform(ar, x, False, rd)
+            _, lse, x_label, _ = ops.mlm_head_ce(t2, ar.compute(dec.weight), dec.bias.data, sel_labels, dec.out_features,
+                                                 rows_dev=rd, want_logits=False)
+        # back to the caption's layout: slot i < *rd of the packed scores holds the i-th scored position (a stable partition)
+        # (no host sync: the slot of a position is the number of labelled positions before it)
+        scored = flat >= 0
+        slot = (torch.cumsum(scored, 0) - 1).clamp_(min=0)
+        return torch.where(scored, (x_label - lse)[slot], torch.zeros((), device=hidden.device)).view(B, T)

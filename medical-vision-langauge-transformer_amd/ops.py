@@ -314,7 +314,8 @@ def gemm(A, B, *, a_kmajor=False, b_kmajor=False, out=None, out_f32=False, bias=
 
 
 def _head_gemm(A, W, bias, lda=None):
-    """The MvltGemm of an MLM-head product (A: [M <= 64, K], W: [N, K], f32 bias or None; no output matrix) -> (p, M, N).
+    """The MvltGemm of an MLM-head product (A: [M, K], W: [N, K], f32 bias or None) -> (p, M, N), without an output matrix: the decode
+    heads (M <= 64, checked by their entry points) have none, mlm_head_ce (any M) sets C / ldc itself when logits are wanted.
     ``lda``: row stride of A when its rows are read in place out of a wider buffer."""
     _need_cuda(A, W)
     M, K = A.shape
@@ -468,6 +469,36 @@ def gemm_beam_candidates(A, W, bias, beam_scores, num_beams, n_cand, want_lse=Fa
     c.cand_score, c.cand_beam, c.cand_tok, c.lse = _p(out[0]), _p(out[1]), _p(out[2]), (_p(lse) if want_lse else None)
     L.check(L.lib().mvlt_gemm_beam_candidates(C.byref(p), C.byref(c), _stream()), "mvlt_gemm_beam_candidates")
     return out, lse
+
+
+def mlm_head_ce(t2, W, bias, labels, V, rows_dev=None, want_logits=True):
+    """MLM decoder product with the cross-entropy forward in its epilogue (mvlt_mlm_head_ce): t2 [M, K], W [V, K], f32 bias [V],
+    int64 labels [M] (negative = ignored), rows_dev (int32 device scalar): only the first *rows_dev rows exist.
+    Returns ``(acc, lse, x_label, logits)``: acc f32 [2] = (sum of nll over the labelled rows, their number) as ce_fwd returns
+    it, lse f32 [M], x_label f32 [M] (the logit at the label; untouched where the label is ignored), and the logits in the
+    storage dtype ([M, ld] with ld = V rounded up to 64, as the head's plain product lays them out) or None with
+    ``want_logits=False`` -- then no logits exist anywhere."""
+    _need_cuda(t2, W, bias, labels)
+    assert W.shape[0] == V and t2.dtype == W.dtype and t2.stride(1) == 1 and W.stride(1) == 1
+    assert labels.dtype == torch.int64 and labels.is_contiguous() and labels.numel() == t2.shape[0]
+    p, M, _ = _head_gemm(t2, W, bias)
+    dev = t2.device
+    logits = None
+    if want_logits:
+        ld = (V + 63) // 64 * 64
+        logits = torch.empty((M, ld), dtype=t2.dtype, device=dev)
+        p.C, p.ldc = _p(logits), ld
+    if rows_dev is not None:
+        p.m_dev = _p(rows_dev)
+    out = torch.empty(2 * M + 2, dtype=torch.float32, device=dev)
+    lse, x_label, acc = out[:M], out[M:2 * M], out[2 * M:]
+    h = L.MvltHeadCE()
+    h.labels, h.lse, h.x_label, h.acc = _p(labels), _p(lse), _p(x_label), _p(acc)
+    need = L.lib().mvlt_mlm_head_ce_workspace_bytes(M, V)
+    ws = workspace("head_ce", need, dev)
+    h.workspace, h.workspace_bytes = _p(ws), ws.numel()
+    L.check(L.lib().mvlt_mlm_head_ce(C.byref(p), C.byref(h), _stream()), "mvlt_mlm_head_ce")
+    return acc, lse, x_label, logits
 
 
 def gumbel_noise(seed, tag, rows, N, device):
