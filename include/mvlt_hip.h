@@ -36,14 +36,14 @@ enum { MVLT_OK = 0, MVLT_ERR_ARG = -1, MVLT_ERR_LAUNCH = -2, MVLT_ERR_UNSUPPORTE
  * signature; a binding compiles / hard-codes the value it was written against and compares it with what the
  * loaded library returns.  mvlt_sizeof(MVLT_STRUCT_*) lets a binding that mirrors the structs by hand (ctypes,
  * cgo, JNI) prove that its mirror has the size the library was compiled with (0 for an unknown id). */
-#define MVLT_ABI_VERSION 14
+#define MVLT_ABI_VERSION 15
 int mvlt_version(void);            /* MVLT_ABI_VERSION of the loaded library */
 const char* mvlt_arch(void);       /* "gfx950" */
 enum { MVLT_STRUCT_GEMM = 0, MVLT_STRUCT_LAYERNORM = 1, MVLT_STRUCT_LAYERNORM_BWD = 2, MVLT_STRUCT_LN_REDUCE_ITEM = 3,
        MVLT_STRUCT_ATTN = 4, MVLT_STRUCT_SWIN_WMSA = 5, MVLT_STRUCT_EMBED = 6, MVLT_STRUCT_ATTN_CACHED = 7,
        MVLT_STRUCT_ZERO_ITEM = 8, MVLT_STRUCT_RANGE = 9, MVLT_STRUCT_MLM_MASK = 10, MVLT_STRUCT_GREEDY_STATE = 11, MVLT_STRUCT_SWIN_DBIAS_ITEM = 12,
        MVLT_STRUCT_SAMPLE_STATE = 13, MVLT_STRUCT_SAMPLE_FILTER = 14, MVLT_STRUCT_BEAM_CAND = 15, MVLT_STRUCT_ATTN_CACHED_BEAM = 16,
-       MVLT_STRUCT_HEAD_CE = 17, MVLT_STRUCT_COUNT = 18 };
+       MVLT_STRUCT_HEAD_CE = 17, MVLT_STRUCT_RETRIEVAL_HEAD = 18, MVLT_STRUCT_COUNT = 19 };
 size_t mvlt_sizeof(int struct_id);
 
 /* ------------------------------------------------------------------ GEMM
@@ -267,6 +267,54 @@ typedef struct MvltHeadCE {
 } MvltHeadCE;
 int mvlt_mlm_head_ce(const MvltGemm* p, const MvltHeadCE* h, void* stream);
 size_t mvlt_mlm_head_ce_workspace_bytes(int M, int V);
+
+/* ------------------------------------------------------------------ retrieval (csrc/retrieval.hip)
+ * Scoring head of MVLBertForRetrieval (model.py:444-476) on the packed output of one encoder pass over P (image, caption)
+ * pairs, in ONE launch: the [CLS] gather, BertPooler (dense + tanh, modeling_bert.py:451-463), BertPredictionHeadTransform
+ * (dense + erf-GELU + LayerNorm), Linear(H, 2), the softmax over the two classes and the scatter of the class-1 probability
+ * into a score matrix.  Per pair p < min(P, *p_dev), with x = hidden[row_start[p], :]:
+ *   pooled = round_dtype(tanh(x Wp^T + bp))                     f32 accumulate, ONE rounding to the compute dtype
+ *   t1     = round_dtype(gelu_erf(pooled Wt^T + bt))            f32 accumulate, ONE rounding to the compute dtype
+ *   everything below is f32 and is never rounded to the compute dtype:
+ *   mean = sum_n t1 / H,  var = sum_n (t1 - mean)^2 / H  (two passes),  y_n = (t1_n - mean) rsqrt(var + eps) gamma_n + beta_n
+ *   logit_c = sum_n y_n Wo[c, n] + bo[c]  (c = 0, 1),  scores[out_index[p]] = e_1 / (e_0 + e_1),  e_c = expf(logit_c - max logit)
+ * (the unfused route rounds the pooler product before tanh, t2 = LayerNorm(t1) and the logits to the compute dtype as well.)
+ * A workgroup owns 16 pairs; their gathered rows and the block's `pooled` / `t1` stay in LDS between the two H x H MFMA
+ * products (2 x 16 x (H + 8) elements: 66 KB at H = 1024), the weights stream from L2.  Fixed summation shapes: no atomics,
+ * the same operands give the same bits.  Optional outputs (written when non-NULL, rows p < min(P, *p_dev) only):
+ * pooled [P, H], t1 [P, H] in the compute dtype, logits f32 [P, 2].  Entries of `scores` no out_index names are not touched.
+ * MVLT_ERR_ARG: a NULL required pointer, P < 1, ld_hidden < H, operands the kernel reads in 16-byte vectors (hidden, w_pool,
+ * w_tr, pooled, t1) not 16-byte aligned or ld_hidden not a multiple of 8.  MVLT_ERR_UNSUPPORTED: whatever
+ * mvlt_retrieval_head_supported refuses (bf16 only, H a multiple of 64, H <= 1024); callers then issue the separate launches. */
+typedef struct MvltRetrievalHead {
+    int dtype, P, H;
+    const void* hidden; int64_t ld_hidden;      /* packed encoder output [R, ld_hidden >= H] */
+    const int32_t* row_start;                   /* [P]: the [CLS] row of every pair */
+    const int32_t* p_dev;                       /* optional, DEVICE int: the number of valid pairs (<= P) */
+    const void* w_pool; const float* b_pool;    /* BertPooler.dense [H, H] (compute dtype), [H] */
+    const void* w_tr; const float* b_tr;        /* transform.dense [H, H] (compute dtype), [H] */
+    const float* ln_gamma; const float* ln_beta; float ln_eps;
+    const void* w_out; const float* b_out;      /* final Linear [2, H] (compute dtype), [2] */
+    const int64_t* out_index;                   /* [P]: flat position of pair p in `scores` */
+    float* scores;
+    void* pooled; void* t1; float* logits;      /* optional outputs */
+} MvltRetrievalHead;
+int mvlt_retrieval_head_supported(int dtype, int H);
+int mvlt_retrieval_head(const MvltRetrievalHead* p, void* stream);
+/* Recall ranks of a score matrix (compute_ranks of run_retrieval.py:220-249 without the N x N label matrix and with the ties
+ * decided): scores f32 [Ni, ld >= Nc], pair (i, j) matches iff image_group[i] == caption_group[j] (int64 ids).  Order: the
+ * stable ascending sort reversed -- (score, index) lexicographic, among equal scores the HIGHER index first; NaN is smaller
+ * than every number (and than -inf), -0 equals +0.  For row i let (s*, j*) be the lexicographic maximum over its matching
+ * columns: i2t_rank[i] = the number of columns j with (scores[i, j], j) > (s*, j*), or Nc when the row has no match;
+ * t2i_rank[j] likewise down column j over the rows (Ni without a match).  Two passes per line (maximum, then count), integer
+ * compares on an order-preserving key, no atomics.  Rows: a workgroup per row, threads along it.  Columns: a workgroup per 64
+ * columns, its threads run along a row of `scores` (coalesced) and its four waves take every fourth row.
+ * MVLT_ERR_ARG: NULL pointers, Ni or Nc < 1, ld < Nc. */
+int mvlt_recall_ranks(const float* scores, int64_t ld, int Ni, int Nc, const int64_t* image_group, const int64_t* caption_group,
+                      int32_t* i2t_rank, int32_t* t2i_rank, void* stream);
+/* counts[k] = |{i < n : rank[i] < ks[k]}| for the nk (1 .. 8) thresholds of the HOST array ks (recall@k = counts / n); counts is
+ * a DEVICE int32 [nk], overwritten.  One workgroup, fixed order. */
+int mvlt_recall_counts(const int32_t* rank, int n, const int32_t* ks, int nk, int32_t* counts, void* stream);
 
 /* Decode step (model.py:82-108: 2 new tokens per sample): skinny product with the reduction split over workgroups:
  * acc[s][M][N] (f32, k_splits slabs) = A[:, k-slice s] B[:, k-slice s]^T, M <= 64, both operands k-contiguous, no epilogue;

@@ -24,3 +24,5 @@ from .bert import MVLBert  # noqa: F401
 from .model import (Conv_layer, MVLBertConfig, MVLBertConfigforVQA, MVLBertConfigForImageCaption,  # noqa: F401
                     MVLBertForImageCaption, MVLBertForPretraining, MVLBertForRetrieval, MVLBertForVQA,
                     MVLBertPretrainConfig, MVLBertRetrieval)
+from . import retrieval  # noqa: F401
+from .retrieval import evaluate, recall_ranks, score_all_pairs  # noqa: F401

@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(_HERE, "libmvlt_hip.so")
 
 F32, BF16 = 0, 1
 OK = 0
-ABI_VERSION = 14         # == MVLT_ABI_VERSION of the include/mvlt_hip.h these mirrors were written against
+ABI_VERSION = 15         # == MVLT_ABI_VERSION of the include/mvlt_hip.h these mirrors were written against
 ERRORS = {-1: "MVLT_ERR_ARG", -2: "MVLT_ERR_LAUNCH", -3: "MVLT_ERR_UNSUPPORTED"}
 
 EPI_BIAS, EPI_GELU, EPI_SAVE_PRE, EPI_DROPOUT = 1, 2, 4, 8
@@ -159,6 +159,12 @@ class MvltHeadCE(C.Structure):
     _fields_ = [("labels", vp), ("lse", vp), ("x_label", vp), ("acc", vp), ("workspace", vp), ("workspace_bytes", sz)]
 
 
+class MvltRetrievalHead(C.Structure):
+    _fields_ = [("dtype", i32), ("P", i32), ("H", i32), ("hidden", vp), ("ld_hidden", i64), ("row_start", vp), ("p_dev", vp),
+                ("w_pool", vp), ("b_pool", vp), ("w_tr", vp), ("b_tr", vp), ("ln_gamma", vp), ("ln_beta", vp), ("ln_eps", f32),
+                ("w_out", vp), ("b_out", vp), ("out_index", vp), ("scores", vp), ("pooled", vp), ("t1", vp), ("logits", vp)]
+
+
 # every symbol include/mvlt_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "mvlt_version": (i32, []),
@@ -180,6 +186,10 @@ SYMBOLS = {
     "mvlt_gemm_beam_candidates": (i32, [C.POINTER(MvltGemm), C.POINTER(MvltBeamCand), vp]),
     "mvlt_mlm_head_ce": (i32, [C.POINTER(MvltGemm), C.POINTER(MvltHeadCE), vp]),
     "mvlt_mlm_head_ce_workspace_bytes": (sz, [i32, i32]),
+    "mvlt_retrieval_head_supported": (i32, [i32, i32]),
+    "mvlt_retrieval_head": (i32, [C.POINTER(MvltRetrievalHead), vp]),
+    "mvlt_recall_ranks": (i32, [vp, i64, i32, i32, vp, vp, vp, vp, vp]),
+    "mvlt_recall_counts": (i32, [vp, i32, C.POINTER(i32), i32, vp, vp]),
     "mvlt_gemm_skinny_accum": (i32, [C.POINTER(MvltGemm), vp, i32, vp]),
     "mvlt_layernorm_acc_fwd": (i32, [i32, vp, i32, vp, vp, vp, vp, f32, i32, i32, vp, vp]),
     "mvlt_colsum": (i32, [i32, vp, i64, i32, i32, vp, i32, vp, vp]),
@@ -242,7 +252,7 @@ SYMBOLS = {
 # ctypes mirror of every struct, in the order of the MVLT_STRUCT_* ids of the header
 STRUCTS = [MvltGemm, MvltLayerNorm, MvltLayerNormBwd, MvltLnReduceItem, MvltAttn, MvltSwinWmsa, MvltEmbed,
            MvltAttnCached, MvltZeroItem, MvltRange, MvltMlmMask, MvltGreedyState, MvltSwinDbiasItem,
-           MvltSampleState, MvltSampleFilter, MvltBeamCand, MvltAttnCachedBeam, MvltHeadCE]
+           MvltSampleState, MvltSampleFilter, MvltBeamCand, MvltAttnCachedBeam, MvltHeadCE, MvltRetrievalHead]
 
 _lib = None
 

@@ -103,9 +103,9 @@ class EncoderOutput(tuple):
 
 class _EncFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, token, image_feature, mod, text_idx, mask_ids, image_mask, seq2seq, save, pack=None):
+    def forward(ctx, token, image_feature, mod, text_idx, mask_ids, image_mask, seq2seq, save, pack=None, pool=True):
         with ops.pin_stream():
-            hidden, pooled, saved = mod._forward(image_feature, text_idx, mask_ids, image_mask, seq2seq, save, pack)
+            hidden, pooled, saved = mod._forward(image_feature, text_idx, mask_ids, image_mask, seq2seq, save, pack, pool)
         ctx.mod, ctx.saved = mod, saved
         ctx.set_materialize_grads(False)     # unused pooled output -> None, so the pooler gets no gradient
         if pooled is None:
@@ -118,7 +118,7 @@ class _EncFn(torch.autograd.Function):
         with ops.pin_stream():
             dimg = ctx.mod._backward(ctx.saved, dhidden, dpooled)
         ctx.saved = None
-        return None, dimg, None, None, None, None, None, None, None
+        return None, dimg, None, None, None, None, None, None, None, None
 
 
 class MVLBert(nn.Module):
@@ -208,13 +208,15 @@ class MVLBert(nn.Module):
         return hidden, (pooled if self.pooler is not None else None), pack[3], pack[1]
 
     def forward_autopack(self, text_idx, image_feature, labels=None, seq2seq_mask=False, inputs_ready=None,
-                         want_label_plan=False):
+                         want_label_plan=False, pool=True, return_plan=False):
         """forward_packed with the plan computed ON THE DEVICE from the ids themselves (mvlt_pack_plan): no extra
         argument, no host sync.  Sample b keeps [CLS] img [SEP] and its caption up to the last position that holds a
         non-zero id (or a label); the launch geometry is sized for the dense upper bound B * L and every kernel
         reads the real row count from device memory (MvltGemm.m_dev / MvltLayerNorm.rows_dev).
         Returns (hidden [B*L, H] -- rows beyond the packed total are never written --, pooled [B, H],
-        text_row int64 [B*T]: the packed row of every caption position, the sample's [CLS] row for dropped ones)."""
+        text_row int64 [B*T]: the packed row of every caption position, the sample's [CLS] row for dropped ones).
+        ``pool=False`` skips the pooler (pooled is None: a caller with a head of its own on the [CLS] rows, mvlt_retrieval_head);
+        ``return_plan=True`` appends (row_start int32 [B], total_rows int32 [1]), both on the device."""
         cd = compute_dtype_of(self)
         B, n_img, _ = image_feature.shape
         dev = image_feature.device
@@ -254,11 +256,14 @@ class MVLBert(nn.Module):
             self.__dict__["_mvlt_token"] = tok
         feat = image_feature if image_feature.dtype == cd else image_feature.to(cd)
         hidden, pooled = _EncFn.apply(tok, feat.contiguous(), self, text_idx, text_idx, None, bool(seq2seq_mask),
-                                      torch.is_grad_enabled(), pack)
-        return hidden, (pooled if self.pooler is not None else None), trow
+                                      torch.is_grad_enabled(), pack, bool(pool))
+        pooled = pooled if (self.pooler is not None and pool) else None
+        if return_plan:
+            return hidden, pooled, trow, rs, tot
+        return hidden, pooled, trow
 
     # ------------------------------------------------------------------ engine
-    def _forward(self, feat, text_idx, mask_ids, image_mask, seq2seq, save, pack=None):
+    def _forward(self, feat, text_idx, mask_ids, image_mask, seq2seq, save, pack=None, pool=True):
         cfg = self.config
         cd = feat.dtype
         ar = Arena.of(self, cd)
@@ -329,7 +334,7 @@ class MVLBert(nn.Module):
         pooled = cls = None
         if tail is not None and ar.__dict__.get("_opt_tail") is not None:
             tail.wait_for(None)              # pooler and heads: the last chunk
-        if self.pooler is not None:          # tanh(Linear(h[:,0]))  (modeling_bert.py:451-463)
+        if self.pooler is not None and pool:          # tanh(Linear(h[:,0]))  (modeling_bert.py:451-463)
             cls = hidden[:, 0] if pack is None else x.index_select(0, pack[3])
             pooled = ops.tanh_fwd(ops.gemm(cls, ar.compute(self.pooler.dense.weight),
                                            bias=self.pooler.dense.bias.data))

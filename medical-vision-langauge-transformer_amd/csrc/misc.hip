@@ -874,6 +874,7 @@ extern "C" size_t mvlt_sizeof(int struct_id) {
         case MVLT_STRUCT_BEAM_CAND: return sizeof(MvltBeamCand);
         case MVLT_STRUCT_ATTN_CACHED_BEAM: return sizeof(MvltAttnCachedBeam);
         case MVLT_STRUCT_HEAD_CE: return sizeof(MvltHeadCE);
+        case MVLT_STRUCT_RETRIEVAL_HEAD: return sizeof(MvltRetrievalHead);
         default: return 0;
     }
 }

@@ -639,7 +639,7 @@ class MVLBertForRetrieval(MVLBertPretrainedModel):
 
     def forward(self, image, caption, image_text_label=None, image_mask=None):
         """model.py:444-476: logits = Linear(LN(GELU(dense(pooled)))); softmax prob when no label is given.
-        (The retrieval *drivers* are out of scope; the head reuses the hot path.)"""
+        (The evaluation driver over all pairs is retrieval.score_all_pairs, on encode_images / score_pairs below.)"""
         Arena.of(self, compute_dtype_of(self))
         image_feature = self.conv(image)
         _, pooled = self.MVLBert(text_idx=caption, text_mask=None, image_feature=image_feature, image_mask=image_mask)
@@ -649,6 +649,68 @@ class MVLBertForRetrieval(MVLBertPretrainedModel):
             with torch.no_grad():
                 return ops.softmax_rows(logits.contiguous(), logits.shape[1])
         return logits
+
+    # ---- all-pairs scoring (retrieval.py): the image tower once per image, one packed encoder pass per chunk of pairs
+    def _check_eval(self, what):
+        if self.training:
+            raise ValueError(f"{what} needs eval mode: dropout would make a pair's score depend on the chunk it is scored in")
+
+    @torch.no_grad()
+    def encode_images(self, images, image_chunk=64):
+        """Image features [Ni, n_img, H] in the compute dtype, on the device: the Swin tower over ``images`` ([Ni, 3, S, S], on
+        the host or on the device) in chunks of ``image_chunk``.  Host images are moved chunk by chunk."""
+        self._check_eval("encode_images")
+        Arena.of(self, compute_dtype_of(self))
+        dev = next(self.parameters()).device
+        out = None
+        for i0 in range(0, images.shape[0], int(image_chunk)):
+            chunk = images[i0:i0 + int(image_chunk)]
+            if not chunk.is_cuda:
+                chunk = chunk.to(dev, non_blocking=True)
+            f = self.conv(chunk)
+            if out is None:
+                out = torch.empty((images.shape[0],) + tuple(f.shape[1:]), dtype=f.dtype, device=f.device)
+            out[i0:i0 + f.shape[0]] = f
+        return out
+
+    @torch.no_grad()
+    def score_pairs(self, features, captions, image_index, caption_index, out=None, out_index=None):
+        """f32 [P]: the softmax probability of class 1 of pair p = (image_index[p], caption_index[p]), i.e. what
+        ``forward(image[i:i+1], caption[j:j+1])[0, 1]`` returns.  features: encode_images' output; captions int64 [Nc, T] on the
+        device; the indices int64 [P] on the device.  One encoder pass over the P pairs on packed rows (the padded tail of every
+        caption is dropped, the row count stays on the device), then the scoring head: the separate launches of forward, or with
+        MVLT_RETRIEVAL_HEAD=1 (bf16, a supported width) one launch on the packed [CLS] rows (mvlt_retrieval_head).
+        ``out`` / ``out_index`` (f32 tensor, int64 [P] flat positions in it): scores are written there instead."""
+        self._check_eval("score_pairs")
+        cd = compute_dtype_of(self)
+        ar = Arena.of(self, cd)
+        feat = features.index_select(0, image_index)
+        ids = captions.index_select(0, caption_index)
+        P = ids.shape[0]
+        if out is None:
+            out = torch.empty(P, dtype=torch.float32, device=ids.device)
+            out_index = torch.arange(P, dtype=torch.int64, device=ids.device)
+        H = features.shape[2]
+        fused = _RETRIEVAL_HEAD and ops.retrieval_head_supported(cd, H)
+        hidden, pooled, _, row_start, _ = self.MVLBert.forward_autopack(ids, feat, pool=not fused, return_plan=True)
+        tr, lin = self.final_mlp[0], self.final_mlp[1]
+        if fused:
+            pd = self.MVLBert.pooler.dense
+            ar.refresh_shadow()
+            with ops.pin_stream():
+                ops.retrieval_head(hidden, row_start, ar.compute(pd.weight), pd.bias.data, ar.compute(tr.dense.weight),
+                                   tr.dense.bias.data, tr.LayerNorm.weight.data, tr.LayerNorm.bias.data, tr.LayerNorm.eps,
+                                   ar.compute(lin.weight), lin.bias.data, out_index, out)
+        else:
+            logits = _TransformLinearFn.apply(_token(lin, pooled.device), pooled, tr, lin, False)
+            prob = ops.softmax_rows(logits.contiguous(), logits.shape[1])
+            out.view(-1).index_copy_(0, out_index, prob[:, 1])
+        return out
+
+
+# MVLT_RETRIEVAL_HEAD=1 routes the scoring head of score_pairs through the one-launch mvlt_retrieval_head.  Off by default: the
+# kernel takes 75 us of device time per 512 pairs where the separate launches take 45 (profiles/retrieval.md)
+_RETRIEVAL_HEAD = os.environ.get("MVLT_RETRIEVAL_HEAD", "0") == "1"
 
 
 class _TransformLinearFn(torch.autograd.Function):

@@ -501,6 +501,68 @@ def mlm_head_ce(t2, W, bias, labels, V, rows_dev=None, want_logits=True):
     return acc, lse, x_label, logits
 
 
+def retrieval_head_supported(dtype, H):
+    """True when mvlt_retrieval_head covers this compute dtype and width (bf16, H % 64 == 0, H <= 1024)."""
+    return dtype in _DT and bool(L.lib().mvlt_retrieval_head_supported(_DT[dtype], int(H)))
+
+
+def retrieval_head(hidden, row_start, w_pool, b_pool, w_tr, b_tr, gamma, beta, eps, w_out, b_out, out_index, scores, *,
+                   p_dev=None, want=False):
+    """Scoring head of MVLBertForRetrieval in one launch (mvlt_retrieval_head): hidden [R, H] packed encoder rows, row_start int32
+    [P] (the [CLS] rows), out_index int64 [P] flat positions in ``scores`` (f32, written in place).  ``want=True`` also returns
+    ``(pooled [P, H], t1 [P, H], logits f32 [P, 2])``; p_dev (int32 device scalar): only the first *p_dev pairs exist."""
+    _need_cuda(hidden, row_start, w_pool, w_tr, w_out, out_index, scores)
+    P, H = row_start.numel(), hidden.shape[1]
+    assert hidden.dim() == 2 and hidden.stride(1) == 1 and row_start.dtype == torch.int32 and row_start.is_contiguous()
+    assert out_index.dtype == torch.int64 and out_index.is_contiguous() and out_index.numel() == P
+    assert scores.dtype == torch.float32 and scores.is_contiguous()
+    for w in (w_pool, w_tr, w_out):
+        assert w.dtype == hidden.dtype and w.is_contiguous() and w.shape[1] == H
+    assert w_pool.shape[0] == H and w_tr.shape[0] == H and w_out.shape[0] == 2
+    for b in (b_pool, b_tr, gamma, beta, b_out):
+        assert b.dtype == torch.float32 and b.is_contiguous()
+    h = L.MvltRetrievalHead()
+    h.dtype, h.P, h.H = _dt(hidden), P, H
+    h.hidden, h.ld_hidden, h.row_start, h.p_dev = _p(hidden), _ld(hidden), _p(row_start), _p(p_dev)
+    h.w_pool, h.b_pool, h.w_tr, h.b_tr = _p(w_pool), _p(b_pool), _p(w_tr), _p(b_tr)
+    h.ln_gamma, h.ln_beta, h.ln_eps, h.w_out, h.b_out = _p(gamma), _p(beta), float(eps), _p(w_out), _p(b_out)
+    h.out_index, h.scores = _p(out_index), _p(scores)
+    extra = None
+    if want:
+        extra = (torch.empty((P, H), dtype=hidden.dtype, device=hidden.device),
+                 torch.empty((P, H), dtype=hidden.dtype, device=hidden.device),
+                 torch.empty((P, 2), dtype=torch.float32, device=hidden.device))
+        h.pooled, h.t1, h.logits = _p(extra[0]), _p(extra[1]), _p(extra[2])
+    L.check(L.lib().mvlt_retrieval_head(C.byref(h), _stream()), "mvlt_retrieval_head")
+    return extra
+
+
+def recall_ranks(scores, image_group, caption_group):
+    """(i2t_rank int32 [Ni], t2i_rank int32 [Nc]) of a f32 score matrix [Ni, Nc] (row stride >= Nc); see mvlt_recall_ranks."""
+    _need_cuda(scores, image_group, caption_group)
+    assert scores.dim() == 2 and scores.dtype == torch.float32 and scores.stride(1) == 1
+    Ni, Nc = scores.shape
+    assert image_group.dtype == torch.int64 and image_group.is_contiguous() and image_group.numel() == Ni
+    assert caption_group.dtype == torch.int64 and caption_group.is_contiguous() and caption_group.numel() == Nc
+    ranks = torch.empty(Ni + Nc, dtype=torch.int32, device=scores.device)
+    i2t, t2i = ranks[:Ni], ranks[Ni:]
+    L.check(L.lib().mvlt_recall_ranks(_p(scores), _ld(scores) if Ni > 1 else max(scores.stride(0), Nc), Ni, Nc, _p(image_group),
+                                      _p(caption_group), _p(i2t), _p(t2i), _stream()), "mvlt_recall_ranks")
+    return i2t, t2i
+
+
+def recall_counts(rank, ks, out=None):
+    """int32 [len(ks)] on the device: the number of ranks below each threshold (mvlt_recall_counts)."""
+    _need_cuda(rank)
+    assert rank.dtype == torch.int32 and rank.is_contiguous()
+    nk = len(ks)
+    if out is None:
+        out = torch.empty(nk, dtype=torch.int32, device=rank.device)
+    arr = (C.c_int * nk)(*[int(k) for k in ks])
+    L.check(L.lib().mvlt_recall_counts(_p(rank), rank.numel(), arr, nk, _p(out), _stream()), "mvlt_recall_counts")
+    return out
+
+
 def gumbel_noise(seed, tag, rows, N, device):
     """The noise of gemm_sample as the kernel computes it, f32 [rows, N] (tests)."""
     out = torch.empty((rows, N), dtype=torch.float32, device=device)
