@@ -448,7 +448,8 @@ int mvlt_attn_bwd_ev(const MvltAttn* p, void* stream, void* event);
 enum MvltAttnRoute {
     MVLT_ATTN_ROUTE_UNSUPPORTED = 0,       /* the call answers MVLT_ERR_UNSUPPORTED */
     MVLT_ATTN_ROUTE_SWIN_FWD = 1,          /* attn_fwd_kernel<T, 32, 4, SWIN> */
-    MVLT_ATTN_ROUTE_BERT_FWD_KT5 = 2,      /* attn_fwd_kernel<T, 64, KT>: L <= 80 / 144 / 208 */
+    MVLT_ATTN_ROUTE_BERT_FWD_KT5 = 2,      /* KT = 5 / 9 / 13 key tiles, L <= 80 / 144 / 208: bf16 bert_attn_fwd_kernel<KT, NW> (one
+                                            * query tile per wave), f32 attn_fwd_kernel<float, 64, KT> */
     MVLT_ATTN_ROUTE_BERT_FWD_KT9 = 3,
     MVLT_ATTN_ROUTE_BERT_FWD_KT13 = 4,
     MVLT_ATTN_ROUTE_SWIN_BWD_KS0 = 5,      /* swin_attn_bwd2_kernel (scores once; bf16, no dropout, shift 0 / 3) */
@@ -456,7 +457,8 @@ enum MvltAttnRoute {
     MVLT_ATTN_ROUTE_SWIN_BWD_KS6 = 7,
     MVLT_ATTN_ROUTE_SWIN_BWD_KS12 = 8,
     MVLT_ATTN_ROUTE_SWIN_BWD = 9,          /* attn_bwd_kernel<T, 32, 4, SWIN> (f32, dropout, other shifts) */
-    MVLT_ATTN_ROUTE_BERT_BWD2_NW5 = 10,    /* bert_attn_bwd2_kernel, one launch: bf16, L <= 160 (5 waves) / 192 (6 waves) */
+    MVLT_ATTN_ROUTE_BERT_BWD2_NW5 = 10,    /* bert_attn_bwd2_kernel, one launch: bf16, L <= 160 (NW5: 10 key tiles per launch, one
+                                            * wave each) / 192 (NW6: 12 key tiles) */
     MVLT_ATTN_ROUTE_BERT_BWD2_NW6 = 11,
     MVLT_ATTN_ROUTE_BERT_BWD_SPLIT_KT5 = 12,   /* attn_bwd_split_kernel, two launches through delta_ws */
     MVLT_ATTN_ROUTE_BERT_BWD_SPLIT_KT9 = 13,

@@ -2,7 +2,9 @@
 // single-stream BERT attention, forward and backward (MvltAttn in
 // include/mvlt_hip.h).
 //
-// One workgroup (4 waves) = one (sequence, head).  Q, K, V (and dO) of that
+// One workgroup = one (sequence, head): 4 waves in the generic kernels, one wave
+// per query tile (forward) or key tile (backward) in the bf16 MVLBert kernels
+// (bert_attn_fwd_kernel, bert_attn_bwd2_kernel).  Q, K, V (and dO) of that
 // head are staged once into LDS ([token][d], padded rows); every product is an
 // MFMA over 16x16 tiles and all intermediates (scores, probabilities, dS) live
 // in accumulator registers -- nothing of size L x L ever touches LDS or HBM.
@@ -307,6 +309,136 @@ __global__ __launch_bounds__(256, (SWIN ? 4 : 2)) void attn_fwd_kernel(const Att
                 for (int td = 0; td < TD; ++td)
                     store4f(out + (rs + q) * C + h * HD + 16 * td + 4 * g, o[td]);
             }
+        }
+    }
+}
+
+// ------------------------------------------------------------------ MVLBert forward, one query tile per wave (bf16, hd 64)
+// The forward runs alone on the chip and every workgroup of the step's launch is resident at once, so the launch takes as
+// long as one workgroup's longest wave.  attn_fwd_kernel deals up to KT query tiles to four waves (wave 0 walks three at
+// L = 131), each round a chain of 2 KT score MFMAs, the softmax and dropout of 4 KT elements per lane and 4 ceil(KT / 2)
+// P.V MFMAs with nothing to hide its latencies behind.  Here a workgroup has KT waves and wave w owns query tile w: the
+// per-element arithmetic and its order are those of attn_fwd_kernel.  Only K and V go through LDS; a wave reads the Q
+// fragments of its tile straight from global memory.  The one barrier comes before any wave can leave: a wave without a
+// tile (packed rows: seq_len) stages its share and then falls through.  Registers: at most 96 up to KT = 9 (five waves
+// per SIMD: two workgroups of nine waves per CU, so the 384 workgroups of the step's launch are resident at once), 128 at
+// KT = 13.  Splitting the tiles of a (sequence, head) over two workgroups of five waves (K and V staged twice, three
+// workgroups per CU) was measured slower than attn_fwd_kernel (profiles/attn_waves.md).
+constexpr int BF_LD = 72;                                     // row stride (elements) of the [.][64] images
+template <int KT>
+__global__ __launch_bounds__(64 * KT, (KT <= 10 ? 5 : 4)) void bert_attn_fwd_kernel(const AttnDev p) {
+    using T = bf16_t;
+    using M = Mma<T>;
+    constexpr int KBT = (KT + 1) / 2, ROWS = 32 * KBT, NTH = 64 * KT, IT = (ROWS * 8 + NTH - 1) / NTH;
+    __shared__ __attribute__((aligned(16))) T kimg[ROWS * BF_LD];
+    __shared__ __attribute__((aligned(16))) T vimg[ROWS * BF_LD];
+    __shared__ float kmask[ROWS];
+    const int seq = blockIdx.x, h = blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), g = lane >> 4, c15 = lane & 15;
+    const int C = p.nH * 64;
+    const long rs = seq_row0(p, seq);
+    const int Ls = seq_length(p, seq);
+    const int nt = p.seq_len ? (Ls + 15) >> 4 : p.NT;
+    const T* qg = reinterpret_cast<const T*>(p.qkv) + rs * 3 * C + h * 64;
+    T* out = reinterpret_cast<T*>(p.out) + rs * C + h * 64;
+    const uint32_t rowbase = (uint32_t)(((long)seq * p.nH + h) * p.L);
+
+    // ---- K and V rows of the sequence (zeros beyond it, up to the last 32-row k-block in use): loads first, LDS writes after
+    bf16x8 rk[IT], rv[IT];
+#pragma unroll
+    for (int i = 0; i < IT; ++i) {
+        const int idx = threadIdx.x + NTH * i, rr = idx >> 3, ch = (idx & 7) * 8;
+        rk[i] = zero_vec<T>(); rv[i] = zero_vec<T>();
+        if (rr < Ls) {
+            rk[i] = *reinterpret_cast<const bf16x8*>(qg + rr * 3 * C + C + ch);
+            rv[i] = *reinterpret_cast<const bf16x8*>(qg + rr * 3 * C + 2 * C + ch);
+        }
+    }
+    const int tq = wave, q = 16 * tq + c15;                    // this wave's query tile, this lane's query
+    bf16x8 fq[2];
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+        fq[kb] = q < Ls ? *reinterpret_cast<const bf16x8*>(qg + q * 3 * C + kb * 32 + g * 8) : zero_vec<T>();
+    if (p.mode == MVLT_ATTN_BIDIR) {
+        const int n_img = p.obj_end - 1;
+        for (int k = threadIdx.x; k < p.L; k += NTH) {
+            bool ok = true;
+            if (k >= 1 && k <= n_img) ok = p.image_mask ? p.image_mask[(long)seq * n_img + k - 1] != 0 : true;
+            else if (k > p.obj_end) ok = p.text_ids[(long)seq * p.T + (k - p.obj_end - 1)] > 0;
+            kmask[k] = ok ? 0.0f : -10000.0f;
+        }
+    }
+    const int rows_used = 32 * ((nt + 1) >> 1);
+#pragma unroll
+    for (int i = 0; i < IT; ++i) {
+        const int idx = threadIdx.x + NTH * i, rr = idx >> 3, ch = (idx & 7) * 8;
+        if (rr < rows_used) {
+            *reinterpret_cast<bf16x8*>(kimg + rr * BF_LD + ch) = rk[i];
+            *reinterpret_cast<bf16x8*>(vimg + rr * BF_LD + ch) = rv[i];
+        }
+    }
+    __syncthreads();                                           // the only barrier: every wave of the workgroup is here
+
+    if (tq < nt) {
+        f32x4 acc[KT];
+#pragma unroll
+        for (int t = 0; t < KT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int t = 0; t < KT; ++t) {
+            if (t < nt) {
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb)
+                    M::mma(acc[t], frag_rowmajor<T>(kimg, BF_LD, 16 * t, kb * 32), fq[kb]);
+            }
+        }
+        float mx = NEG_BIG;
+#pragma unroll
+        for (int t = 0; t < KT; ++t)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int k = 16 * t + 4 * g + j;
+                const float v = (t < nt) ? acc[t][j] * p.scale + logit_bias<false>(p, kmask, nullptr, q, k, 0, 0, Ls) : NEG_BIG;
+                acc[t][j] = v;
+                mx = fmaxf(mx, v);
+            }
+        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        float sum = 0.f;
+#pragma unroll
+        for (int t = 0; t < KT; ++t)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { const float e = __expf(acc[t][j] - mx); acc[t][j] = e; sum += e; }
+        sum += __shfl_xor(sum, 16, 64);
+        sum += __shfl_xor(sum, 32, 64);
+        const float inv = 1.0f / sum;
+        if (g == 0 && q < Ls && p.lse) p.lse[((long)seq * p.nH + h) * p.L + q] = mx + __logf(sum);
+        const bool drop = p.drop_thresh != 0;
+#pragma unroll
+        for (int t = 0; t < KT; ++t)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float pr = acc[t][j] * inv;
+                if (drop) {
+                    const int k = 16 * t + 4 * g + j;
+                    const uint32_t idx = (rowbase + (uint32_t)q) * (uint32_t)p.L + (uint32_t)k;                 // the index mod 2^32
+                    pr = rng_keep(p.seed, p.tag, idx, p.drop_thresh) ? pr * p.drop_scale : 0.0f;
+                }
+                acc[t][j] = pr;
+            }
+        f32x4 o[4];
+#pragma unroll
+        for (int td = 0; td < 4; ++td) o[td] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kb = 0; kb < KBT; ++kb) {
+            if (kb * 2 < nt) {
+                const bf16x8 fp = frag_acc<KT>(acc, kb, T());
+#pragma unroll
+                for (int td = 0; td < 4; ++td) M::mma(o[td], frag_tok(vimg, BF_LD, 16 * td, kb), fp);
+            }
+        }
+        if (q < Ls) {
+#pragma unroll
+            for (int td = 0; td < 4; ++td) store4f(out + q * C + 16 * td + 4 * g, o[td]);
         }
     }
 }
@@ -1056,27 +1188,32 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_split_kernel(const AttnDev p)
     }
 }
 
-// ------------------------------------------------------------------ MVLBert backward, scores once (bf16, hd 64, L <= 160)
+// ------------------------------------------------------------------ MVLBert backward, scores once (bf16, hd 64, L <= 192)
 // The two launches above each evaluate scores, probabilities, the dropout decisions and dS -- ~20 vector instructions per
-// element, twice.  Here one workgroup of 5 waves owns a (sequence, head); wave w keeps the key tiles w and w + 5 (their K
-// and V fragments and the dK / dV accumulators stay in registers) and the workgroup walks the queries in blocks of 32:
+// element, twice.  Here one workgroup of NW waves owns a (sequence, head); wave w keeps key tile w (its V fragments and
+// the dK / dV accumulators stay in registers) and the workgroup walks the queries in blocks of 32:
 //   * scores with the QUERIES on the accumulator rows, so P and dS are directly the second MFMA operand of
 //     dV^T += dO^T P and dK^T += Q^T dS (contraction over the block's 32 queries);
 //   * delta_q = rowsum(dO o O) from the forward output (equal to rowsum(P o dP), dropout included), computed while the
 //     operands are staged: every (query tile, key tile) pair is independent of the others;
-//   * dS also goes to LDS as a bf16 image [32 queries][keys]; after a barrier the waves split dQ^T = K^T dS^T by
-//     (feature tile, query tile): complete results, no reduction over the waves that own the keys.
-// LDS: K image (for the transposing read), double-buffered Q / dO / dS block images, lse, delta, key mask: 60 KB.
-// NW waves own 2 NW key tiles: NW = 5 -> up to 160 rows (config #2: L = 131), NW = 6 -> up to 192 rows (config #5: L = 179; round 5).
+//   * dS also goes to LDS as a bf16 image [32 queries][keys]; after the block's barrier waves 0..7 take one (feature tile,
+//     query tile) unit of dQ^T = K^T dS^T each: complete results, no reduction over the waves that own the keys.
+// LDS: K image (for the transposing read), double-buffered Q / dO / dS block images, lse, delta, key mask: 63 KB at NW = 10.
+// One key tile per wave: the kernel runs alone on the chip with every workgroup of the step's launch resident (two per
+// CU), so its time is the latency of one workgroup's chain; a wave that owns one tile has half the chain per query block
+// of a wave that owns two, and twice as many waves hide each other's MFMA / LDS / exp latencies.
+// NW = 10 -> up to 160 rows (config #2: L = 131), NW = 12 -> up to 192 rows (config #5: L = 179).  A wave whose tile lies
+// beyond the sequence computes nothing but reaches every barrier.
 constexpr int AB2_LD = 72;                                    // row stride (elements) of the [.][64] images
 template <int NW> struct Ab2Geom {
-    static constexpr int NT = 64 * NW, ROWS = 32 * NW, LDS = ROWS + 8;          // LDS = row stride of the [32][ROWS] dS image
+    static constexpr int NT = 64 * NW, ROWS = 16 * NW, LDS = ROWS + 8;          // LDS = row stride of the [32][ROWS] dS image
     static constexpr size_t SMEM = (size_t)ROWS * AB2_LD * 2 + 2 * 2 * 32 * AB2_LD * 2 + 2 * 32 * LDS * 2 + 3 * ROWS * 4;
+    static_assert(NW >= 8, "the block staging and the dQ phase use waves 0..7");
 };
 
 template <bool S2S, bool DROP, int NW>
-__global__ __launch_bounds__(64 * NW) void bert_attn_bwd2_kernel(const AttnDev p) {
-    constexpr int AB2_NW = NW, AB2_NT = Ab2Geom<NW>::NT, AB2_ROWS = Ab2Geom<NW>::ROWS, AB2_LDS = Ab2Geom<NW>::LDS;
+__global__ __launch_bounds__(64 * NW, (NW <= 10 ? 5 : 3)) void bert_attn_bwd2_kernel(const AttnDev p) {
+    constexpr int AB2_NT = Ab2Geom<NW>::NT, AB2_ROWS = Ab2Geom<NW>::ROWS, AB2_LDS = Ab2Geom<NW>::LDS;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     using T = bf16_t;
     using M = Mma<T>;
@@ -1100,24 +1237,24 @@ __global__ __launch_bounds__(64 * NW) void bert_attn_bwd2_kernel(const AttnDev p
     T* dqkv = reinterpret_cast<T*>(p.dqkv) + rs * 3 * C + h * 64;
     constexpr float LOG2E_ = 1.4426950408889634f;
 
-    // ---- this wave's key tiles: K and V fragments (rows = keys, k-slots = features) straight from global memory
-    bf16x8 kf[2][2], vf[2][2];
+    // ---- this wave's key tile: V fragments (rows = keys, k-slots = features) straight from global memory; the K fragments
+    //      are read from the K image per block (two LDS reads; holding them too would pass 96 registers)
+    bf16x8 vf[2];
+    {
+        const int row = min(16 * wave + c15, Ls - 1);
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int row = min(16 * (wave + AB2_NW * i) + c15, Ls - 1);
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-            kf[i][kb] = *reinterpret_cast<const bf16x8*>(qg + (long)row * 3 * C + C + kb * 32 + g * 8);
-            vf[i][kb] = *reinterpret_cast<const bf16x8*>(qg + (long)row * 3 * C + 2 * C + kb * 32 + g * 8);
-        }
+        for (int kb = 0; kb < 2; ++kb)
+            vf[kb] = *reinterpret_cast<const bf16x8*>(qg + row * 3 * C + 2 * C + kb * 32 + g * 8);
     }
-    // first query block: this thread's 16-byte chunk of Q and dO (threads 0..255; clamped row)
+    // first query block: one 16-byte chunk per thread, Q rows by waves 0..3 and dO rows by waves 4..7 (clamped row;
+    // offsets from the uniform sequence base fit 32 bits)
     const int srow = (threadIdx.x >> 3) & 31, sch = (threadIdx.x & 7) * 8;
-    bf16x8 gq, gd;
+    const bool stage_q = wave < 4, stages = wave < 8;
+    const T* sg = stage_q ? qg : dg;
+    const int sstride = stage_q ? 3 * C : C;
+    bf16x8 gx;
     auto issue_block = [&](int qb) {
-        const long r = min(32 * qb + srow, Ls - 1);
-        gq = *reinterpret_cast<const bf16x8*>(qg + r * 3 * C + sch);
-        gd = *reinterpret_cast<const bf16x8*>(dg + r * C + sch);
+        if (stages) gx = *reinterpret_cast<const bf16x8*>(sg + min(32 * qb + srow, Ls - 1) * sstride + sch);
     };
     issue_block(0);
 
@@ -1126,7 +1263,7 @@ __global__ __launch_bounds__(64 * NW) void bert_attn_bwd2_kernel(const AttnDev p
     for (int u = threadIdx.x; u < AB2_ROWS * 8; u += AB2_NT) {
         const int row = u >> 3, ch = (u & 7) * 8;
         const bool ok = row < Ls;
-        const long r = min(row, Ls - 1);
+        const int r = min(row, Ls - 1);
         const bf16x8 kv = *reinterpret_cast<const bf16x8*>(qg + r * 3 * C + C + ch);
         const bf16x8 dv = *reinterpret_cast<const bf16x8*>(dg + r * C + ch);
         const bf16x8 ov = *reinterpret_cast<const bf16x8*>(og + r * C + ch);
@@ -1148,82 +1285,89 @@ __global__ __launch_bounds__(64 * NW) void bert_attn_bwd2_kernel(const AttnDev p
         kmask[q] = q < Ls ? (ok ? 0.0f : -10000.0f * LOG2E_) : NEG_BIG;              // a key outside the sequence: P = 0
     }
 
-    f32x4 dk[2][4], dv[2][4];
+    f32x4 dk[4], dv[4];
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int td = 0; td < 4; ++td) { dk[i][td] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[i][td] = dk[i][td]; }
+    for (int td = 0; td < 4; ++td) { dk[td] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[td] = dk[td]; }
     const float sc2 = p.scale * LOG2E_;
-    const bool own0 = wave < nt, own1 = wave + AB2_NW < nt;
+    const bool own = wave < nt;
+    const int k = 16 * wave + c15;                         // this lane's key
+
+    // One barrier per query block.  In program order every wave runs
+    //     scores(qb), stage(qb + 1) | barrier qb | dQ(qb), scores(qb + 1), stage(qb + 2) | barrier qb + 1 | ...
+    // so the dQ phase of a block (eight waves, a chain of MFMAs) runs beside the scores of the next one.  Buffers alternate
+    // with the block's parity: the Q / dO images of block qb + 1 are written after barrier qb - 1, behind which every read of
+    // block qb - 1 lies; scores(qb + 1) overwrites the dS image that dQ(qb - 1) read before barrier qb; dQ(qb) reads what
+    // scores(qb) wrote before barrier qb.
+    auto stage_block = [&](int qb) {
+        if (stages)
+            *reinterpret_cast<bf16x8*>((stage_q ? qblk : dblk) + (qb & 1) * 32 * AB2_LD + srow * AB2_LD + sch) =
+                32 * qb + srow < Ls ? gx : zero_vec<T>();
+    };
+    stage_block(0);
+    issue_block(min(1, nqb - 1));                          // next block in flight (one block only: a harmless re-read)
+    __syncthreads();                                       // block 0, K image, lse, delta and mask staged; dS images zeroed
 
     for (int qb = 0; qb < nqb; ++qb) {
         T* qb_img = qblk + (qb & 1) * 32 * AB2_LD;
         T* db_img = dblk + (qb & 1) * 32 * AB2_LD;
         T* s_img = simg + (qb & 1) * 32 * AB2_LDS;
-        if (threadIdx.x < 256) {
-            const bool ok = 32 * qb + srow < Ls;
-            *reinterpret_cast<bf16x8*>(qb_img + srow * AB2_LD + sch) = ok ? gq : zero_vec<T>();
-            *reinterpret_cast<bf16x8*>(db_img + srow * AB2_LD + sch) = ok ? gd : zero_vec<T>();
-        }
-        __syncthreads();                                   // block staged (first pass: K image, lse, delta, mask too)
-        issue_block(min(qb + 1, nqb - 1));                 // next block in flight (last pass: a harmless re-read)
 
-        // ---- scores of the block against this wave's key tiles: queries on accumulator rows
+        // ---- scores of the block against this wave's key tile: queries on accumulator rows
+        if (own) {
+            f32x4 sc[2], dp[2];
+            const bf16x8 kf[2] = {frag_rowmajor<T>(kimg, AB2_LD, 16 * wave, 0), frag_rowmajor<T>(kimg, AB2_LD, 16 * wave, 32)};
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            if (i == 0 ? own0 : own1) {
-                const int kt = wave + AB2_NW * i;
-                const int k = 16 * kt + c15;
-                f32x4 sc[2], dp[2];
+            for (int qi = 0; qi < 2; ++qi) {
+                sc[qi] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[qi] = sc[qi];
 #pragma unroll
-                for (int qi = 0; qi < 2; ++qi) {
-                    sc[qi] = f32x4{0.f, 0.f, 0.f, 0.f}; dp[qi] = sc[qi];
-#pragma unroll
-                    for (int kb = 0; kb < 2; ++kb) {
-                        M::mma(sc[qi], frag_rowmajor<T>(qb_img, AB2_LD, 16 * qi, kb * 32), kf[i][kb]);
-                        M::mma(dp[qi], frag_rowmajor<T>(db_img, AB2_LD, 16 * qi, kb * 32), vf[i][kb]);
-                    }
-                }
-                const float kb2 = kmask[k];
-#pragma unroll
-                for (int qi = 0; qi < 2; ++qi) {
-                    const int q0 = 32 * qb + 16 * qi + 4 * g;
-                    const f32x4 lq = *reinterpret_cast<const f32x4*>(lse_s + q0);
-                    const f32x4 dl = *reinterpret_cast<const f32x4*>(delta_s + q0);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int q = q0 + j;
-                        float bias = kb2;
-                        if (S2S) bias += (k <= q || k <= p.obj_end) ? 0.0f : -10000.0f * LOG2E_;
-                        const float pr = __builtin_amdgcn_exp2f(fmaf(sc[qi][j], sc2, bias) - lq[j]);
-                        float dpv = dp[qi][j], pd = pr;
-                        if (DROP) {
-                            const bool keep = rng_keep(p.seed, p.tag, (uint32_t)((rowbase + q) * p.L + k), p.drop_thresh);
-                            dpv = keep ? dpv * p.drop_scale : 0.0f;
-                            pd = keep ? pr * p.drop_scale : 0.0f;
-                        }
-                        sc[qi][j] = pr * (dpv - dl[j]);
-                        dp[qi][j] = pd;
-                    }
-                    // dS of this (query tile, key tile) -> the block's dS image [query][key]
-                    T* dst = s_img + (16 * qi + 4 * g) * AB2_LDS + k;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) dst[j * AB2_LDS] = (T)sc[qi][j];
-                }
-                const bf16x8 fs = frag_acc<2>(sc, 0, T());
-                const bf16x8 fp = frag_acc<2>(dp, 0, T());
-#pragma unroll
-                for (int td = 0; td < 4; ++td) {
-                    M::mma(dk[i][td], frag_tok(qb_img, AB2_LD, 16 * td, 0), fs);
-                    M::mma(dv[i][td], frag_tok(db_img, AB2_LD, 16 * td, 0), fp);
+                for (int kb = 0; kb < 2; ++kb) {
+                    M::mma(sc[qi], frag_rowmajor<T>(qb_img, AB2_LD, 16 * qi, kb * 32), kf[kb]);
+                    M::mma(dp[qi], frag_rowmajor<T>(db_img, AB2_LD, 16 * qi, kb * 32), vf[kb]);
                 }
             }
+            const float kb2 = kmask[k];
+#pragma unroll
+            for (int qi = 0; qi < 2; ++qi) {
+                const int q0 = 32 * qb + 16 * qi + 4 * g;
+                const f32x4 lq = *reinterpret_cast<const f32x4*>(lse_s + q0);
+                const f32x4 dl = *reinterpret_cast<const f32x4*>(delta_s + q0);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int q = q0 + j;
+                    float bias = kb2;
+                    if (S2S) bias += (k <= q || k <= p.obj_end) ? 0.0f : -10000.0f * LOG2E_;
+                    const float pr = __builtin_amdgcn_exp2f(fmaf(sc[qi][j], sc2, bias) - lq[j]);
+                    float dpv = dp[qi][j], pd = pr;
+                    if (DROP) {
+                        const bool keep = rng_keep(p.seed, p.tag, ((uint32_t)rowbase + (uint32_t)q) * (uint32_t)p.L + (uint32_t)k, p.drop_thresh);   // the index mod 2^32
+                        dpv = keep ? dpv * p.drop_scale : 0.0f;
+                        pd = keep ? pr * p.drop_scale : 0.0f;
+                    }
+                    sc[qi][j] = pr * (dpv - dl[j]);
+                    dp[qi][j] = pd;
+                }
+                // dS of this (query tile, key tile) -> the block's dS image [query][key]
+                T* dst = s_img + (16 * qi + 4 * g) * AB2_LDS + k;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) dst[j * AB2_LDS] = (T)sc[qi][j];
+            }
+            const bf16x8 fs = frag_acc<2>(sc, 0, T());
+            const bf16x8 fp = frag_acc<2>(dp, 0, T());
+#pragma unroll
+            for (int td = 0; td < 4; ++td) {
+                M::mma(dk[td], frag_tok(qb_img, AB2_LD, 16 * td, 0), fs);
+                M::mma(dv[td], frag_tok(db_img, AB2_LD, 16 * td, 0), fp);
+            }
         }
-        __syncthreads();                                   // the block's dS image is complete
+        if (qb + 1 < nqb) {
+            stage_block(qb + 1);
+            issue_block(min(qb + 2, nqb - 1));
+        }
+        __syncthreads();                                   // the block's dS image is complete, the next block is staged
 
-        // ---- dQ^T[feature tile, query tile] = sum over key blocks of K^T dS^T: units dealt to the waves
-        for (int u = wave; u < 8; u += AB2_NW) {
-            const int dt = u & 3, qi = u >> 2;
+        // ---- dQ^T[feature tile, query tile] = sum over key blocks of K^T dS^T: one unit per wave, waves 0..7
+        if (wave < 8) {
+            const int dt = wave & 3, qi = wave >> 2;
             f32x4 dq = f32x4{0.f, 0.f, 0.f, 0.f};
             const T* srow_p = s_img + (16 * qi + c15) * AB2_LDS + 4 * g;
             for (int kb = 0; kb < nqb; ++kb) {
@@ -1235,19 +1379,15 @@ __global__ __launch_bounds__(64 * NW) void bert_attn_bwd2_kernel(const AttnDev p
                 M::mma(dq, frag_tok(kimg, AB2_LD, 16 * dt, kb), fb);
             }
             const int q = 32 * qb + 16 * qi + c15;
-            if (q < Ls) store4f(dqkv + (long)q * 3 * C + 16 * dt + 4 * g, dq * p.scale);
+            if (q < Ls) store4f(dqkv + q * 3 * C + 16 * dt + 4 * g, dq * p.scale);
         }
     }
+    if (k < Ls) {
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int k = 16 * (wave + AB2_NW * i) + c15;
-        if (k < Ls) {
-#pragma unroll
-            for (int td = 0; td < 4; ++td) {
-                T* ob = dqkv + (long)k * 3 * C + 16 * td + 4 * g;
-                store4f(ob + C, dk[i][td] * p.scale);
-                store4f(ob + 2 * C, dv[i][td]);
-            }
+        for (int td = 0; td < 4; ++td) {
+            T* ob = dqkv + k * 3 * C + 16 * td + 4 * g;
+            store4f(ob + C, dk[td] * p.scale);
+            store4f(ob + 2 * C, dv[td]);
         }
     }
 }
@@ -1286,6 +1426,15 @@ static int launch_bert_bwd2(const AttnDev& d, hipStream_t s) {
     return MVLT_OK;
 }
 
+// bf16 MVLBert forward: one workgroup of KT waves per (sequence, head), one query tile per wave
+template <int KT>
+static int launch_bert_fwd(const AttnDev& d, hipStream_t s) {
+    static_assert(KT * 64 <= 1024, "workgroup size");
+    hipLaunchKernelGGL((bert_attn_fwd_kernel<KT>), dim3(d.nseq, d.nH), dim3(64 * KT), 0, s, d);
+    MVLT_LAUNCH_CHECK();
+    return MVLT_OK;
+}
+
 template <typename T, int HD, int KT>
 int launch_split(const AttnDev& d, int dtype, hipStream_t s) {
     const size_t sh = smem_bytes_split(dtype, d.rows_alloc, d.ld);
@@ -1319,6 +1468,8 @@ int launch(const AttnDev& d, bool bwd, int dtype, hipStream_t s) {
         auto k = attn_bwd_kernel<T, HD, KT, SWIN>;
         if (sh > 64 * 1024) hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
         ATTN_LAUNCH_LAST(k, grid, dim3(256), sh, s, d);
+    } else if constexpr (!SWIN && sizeof(T) == 2) {
+        return MVLT_ERR_UNSUPPORTED;                    // the bf16 MVLBert forward is bert_attn_fwd_kernel (launch_bert_fwd)
     } else {
         auto k = attn_fwd_kernel<T, HD, KT, SWIN>;
         if (sh > 64 * 1024) hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
@@ -1420,13 +1571,20 @@ int dispatch(AttnDev d, bool bwd, int dtype, hipStream_t s) {
     case MVLT_ATTN_ROUTE_SWIN_BWD_KS3:
     case MVLT_ATTN_ROUTE_SWIN_BWD_KS6:
     case MVLT_ATTN_ROUTE_SWIN_BWD_KS12: return launch_swin_bwd2(d, s);
+    // bf16 forward: one query tile per wave (bert_attn_fwd_kernel); f32 and the generic backward: attn_fwd / attn_bwd_kernel
     case MVLT_ATTN_ROUTE_BERT_FWD_KT5:
-    case MVLT_ATTN_ROUTE_BERT_BWD_KT5: return launch<T, 64, 5, false>(d, bwd, dtype, s);
+        if constexpr (sizeof(T) == 2) return launch_bert_fwd<5>(d, s);
+        else return launch<T, 64, 5, false>(d, false, dtype, s);
     case MVLT_ATTN_ROUTE_BERT_FWD_KT9:
-    case MVLT_ATTN_ROUTE_BERT_BWD_KT9: return launch<T, 64, 9, false>(d, bwd, dtype, s);
-    case MVLT_ATTN_ROUTE_BERT_FWD_KT13: return launch<T, 64, 13, false>(d, false, dtype, s);
-    case MVLT_ATTN_ROUTE_BERT_BWD2_NW5: return launch_bert_bwd2<5>(d, s);
-    case MVLT_ATTN_ROUTE_BERT_BWD2_NW6: return launch_bert_bwd2<6>(d, s);
+        if constexpr (sizeof(T) == 2) return launch_bert_fwd<9>(d, s);
+        else return launch<T, 64, 9, false>(d, false, dtype, s);
+    case MVLT_ATTN_ROUTE_BERT_FWD_KT13:
+        if constexpr (sizeof(T) == 2) return launch_bert_fwd<13>(d, s);
+        else return launch<T, 64, 13, false>(d, false, dtype, s);
+    case MVLT_ATTN_ROUTE_BERT_BWD_KT5: return launch<T, 64, 5, false>(d, true, dtype, s);
+    case MVLT_ATTN_ROUTE_BERT_BWD_KT9: return launch<T, 64, 9, false>(d, true, dtype, s);
+    case MVLT_ATTN_ROUTE_BERT_BWD2_NW5: return launch_bert_bwd2<10>(d, s);
+    case MVLT_ATTN_ROUTE_BERT_BWD2_NW6: return launch_bert_bwd2<12>(d, s);
     case MVLT_ATTN_ROUTE_BERT_BWD_SPLIT_KT5: return launch_split<T, 64, 5>(d, dtype, s);
     case MVLT_ATTN_ROUTE_BERT_BWD_SPLIT_KT9: return launch_split<T, 64, 9>(d, dtype, s);
     case MVLT_ATTN_ROUTE_BERT_BWD_SPLIT_KT13: return launch_split<T, 64, 13>(d, dtype, s);

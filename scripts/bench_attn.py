@@ -1,5 +1,8 @@
 """Attention kernel microbenchmark at the pre-training step's shapes (B=32, bf16).
-    python scripts/bench_attn.py [stage]      # stage 0..3: only that Swin stage (for counter runs), no BERT part"""
+    python scripts/bench_attn.py [stage]      # stage 0..3: only that Swin stage (for counter runs), no BERT part
+    python scripts/bench_attn.py bert         # only the MVLBert part: dense L = 131, then the step's packed rows
+The packed lines draw the caption lengths of bench.py's batch (synthetic_batch(32, 80, seed 1234)) and lay the sequences
+out back to back (row_start / seq_len) as the step does, so the figure is taken at the shape the step runs."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -20,9 +23,10 @@ def timeit(f, n=20):
 
 
 tot = 0.0
-ONLY = int(sys.argv[1]) if len(sys.argv) > 1 else None
+BERT_ONLY = len(sys.argv) > 1 and sys.argv[1] == "bert"
+ONLY = int(sys.argv[1]) if len(sys.argv) > 1 and not BERT_ONLY else None
 for st, (res, C, nH, nblk) in enumerate([(56, 96, 3, 2), (28, 192, 6, 2), (14, 384, 12, 18), (7, 768, 24, 2)]):
-    if ONLY is not None and st != ONLY:
+    if BERT_ONLY or (ONLY is not None and st != ONLY):
         continue
     nW = (res // 7) ** 2
     nseq = B * nW
@@ -43,17 +47,29 @@ for st, (res, C, nH, nblk) in enumerate([(56, 96, 3, 2), (28, 192, 6, 2), (14, 3
 if ONLY is not None:
     sys.exit(0)
 Lq, H, nH = 131, 768, 12
-qkv = (torch.randn(B * Lq, 3 * H, device="cuda") * 0.5).to(dt)
-ids = torch.randint(1000, 30000, (B, 80), device="cuda"); ids[:, 50:] = 0
-for mode, name in ((L.ATTN_BIDIR, "bidir"), (L.ATTN_SEQ2SEQ, "seq2seq")):
-    for pd in (0.0, 0.1):
-        kw = dict(text_ids=ids, obj_end=50, dropout=(pd, 1234, 3))
-        out, lse = ops.attn_fwd(qkv, mode, B, Lq, nH, 64, 0.125, **kw)
-        dout = torch.randn_like(out)
-        tf = timeit(lambda: ops.attn_fwd(qkv, mode, B, Lq, nH, 64, 0.125, **kw))
-        tb = timeit(lambda: ops.attn_bwd(dout, qkv, out, lse, mode, B, Lq, nH, 64, 0.125, **kw))
-        byt_f = qkv.numel() * 2 + out.numel() * 2
-        byt_b = 2 * qkv.numel() * 2 + 2 * out.numel() * 2
-        if pd > 0 and mode == L.ATTN_BIDIR: tot += (tf + tb) * 12
-        print(f"bert {name} p={pd}: fwd {tf:6.1f} us ({byt_f/tf/1e6:5.2f} TB/s)  bwd {tb:6.1f} us ({byt_b/tb/1e6:5.2f} TB/s)  x12", flush=True)
-print(f"TOTAL per step (standalone): {tot/1e3:.2f} ms")
+from mvlt_amd.train import synthetic_batch
+ids_step = synthetic_batch(B, 80, "cpu", 1234)[1]                    # bench.py's batch (rank 0)
+seq_len = (51 + (ids_step != 0).sum(1)).to(torch.int32)
+row_start = (torch.cumsum(seq_len, 0) - seq_len).to(torch.int32)
+rows_packed = int(seq_len.sum())
+ids_dense = torch.randint(1000, 30000, (B, 80)); ids_dense[:, 50:] = 0
+for layout in ("dense", "packed"):
+    packed = layout == "packed"
+    rows = rows_packed if packed else B * Lq
+    ids = (ids_step if packed else ids_dense).cuda()
+    qkv = (torch.randn(rows, 3 * H, device="cuda") * 0.5).to(dt)
+    for mode, name in ((L.ATTN_BIDIR, "bidir"), (L.ATTN_SEQ2SEQ, "seq2seq")):
+        for pd in (0.0, 0.1):
+            kw = dict(text_ids=ids, obj_end=50, dropout=(pd, 1234, 3))
+            if packed:
+                kw["pack"] = (row_start.cuda(), seq_len.cuda(), rows)
+            out, lse = ops.attn_fwd(qkv, mode, B, Lq, nH, 64, 0.125, **kw)
+            dout = torch.randn_like(out)
+            tf = timeit(lambda: ops.attn_fwd(qkv, mode, B, Lq, nH, 64, 0.125, **kw))
+            tb = timeit(lambda: ops.attn_bwd(dout, qkv, out, lse, mode, B, Lq, nH, 64, 0.125, **kw))
+            byt_f = qkv.numel() * 2 + out.numel() * 2
+            byt_b = 2 * qkv.numel() * 2 + 2 * out.numel() * 2
+            if pd > 0 and mode == L.ATTN_BIDIR and not packed: tot += (tf + tb) * 12
+            print(f"bert {layout} ({rows} rows) {name} p={pd}: fwd {tf:6.1f} us ({byt_f/tf/1e6:5.2f} TB/s)  bwd {tb:6.1f} us ({byt_b/tb/1e6:5.2f} TB/s)  x12", flush=True)
+if not BERT_ONLY:
+    print(f"TOTAL per step (standalone, dense BERT rows): {tot/1e3:.2f} ms")
