@@ -36,14 +36,14 @@ enum { MVLT_OK = 0, MVLT_ERR_ARG = -1, MVLT_ERR_LAUNCH = -2, MVLT_ERR_UNSUPPORTE
  * signature; a binding compiles / hard-codes the value it was written against and compares it with what the
  * loaded library returns.  mvlt_sizeof(MVLT_STRUCT_*) lets a binding that mirrors the structs by hand (ctypes,
  * cgo, JNI) prove that its mirror has the size the library was compiled with (0 for an unknown id). */
-#define MVLT_ABI_VERSION 15
+#define MVLT_ABI_VERSION 16
 int mvlt_version(void);            /* MVLT_ABI_VERSION of the loaded library */
 const char* mvlt_arch(void);       /* "gfx950" */
 enum { MVLT_STRUCT_GEMM = 0, MVLT_STRUCT_LAYERNORM = 1, MVLT_STRUCT_LAYERNORM_BWD = 2, MVLT_STRUCT_LN_REDUCE_ITEM = 3,
        MVLT_STRUCT_ATTN = 4, MVLT_STRUCT_SWIN_WMSA = 5, MVLT_STRUCT_EMBED = 6, MVLT_STRUCT_ATTN_CACHED = 7,
        MVLT_STRUCT_ZERO_ITEM = 8, MVLT_STRUCT_RANGE = 9, MVLT_STRUCT_MLM_MASK = 10, MVLT_STRUCT_GREEDY_STATE = 11, MVLT_STRUCT_SWIN_DBIAS_ITEM = 12,
        MVLT_STRUCT_SAMPLE_STATE = 13, MVLT_STRUCT_SAMPLE_FILTER = 14, MVLT_STRUCT_BEAM_CAND = 15, MVLT_STRUCT_ATTN_CACHED_BEAM = 16,
-       MVLT_STRUCT_HEAD_CE = 17, MVLT_STRUCT_RETRIEVAL_HEAD = 18, MVLT_STRUCT_COUNT = 19 };
+       MVLT_STRUCT_HEAD_CE = 17, MVLT_STRUCT_RETRIEVAL_HEAD = 18, MVLT_STRUCT_BEAM_STEP = 19, MVLT_STRUCT_COUNT = 20 };
 size_t mvlt_sizeof(int struct_id);
 
 /* ------------------------------------------------------------------ GEMM
@@ -701,6 +701,53 @@ typedef struct MvltAttnCachedBeam {
     const int32_t* slot; int64_t ld_slot;       /* [rows, ld_slot] */
 } MvltAttnCachedBeam;
 int mvlt_attn_cached_beam(const MvltAttnCachedBeam* p, void* stream);
+/* The hypothesis bookkeeping of one beam-search token on the device (csrc/beam.hip): HF transformers 4.16
+ * BeamSearchScorer.process (decode.BeamScorer.process: length_penalty 1, early stopping off) and the three lines beam_search runs
+ * behind it (model.py:722-763: beam scores / tokens / indices, the input_ids update, the beam reorder -- here of the slot table of
+ * mvlt_attn_cached_beam, not of the cache).  One launch, a workgroup per sample; the walk over the candidates runs on one lane in
+ * f64 (the host scorer works in Python floats on f32 inputs, and no comparison may differ by a rounding), the row copies on all
+ * lanes; no float atomics.  rows = G * num_beams; c = *col, the number of tokens generated so far; L = max(1, c) (at step 0 the
+ * host scorer is handed [[mask_id]]: a hypothesis that finishes there is the one-token list [mask_id]).
+ * Inputs: the sorted candidate lists of mvlt_gemm_beam_candidates (cand_score f32, cand_beam, cand_tok, [G, n_cand]); src_beams =
+ * the num_beams of the candidate call that made them (1 at step 0, where one row per sample was scored; cand_beam is clamped
+ * into [0, src_beams)); the parent row of a candidate is g * num_beams + cand_beam.
+ * State per sample, caller-allocated: the pool of finished hypotheses in insertion order -- hyp_score f64 [G, num_beams + 1],
+ * hyp_len [G, num_beams + 1], hyp_tokens [G, num_beams + 1, max_length] (entries at and beyond a hypothesis' length are
+ * unspecified) --, n_hyp [G], worst f64 [G] (the caller starts it at 1e9), done [G]; the live sequences seq [rows, max_length];
+ * the slot table [rows, ld_slot >= max_length].  Counters: col (int64), past (int32, optional), ticket (int32, zeroed once by the
+ * caller), alive int64 [max_length] (zeroed when a decode starts).
+ * Sample g, when done[g] == 0: walk the candidates in rank order until num_beams are kept.  A candidate with token eos_id (has_eos
+ * != 0 only) at rank < num_beams offers its parent's sequence (the first L tokens of seq[parent] as they were BEFORE this launch;
+ * [mask_id] at c = 0) to the pool with score (double)cand_score / (double)L; at rank >= num_beams it is skipped.  The offer is
+ * taken when n_hyp < num_beams or score > worst; the pool then grows, and beyond num_beams entries the one with the lowest (score,
+ * insertion index) leaves (later entries move up) and worst = the second lowest score, else worst = min(score, worst).  Any other
+ * candidate is kept as the next live beam k = 0, 1, ...:  beam_scores[g nb + k] = its score (bit for bit), new_ids[g nb + k] =
+ * [token, mask_id] (int64 [rows, 2]), beam_idx[g nb + k] = its parent row (int32, global), seq[g nb + k] = seq[parent] with the
+ * token at column c, slot[g nb + k] = slot[parent] with column c = k (the position the next forward appends lives in the row's own
+ * cache row; that forward reads only columns below c, so writing the column before it equals writing it after).  Both
+ * permutations are in place, staged through LDS.  Then done[g] |= n_hyp >= num_beams && worst >= (double)cand_score[g, 0] / L.
+ * (At most num_beams of 2 num_beams distinct (beam, token) candidates carry EOS, so num_beams are always kept; with fewer
+ * candidates the missing beams are filled with pad_id, score 0, parent 0.)
+ * Sample g, when done[g] != 0: beam_scores 0, new_ids [pad_id, mask_id], beam_idx 0; its seq, slot rows and pool stay untouched.
+ * Every launch: alive[c] is raised to 1 by every sample that is still not done; cand_log (optional, int32 [max_length, G, 3,
+ * n_cand]) receives the consumed lists at index c (score bits, beam, token); the last workgroup to arrive advances *col and *past
+ * by one and re-arms the ticket.  A launch that finds c outside [0, max_length) writes nothing and advances nothing.
+ * Refusals (nothing launched, nothing written): MVLT_ERR_ARG for a NULL b or required pointer (all but past and cand_log), G < 1,
+ * num_beams < 1, n_cand < num_beams, src_beams not in {1, num_beams}, max_length < 1, ld_slot < max_length; then
+ * MVLT_ERR_UNSUPPORTED for num_beams > 8, n_cand > 16, num_beams * max_length > 8192 (the staging area in LDS). */
+typedef struct MvltBeamStep {
+    int32_t G, num_beams, n_cand, src_beams, max_length, has_eos;
+    int64_t eos_id, pad_id, mask_id;
+    const float* cand_score; const int32_t* cand_beam; const int32_t* cand_tok;        /* [G, n_cand] */
+    double* hyp_score; int32_t* hyp_len; int32_t* hyp_tokens;                          /* the pool */
+    int32_t* n_hyp; double* worst; int32_t* done;                                      /* [G] */
+    int32_t* seq;                                                                      /* [rows, max_length] */
+    int32_t* slot; int64_t ld_slot;                                                    /* [rows, ld_slot] */
+    int64_t* col; int32_t* past; int32_t* ticket; int64_t* alive;
+    float* beam_scores; int64_t* new_ids; int32_t* beam_idx;                           /* outputs: [rows], [rows, 2], [rows] */
+    int32_t* cand_log;                                                                 /* optional */
+} MvltBeamStep;
+int mvlt_beam_step(const MvltBeamStep* b, void* stream);
 /* argmax over V of logits [rows, ld] -> int64 ids (greedy_search, model.py:896-900) */
 int mvlt_argmax(int dtype, const void* logits, int64_t ld, int rows, int V, int64_t* out, void* stream);
 

@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(_HERE, "libmvlt_hip.so")
 
 F32, BF16 = 0, 1
 OK = 0
-ABI_VERSION = 15         # == MVLT_ABI_VERSION of the include/mvlt_hip.h these mirrors were written against
+ABI_VERSION = 16         # == MVLT_ABI_VERSION of the include/mvlt_hip.h these mirrors were written against
 ERRORS = {-1: "MVLT_ERR_ARG", -2: "MVLT_ERR_LAUNCH", -3: "MVLT_ERR_UNSUPPORTED"}
 
 EPI_BIAS, EPI_GELU, EPI_SAVE_PRE, EPI_DROPOUT = 1, 2, 4, 8
@@ -155,6 +155,15 @@ class MvltAttnCachedBeam(C.Structure):
         ("num_beams", i32), ("prefix", i32), ("slot", vp), ("ld_slot", i64)]
 
 
+class MvltBeamStep(C.Structure):
+    _fields_ = [("G", i32), ("num_beams", i32), ("n_cand", i32), ("src_beams", i32), ("max_length", i32), ("has_eos", i32),
+                ("eos_id", i64), ("pad_id", i64), ("mask_id", i64),
+                ("cand_score", vp), ("cand_beam", vp), ("cand_tok", vp), ("hyp_score", vp), ("hyp_len", vp), ("hyp_tokens", vp),
+                ("n_hyp", vp), ("worst", vp), ("done", vp), ("seq", vp), ("slot", vp), ("ld_slot", i64),
+                ("col", vp), ("past", vp), ("ticket", vp), ("alive", vp), ("beam_scores", vp), ("new_ids", vp), ("beam_idx", vp),
+                ("cand_log", vp)]
+
+
 class MvltHeadCE(C.Structure):
     _fields_ = [("labels", vp), ("lse", vp), ("x_label", vp), ("acc", vp), ("workspace", vp), ("workspace_bytes", sz)]
 
@@ -242,6 +251,7 @@ SYMBOLS = {
     "mvlt_adamw": (i32, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp]),
     "mvlt_attn_cached": (i32, [C.POINTER(MvltAttnCached), vp]),
     "mvlt_attn_cached_beam": (i32, [C.POINTER(MvltAttnCachedBeam), vp]),
+    "mvlt_beam_step": (i32, [C.POINTER(MvltBeamStep), vp]),
     "mvlt_argmax": (i32, [i32, vp, i64, i32, i32, vp, vp]),
     "mvlt_zero_batch": (i32, [C.POINTER(MvltZeroItem), i32, vp]),
     "mvlt_prefetch": (i32, [C.POINTER(MvltRange), i32, vp]),
@@ -252,7 +262,7 @@ SYMBOLS = {
 # ctypes mirror of every struct, in the order of the MVLT_STRUCT_* ids of the header
 STRUCTS = [MvltGemm, MvltLayerNorm, MvltLayerNormBwd, MvltLnReduceItem, MvltAttn, MvltSwinWmsa, MvltEmbed,
            MvltAttnCached, MvltZeroItem, MvltRange, MvltMlmMask, MvltGreedyState, MvltSwinDbiasItem,
-           MvltSampleState, MvltSampleFilter, MvltBeamCand, MvltAttnCachedBeam, MvltHeadCE, MvltRetrievalHead]
+           MvltSampleState, MvltSampleFilter, MvltBeamCand, MvltAttnCachedBeam, MvltHeadCE, MvltRetrievalHead, MvltBeamStep]
 
 _lib = None
 

@@ -875,6 +875,7 @@ extern "C" size_t mvlt_sizeof(int struct_id) {
         case MVLT_STRUCT_ATTN_CACHED_BEAM: return sizeof(MvltAttnCachedBeam);
         case MVLT_STRUCT_HEAD_CE: return sizeof(MvltHeadCE);
         case MVLT_STRUCT_RETRIEVAL_HEAD: return sizeof(MvltRetrievalHead);
+        case MVLT_STRUCT_BEAM_STEP: return sizeof(MvltBeamStep);
         default: return 0;
     }
 }

@@ -23,7 +23,10 @@ from ``mvlt_gemm_beam_candidates`` (head + log-softmax + beam score + top 2*beam
 the cache is never reordered -- ``mvlt_attn_cached_beam`` follows an int32 table [rows, max_length] that names, per hypothesis and
 generated position, the cache row (within the sample) that holds it; the image prefix is stored once per sample.
 ``MVLT_BEAM_FUSED=0`` (and any other shape) takes the route of the reference: bf16 logits, ``log_softmax``, ``topk`` and a
-gather of every layer's cache by beam index per token.
+gather of every layer's cache by beam index per token.  ``MVLT_BEAM_DEVICE=1`` / ``beam_search(device_scorer=True)`` (off by default,
+shapes of the fused route): the scorer's ``process`` runs on the device too (``mvlt_beam_step`` on a ``BeamDeviceState``), so the loop
+has no per-token read-back and is replayed as one HIP graph per token (``_BeamGraph``; ``MVLT_DECODE_GRAPH=0``: eager); ``finalize``
+stays on the host, after one read-back.
 """
 from __future__ import annotations
 
@@ -492,13 +495,220 @@ class BeamScorer:
         return out
 
 
+class BeamDeviceState:
+    """Everything ``mvlt_beam_step`` reads and writes for B samples x num_beams beams, in static device buffers, with the prepared
+    ``L.MvltBeamStep`` (``self.struct``).  The pool, the flags, the live sequences and the beam scores share ONE allocation, so
+    ``finalize`` needs one read-back.  ``cand`` is the int32 [3, B, 2 * num_beams] buffer ``ops.gemm_beam_candidates(out=...)``
+    fills; ``cand_log`` (int32 [max_length, B, 3, 2 * num_beams] or None) receives the lists every step consumed."""
+
+    def __init__(self, B, num_beams, max_length, pad, eos, mask_id, device, cand_log=None):
+        nb, ml, rows, nc = num_beams, max_length, B * num_beams, 2 * num_beams
+        self.B, self.nb, self.max_length, self.pad, self.eos = B, nb, ml, pad, eos
+        layout, off = {}, 0
+        for name, shape, dt in (("hyp_score", (B, nb + 1), torch.float64), ("worst", (B,), torch.float64), ("col", (1,), torch.int64),
+                                ("beam_scores", (rows,), torch.float32), ("hyp_len", (B, nb + 1), torch.int32),
+                                ("hyp_tokens", (B, nb + 1, ml), torch.int32), ("n_hyp", (B,), torch.int32), ("done", (B,), torch.int32),
+                                ("seq", (rows, ml), torch.int32)):
+            n = 1
+            for s in shape:
+                n *= s
+            layout[name] = (off, n * dt.itemsize, shape, dt)
+            off += (n * dt.itemsize + 15) // 16 * 16
+        self._layout = layout
+        self.flat = torch.zeros(off, dtype=torch.uint8, device=device)
+        for name, v in self._views(self.flat).items():
+            setattr(self, name, v)
+        self.slot = torch.zeros((rows, ml), dtype=torch.int32, device=device)
+        self.past = torch.zeros(1, dtype=torch.int32, device=device)
+        self.ticket = torch.zeros(1, dtype=torch.int32, device=device)
+        self.alive = torch.zeros(ml, dtype=torch.int64, device=device)
+        self.new_ids = torch.full((rows, 2), mask_id, dtype=torch.int64, device=device)
+        self.beam_idx = torch.zeros(rows, dtype=torch.int32, device=device)
+        self.cand = torch.zeros((3, B, nc), dtype=torch.int32, device=device)
+        self.cand_log = cand_log
+        if cand_log is not None:
+            assert cand_log.dtype == torch.int32 and cand_log.is_contiguous() and tuple(cand_log.shape) == (ml, B, 3, nc)
+        st = self.struct = L.MvltBeamStep()
+        st.G, st.num_beams, st.n_cand, st.src_beams, st.max_length = B, nb, nc, nb, ml
+        st.has_eos, st.eos_id, st.pad_id, st.mask_id = int(eos is not None), (eos if eos is not None else -1), pad, mask_id
+        st.cand_score, st.cand_beam, st.cand_tok = self.cand[0].data_ptr(), self.cand[1].data_ptr(), self.cand[2].data_ptr()
+        for name in ("hyp_score", "hyp_len", "hyp_tokens", "n_hyp", "worst", "done", "seq", "slot", "col", "past", "ticket", "alive",
+                     "beam_scores", "new_ids", "beam_idx"):
+            setattr(st, name, getattr(self, name).data_ptr())
+        st.ld_slot = ml
+        st.cand_log = cand_log.data_ptr() if cand_log is not None else None
+        self.reset(0)
+
+    def _views(self, flat):
+        return {name: flat[off:off + nbytes].view(dt).view(shape) for name, (off, nbytes, shape, dt) in self._layout.items()}
+
+    def reset(self, past):
+        """Start of a decode: empty pools (worst = 1e9), nothing done, column 0, the cache position of the step before the first
+        cached forward (the first beam step advances it)."""
+        self.flat.zero_()
+        self.worst.fill_(1e9)
+        self.slot.zero_(); self.alive.zero_(); self.ticket.zero_()
+        self.past.fill_(past)
+
+    def scorer(self):
+        """One read-back -> (BeamScorer holding the pools and done flags, live sequences as lists, beam scores as a list)."""
+        host = self._views(self.flat.cpu())
+        nb = self.nb
+        sc = BeamScorer(self.B, nb)
+        for b, hyp in enumerate(sc.hyps):
+            sc.done[b] = bool(host["done"][b])
+            hyp.worst_score = float(host["worst"][b])
+            hyp.beams = [(float(host["hyp_score"][b, i]), host["hyp_tokens"][b, i, :int(host["hyp_len"][b, i])].tolist())
+                         for i in range(int(host["n_hyp"][b]))]
+        n = max(1, min(int(host["col"][0]), self.max_length))
+        return sc, host["seq"][:, :n].tolist(), host["beam_scores"].tolist()
+
+
+def _beam_device_step0(model, ar, feat, st, kc, vc, W, bias, ws=None):
+    """Step 0 of the device-scorer routes, eager: the full forward on the B images, the prefix into the first cache row of every
+    sample, the candidates of the one scored row per sample into ``st.cand``.  Returns the prefix length."""
+    mv, cfg = model.MVLBert, model.config
+    B, n_img, H = feat.shape
+    nH = cfg.num_attention_heads
+    nb = st.nb
+    mask_col = st.new_ids[::nb, 1:2].contiguous()
+    hidden, _, saved = mv._forward(feat, mask_col, mask_col, None, True, True)
+    L0 = n_img + 3
+    for i in range(len(mv.encoder.layer)):
+        _fill_cache_from_qkv(saved["layers"][i][1], B, L0, nH, H // nH, kc[i][::nb], vc[i][::nb], L0 - 1)
+    del saved
+    st.reset(L0 - 2)
+    _, _, t2, _, _ = model.MLM_head_seq2seq._transform(ar, hidden[:, -1].contiguous(), False)
+    ops.gemm_beam_candidates(t2, W, bias, torch.zeros(B, dtype=torch.float32, device=feat.device), 1, 2 * nb, out=st.cand, ws=ws)
+    return L0 - 1
+
+
+class _BeamGraph:
+    """Beam search per token as one replayed HIP graph, after the model of ``_GreedyGraph``: [mvlt_beam_step, the 2-token cached
+    forward over the B * beams rows, the head transform, mvlt_gemm_beam_candidates], captured on one stream (no parallel
+    branches).  All state is static: ``BeamDeviceState``, the caches, the hidden rows, the logits workspace.  The captured
+    beam step carries src_beams = num_beams also for the lists of step 0 (their beam index is 0, which both values admit)."""
+
+    def __reduce__(self):                 # captured graphs do not survive pickling: rebuilt on the next call
+        return (_no_graph, ())
+
+    def __init__(self, model, B, nb, n_img, max_length, cd, pad, eos, mask_id, key, log):
+        mv, cfg = model.MVLBert, model.config
+        dev = next(model.parameters()).device
+        H, nH = cfg.hidden_size, cfg.num_attention_heads
+        nl = len(mv.encoder.layer)
+        rows = B * nb
+        self.key, self.model, self.B, self.nb, self.cd, self.graph = key, model, B, nb, cd, None
+        self.prefix = n_img + 2
+        cap = n_img + 2 + max_length + 1
+        self.kc = [torch.zeros((rows, nH, cap, H // nH), dtype=cd, device=dev) for _ in range(nl)]
+        self.vc = [torch.zeros((rows, nH, cap, H // nH), dtype=cd, device=dev) for _ in range(nl)]
+        self.log = torch.zeros((max_length, B, 3, 2 * nb), dtype=torch.int32, device=dev) if log else None
+        self.st = BeamDeviceState(B, nb, max_length, pad, eos, mask_id, dev, cand_log=self.log)
+        self.hfull = torch.zeros((rows * 2, H), dtype=cd, device=dev)
+        self.hlast = self.hfull.view(rows, 2, H)[:, 1]
+        V = model.MLM_head_seq2seq.predictions.decoder.out_features
+        self.ws = torch.empty(rows * ((V + 3) // 4 * 4), dtype=torch.float32, device=dev)
+
+    def step(self):
+        ops.beam_step(self.st.struct)
+
+    def forward2(self):
+        """The cached forward of [kept token, MASK] at positions past, past + 1, then the candidates of the next token."""
+        model, st = self.model, self.st
+        mv = model.MVLBert
+        ar = Arena.of(model, self.cd)
+        hd = model.MLM_head_seq2seq
+        H = mv.config.hidden_size
+        x = _embed_new(mv, st.new_ids, st.past, self.cd).view(self.B * self.nb * 2, H)
+        _layers_cached(mv, ar, x, self.kc, self.vc, st.past, 2, out_last=self.hfull, beam=(self.nb, self.prefix, st.slot))
+        _, _, t2, _, _ = hd._transform(ar, self.hlast, False)
+        ops.gemm_beam_candidates(t2, ar.compute(hd.predictions.decoder.weight), hd.predictions.decoder.bias.data, st.beam_scores,
+                                 self.nb, 2 * self.nb, out=st.cand, ws=self.ws)
+
+    def capture(self):
+        self.st.reset(self.prefix - 1)          # a valid position for the warm-up and the capture pass: both really run
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side), ops.on_stream(side, "graph"):     # warm-up outside the capture (allocator, lazy state)
+            self.step(); self.forward2()
+        torch.cuda.current_stream().wait_stream(side)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            with ops.on_stream(torch.cuda.current_stream(), "graph"):
+                self.step(); self.forward2()
+        self.graph = g
+
+
+def _beam_device_search(model, feat, nb, max_length, pad, eos, mask_id, cd, cand_log):
+    """beam_search with the scorer on the device (``mvlt_beam_step``): no per-token read-back.  MVLT_DECODE_GRAPH=0: the eager
+    loop; otherwise one graph replay per token (``_BeamGraph``).  The host reads ``alive`` back every 8 tokens; the steps that run
+    past the point where every sample is done change no pool (done samples are skipped).  ``finalize`` is the host scorer's."""
+    mv, cfg = model.MVLBert, model.config
+    B, n_img, H = feat.shape
+    nH = cfg.num_attention_heads
+    nl = len(mv.encoder.layer)
+    dev = feat.device
+    ar = Arena.of(model, cd)
+    head = model.MLM_head_seq2seq
+    W, bias = ar.compute(head.predictions.decoder.weight), head.predictions.decoder.bias.data
+    rows = B * nb
+
+    def all_done(t):          # after the beam step of token t: one host sync per 8 tokens
+        return eos is not None and (t + 1) % 8 == 0 and 0 in st.alive[t - 7:t + 1].tolist()
+
+    if os.environ.get("MVLT_DECODE_GRAPH", "1") == "1":
+        key = (B, nb, n_img, max_length, cd, pad, eos, mask_id, ar.flat.data_ptr(), dev.index, cand_log is not None)
+        bg = model.__dict__.get("_mvlt_beam_graph")
+        if bg is None or bg.key != key:
+            bg = _BeamGraph(model, B, nb, n_img, max_length, cd, pad, eos, mask_id, key, cand_log is not None)
+            bg.capture()
+            model.__dict__["_mvlt_beam_graph"] = bg
+        st = bg.st
+        if bg.log is not None:
+            bg.log.zero_()
+        _beam_device_step0(model, ar, feat, st, bg.kc, bg.vc, W, bias, ws=bg.ws)
+        for t in range(max_length - 1):
+            bg.graph.replay()                    # the beam step of token t, then the forward and candidates of token t + 1
+            if all_done(t):
+                break
+        else:
+            bg.step()                            # last token: the beam step only
+        if cand_log is not None:
+            cand_log.copy_(bg.log)
+    else:
+        st = BeamDeviceState(B, nb, max_length, pad, eos, mask_id, dev, cand_log=cand_log)
+        cap = n_img + 2 + max_length + 1
+        kc = [torch.zeros((rows, nH, cap, H // nH), dtype=cd, device=dev) for _ in range(nl)]
+        vc = [torch.zeros((rows, nH, cap, H // nH), dtype=cd, device=dev) for _ in range(nl)]
+        prefix = _beam_device_step0(model, ar, feat, st, kc, vc, W, bias)
+        for t in range(max_length):
+            ops.beam_step(st.struct, 1 if t == 0 else nb)
+            if t + 1 >= max_length or all_done(t):
+                break
+            x = _embed_new(mv, st.new_ids, st.past, cd).view(rows * 2, H)
+            h = _layers_cached(mv, ar, x, kc, vc, st.past, 2, beam=(nb, prefix, st.slot)).view(rows, 2, H)
+            _, _, t2, _, _ = head._transform(ar, h[:, -1].contiguous(), False)
+            ops.gemm_beam_candidates(t2, W, bias, st.beam_scores, nb, 2 * nb, out=st.cand)
+    scorer, seqs, scores = st.scorer()
+    out = scorer.finalize(seqs, scores, cfg.max_length, pad, eos)
+    return torch.tensor(out, dtype=torch.int64, device=dev)
+
+
+BEAM_STEP_STAGE = 8192          # num_beams * max_length int32 words mvlt_beam_step stages in LDS (csrc/beam.hip BS_STAGE)
+
+
 @torch.no_grad()
 def beam_search(model, image_feature, num_beams, learning_strategy='unilm', max_length=None, pad_token_id=None,
-                eos_token_id=None):
+                eos_token_id=None, device_scorer=None, cand_log=None):
     """``MVLBertForImageCaption.beam_search`` (model.py:636-816) with the KV cache: scores = log_softmax(logits) +
     beam score, top 2*beams over (beam, token), scorer bookkeeping, cache rows gathered by ``beam_idx`` (:758-763).
     Step 0 runs once per image (all beams of a sample start identical and only beam 0 carries score 0, :681-682),
-    then 2-token cached steps over the B*beams rows.  Returns the sequences [B, <= max_length] (:795-815)."""
+    then 2-token cached steps over the B*beams rows.  Returns the sequences [B, <= max_length] (:795-815).
+    ``device_scorer`` (None: MVLT_BEAM_DEVICE=1 switches it on; default off): the scorer bookkeeping runs on the device
+    (``mvlt_beam_step``) and the loop has no per-token read-back; as a replayed graph unless MVLT_DECODE_GRAPH=0.  Same shapes as
+    the fused route (anything else decodes as without the switch), same sequences.  ``cand_log`` (device-scorer route only): an
+    int32 device tensor [max_length, B, 3, 2 * num_beams] that receives the candidate lists every step consumed."""
     if learning_strategy != 'unilm':
         raise NotImplementedError("only learning_strategy='unilm' is coherent with the KV cache (SURVEY.md 3.3)")
     mv, cfg = model.MVLBert, model.config
@@ -535,6 +745,10 @@ def beam_search(model, image_feature, num_beams, learning_strategy='unilm', max_
     cur_len = 0
     # the fused route needs what its two entry points need; everything else decodes the way the reference does
     fused = os.environ.get("MVLT_BEAM_FUSED", "1") != "0" and 1 <= nb <= ops.BEAM_MAX_BEAMS and 2 * nb <= ops.BEAM_MAX_CAND and hd == 64
+    if device_scorer is None:
+        device_scorer = os.environ.get("MVLT_BEAM_DEVICE", "0") == "1"
+    if device_scorer and fused and nb * max_length <= BEAM_STEP_STAGE:
+        return _beam_device_search(model, feat, nb, max_length, pad, eos, mask_id, cd, cand_log)
     if fused:
         W, bias = ar.compute(head.predictions.decoder.weight), head.predictions.decoder.bias.data
 

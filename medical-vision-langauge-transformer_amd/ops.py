@@ -451,24 +451,41 @@ def gemm_sample_filtered_step(A, W, bias, state, top_k=0, top_p=1.0):
 BEAM_MAX_BEAMS, BEAM_MAX_CAND = 8, 16          # limits of mvlt_gemm_beam_candidates (csrc/skinny.hip BEAM_MAXB / BEAM_MAXC)
 
 
-def gemm_beam_candidates(A, W, bias, beam_scores, num_beams, n_cand, want_lse=False):
+def gemm_beam_candidates(A, W, bias, beam_scores, num_beams, n_cand, want_lse=False, out=None, ws=None):
     """The candidate step of beam search without the logits round trip (mvlt_gemm_beam_candidates): A: [G * num_beams, K] (the
     beams of sample g are the rows g * num_beams .. + num_beams; any number of rows), W: [N, K], beam_scores f32 [G * num_beams].
     Per sample the n_cand largest log_softmax(A @ W^T + bias) + beam score over (beam, token), sorted descending, ties by the
     lower beam * N + token.  Returns ``(out, lse)``: ``out`` one int32 tensor [3, G, n_cand] -- out[0] viewed as f32 holds the
-    scores, out[1] the beams, out[2] the tokens (one buffer: one read-back) -- and lse f32 [rows] or None."""
+    scores, out[1] the beams, out[2] the tokens (one buffer: one read-back) -- and lse f32 [rows] or None.
+    ``out`` / ``ws``: caller-owned buffers for the lists (int32 [3, G, n_cand], contiguous) and the f32 logits workspace (at least
+    rows * ldx elements, ldx = N rounded up to 4) -- a replayed decode loop reads the lists at a fixed address."""
     p, M, N = _head_gemm(A, W, bias)
     assert beam_scores.dtype == torch.float32 and beam_scores.is_contiguous() and beam_scores.numel() == M
     ldx = (N + 3) // 4 * 4
-    ws = workspace("beam_logits", M * ldx * 4, A.device)
+    if ws is None:
+        ws = workspace("beam_logits", M * ldx * 4, A.device)
+    else:
+        assert ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() >= M * ldx
     G = M // max(int(num_beams), 1)
-    out = torch.empty((3, G, n_cand), dtype=torch.int32, device=A.device)
+    if out is None:
+        out = torch.empty((3, G, n_cand), dtype=torch.int32, device=A.device)
+    else:
+        assert out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (3, G, n_cand)
     lse = torch.empty(M, dtype=torch.float32, device=A.device) if want_lse else None
     c = L.MvltBeamCand()
     c.num_beams, c.n_cand, c.beam_scores, c.x, c.ldx = int(num_beams), int(n_cand), _p(beam_scores), _p(ws), ldx
     c.cand_score, c.cand_beam, c.cand_tok, c.lse = _p(out[0]), _p(out[1]), _p(out[2]), (_p(lse) if want_lse else None)
     L.check(L.lib().mvlt_gemm_beam_candidates(C.byref(p), C.byref(c), _stream()), "mvlt_gemm_beam_candidates")
     return out, lse
+
+
+def beam_step(state, src_beams=None):
+    """One token of beam-search bookkeeping on the device (mvlt_beam_step): consumes the candidate lists ``state`` points at and
+    advances pool, live sequences, slot table, beam scores, next ids and the counters.  ``state``: a prepared ``L.MvltBeamStep``
+    (decode.BeamDeviceState); ``src_beams``: the num_beams of the candidate call that made the lists (1 at step 0), when given."""
+    if src_beams is not None:
+        state.src_beams = int(src_beams)
+    L.check(L.lib().mvlt_beam_step(C.byref(state), _stream()), "mvlt_beam_step")
 
 
 def mlm_head_ce(t2, W, bias, labels, V, rows_dev=None, want_logits=True):

@@ -5,7 +5,10 @@ existed), interleaved round by round in ONE process after a warm-up round.  Prin
 batch with min / max over the rounds, then -- from one extra instrumented run per route -- the per-token split: head (device time
 from the head product to the candidates), attention (the cached-attention launches), cache gather (plain route only), scorer
 (host time in BeamScorer.process) and host sync (host time waiting in the read-back).
-BATCHES ("8,32"), ROUNDS (5), MAXLEN (150), BEAMS (5)."""
+Two more routes run in the same rounds: the device scorer (mvlt_beam_step, MVLT_BEAM_DEVICE=1) as an eager loop
+(MVLT_DECODE_GRAPH=0, "device") and as one replayed HIP graph per token ("graph"); both are compared with the fused host-scorer
+route.  A replayed graph makes no per-token Python calls, so it has no per-token split.
+BATCHES ("8,32"), ROUNDS (5), MAXLEN (150), BEAMS (5), ROUTES ("fused,plain,device,graph")."""
 import os, statistics, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -17,11 +20,15 @@ BEAMS, MAXLEN, ROUNDS = int(os.environ.get("BEAMS", 5)), int(os.environ.get("MAX
 cfg = M.MVLBertConfigForImageCaption(); cfg.max_length = MAXLEN; cfg.eos_token_id = None
 tok = type("Tok", (), {"mask_token_id": 103, "sep_token_id": 102})()
 model = M.MVLBertForImageCaption(cfg, tokenizer=tok).cuda().eval()
-ROUTES = (("fused", "1"), ("plain", "0"))
+ENV = {"fused": dict(MVLT_BEAM_FUSED="1", MVLT_BEAM_DEVICE="0", MVLT_DECODE_GRAPH="1"),
+       "plain": dict(MVLT_BEAM_FUSED="0", MVLT_BEAM_DEVICE="0", MVLT_DECODE_GRAPH="1"),
+       "device": dict(MVLT_BEAM_FUSED="1", MVLT_BEAM_DEVICE="1", MVLT_DECODE_GRAPH="0"),
+       "graph": dict(MVLT_BEAM_FUSED="1", MVLT_BEAM_DEVICE="1", MVLT_DECODE_GRAPH="1")}
+ROUTES = tuple((n, n) for n in os.environ.get("ROUTES", "fused,plain,device,graph").split(","))
 
 
 def run(img, flag):
-    os.environ["MVLT_BEAM_FUSED"] = flag
+    os.environ.update(ENV[flag])
     torch.cuda.synchronize(); t = time.time()
     out = model(img, None, BEAMS, "unilm")
     torch.cuda.synchronize()
@@ -103,15 +110,27 @@ for B in [int(b) for b in os.environ.get("BATCHES", "8,32").split(",")]:
             ms, outs[name] = run(img, flag)
             if r:
                 times[name].append(ms)
-    same = outs["fused"].shape == outs["plain"].shape and bool((outs["fused"] == outs["plain"]).all())
+    def same_as_fused(name):
+        return outs["fused"].shape == outs[name].shape and bool((outs["fused"] == outs[name]).all())
+
     for name, _ in ROUTES:
         v = times[name]
         print(f"B={B:3d} beams={BEAMS} {name:6s} median {statistics.median(v):8.2f} ms/batch  (min {min(v):.2f} max {max(v):.2f}, spread "
               f"{max(v) - min(v):.2f} over {len(v)} rounds)", flush=True)
-    gain = statistics.median(times["plain"]) - statistics.median(times["fused"])
-    print(f"B={B:3d} fused is {gain:+.2f} ms/batch ({1e3 * gain / MAXLEN:+.1f} us/token) against a plain-route spread of "
-          f"{max(times['plain']) - min(times['plain']):.2f} ms; same sequences on both routes (random weights, bf16 against f32 logits): {same}", flush=True)
+    if "plain" in times and "fused" in times:
+        gain = statistics.median(times["plain"]) - statistics.median(times["fused"])
+        print(f"B={B:3d} fused is {gain:+.2f} ms/batch ({1e3 * gain / MAXLEN:+.1f} us/token) against a plain-route spread of "
+              f"{max(times['plain']) - min(times['plain']):.2f} ms; same sequences on both routes (random weights, bf16 against f32 logits): "
+              f"{same_as_fused('plain')}", flush=True)
+    for name in ("device", "graph"):          # the device scorer against the host scorer on the same (fused) kernels
+        if name in times and "fused" in times:
+            gain = statistics.median(times["fused"]) - statistics.median(times[name])
+            print(f"B={B:3d} {name} is {gain:+.2f} ms/batch ({1e3 * gain / MAXLEN:+.1f} us/token) against fused, whose spread is "
+                  f"{max(times['fused']) - min(times['fused']):.2f} ms ({name}: {max(times[name]) - min(times[name]):.2f}); same sequences as "
+                  f"fused: {same_as_fused(name)}", flush=True)
     for name, flag in ROUTES:
+        if name == "graph":
+            continue
         with Split() as sp:
             run(img, flag)
         print(f"B={B:3d} {name:6s} per token [us]: " + "  ".join(f"{k} {v:7.1f}" for k, v in sp.per_token().items()), flush=True)
