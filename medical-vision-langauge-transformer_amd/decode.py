@@ -3,11 +3,13 @@ decode loop (``modules/model.py:82-108`` cache branch of ``get_embedding``,
 ``:577-604`` prepare_inputs, ``:826-984`` greedy_search, ``:890-894`` cache trim).
 
 Layout: one preallocated cache ``[layers][B, nH, cap, hd]`` per K and V
-(cap = n_img + 2 + max_length + 1).  Step 0 runs the full seq2seq forward over
-``[CLS] img [SEP] [MASK]``; every later step feeds the 2 tokens
+(``_alloc_cache``: the prefix, max_length tokens and the [MASK] slot).  Step 0 (``_step0``) runs the full seq2seq forward
+over ``[CLS] img [SEP] [MASK]``; every later step (``_step2``) feeds the 2 tokens
 ``[last_token, [MASK]]`` at positions ``past, past+1`` (type 0), appends their
 K/V in place and attends causally (``mvlt_attn_cached``).  "Trimming the [MASK]
 slot" (model.py:890-894) is just ``past += 1``: the next step overwrites it.
+Every search is argument resolution (``_resolve``), a route (``_greedy_route`` / ``_beam_route``: pure functions of the call's
+arguments and of the switches ``_env`` reads per call) and one loop per route; the two replayed graphs share ``_DecodeGraph``.
 Greedy mode replays one captured HIP graph per token (``_GreedyGraph``: position,
 output column and finished flags live on the device; ``MVLT_DECODE_GRAPH=0`` selects
 the eager loop).  'sample' mode (B <= 64) is the same graph with the Gumbel-max pick of ``mvlt_gemm_sample_step`` as
@@ -48,6 +50,63 @@ _SPLITS = (2, 4)      # reduction splits of (attention output, FFN-out) projecti
 # noise tags of sampled decoding: output column c draws with tag SAMPLE_TAG0 + c (the seed is the call's own, so the range
 # cannot meet the dropout / DropPath / MLM-mask tags of a training step, which hash their step seed)
 SAMPLE_TAG0 = 0x53000000
+BEAM_STEP_STAGE = 8192          # num_beams * max_length int32 words mvlt_beam_step stages in LDS (csrc/beam.hip BS_STAGE)
+# The reference asks the device "all finished?" after every token (model.py:954), which serialises host and GPU.  Finished
+# sequences only emit PAD, so running a few steps past the end changes nothing that is kept: the flag of every column is
+# recorded on the device, read back every SYNC_EVERY columns, and the outputs are cut where the reference would have stopped.
+SYNC_EVERY = 8
+
+
+# ----------------------------------------------------------------------------- host-only rules (tests/test_decode_host_cpu.py)
+def _env():
+    """The switches of this module, read per call: (graph_on, fused_on, device_on)."""
+    env = os.environ.get
+    return env("MVLT_DECODE_GRAPH", "1") == "1", env("MVLT_BEAM_FUSED", "1") != "0", env("MVLT_BEAM_DEVICE", "0") == "1"
+
+
+def _greedy_route(sample_mode, B, filtered, graph_on):
+    """(loop, pick) of greedy_search, a pure function of its arguments.  ('graph', 'greedy' | 'sample'): the replayed graph, whose
+    fused head holds the whole batch in one 64-row tile (a filter only swaps the sampled head's entry point).  ('eager', pick):
+    'gemm_argmax' / 'gemm_sample' (the fused picks, B <= 64), 'filtered' (the fused filtered pick, rows in chunks of 64),
+    'argmax' / 'multinomial' (B > 64: torch on the logits)."""
+    if filtered and sample_mode != 'sample':
+        raise ValueError("top_k / top_p filter the sampled pick: they need sample_mode='sample'")
+    if sample_mode not in ('greedy', 'sample'):
+        raise ValueError("sample mode error!")
+    if graph_on and B <= 64:
+        return 'graph', sample_mode
+    if filtered:
+        return 'eager', 'filtered'
+    if sample_mode == 'greedy':
+        return 'eager', 'gemm_argmax' if B <= 64 else 'argmax'
+    return 'eager', 'gemm_sample' if B <= 64 else 'multinomial'
+
+
+def _beam_route(num_beams, head_dim, max_length, fused_on, device_scorer, device_on=False):
+    """'plain' | 'fused' | 'device', a pure function of its arguments (``device_scorer`` None: ``device_on``, the env value).
+    The fused route needs what its two entry points need, the device scorer also the LDS stage of mvlt_beam_step; everything
+    else decodes the way the reference does."""
+    fused = fused_on and 1 <= num_beams <= ops.BEAM_MAX_BEAMS and 2 * num_beams <= ops.BEAM_MAX_CAND and head_dim == 64
+    if device_scorer is None:
+        device_scorer = device_on
+    if device_scorer and fused and num_beams * max_length <= BEAM_STEP_STAGE:
+        return 'device'
+    return 'fused' if fused else 'plain'
+
+
+def _sync_due(eos, done, last=None):
+    """Read the finished flags back after ``done`` columns?  One host sync per SYNC_EVERY tokens (and at column ``last``)."""
+    return eos is not None and (done % SYNC_EVERY == 0 or done == last)
+
+
+def _cut(alive, n_cols):
+    """(n_out, n_scores) of a greedy decode that produced ``n_cols`` columns; ``alive``: the per-column "a sample is unfinished"
+    flags as a list (empty without eos).  The reference's per-token check stops at the first 0, before appending that step's
+    score."""
+    if 0 in alive:
+        n_out = alive.index(0) + 1
+        return n_out, n_out - 1
+    return n_cols, n_cols
 
 
 def _layers_cached(mv, ar, x, kc, vc, past, n_new, out_last=None, beam=None):
@@ -110,6 +169,59 @@ def _fill_cache_from_qkv(qkv, B, Lq, nH, hd, kc, vc, keep):
     vc[:, :, :keep].copy_(v5[:, :keep, 2].permute(0, 2, 1, 3))
 
 
+def _resolve(model, image_feature, max_length, pad_token_id, eos_token_id):
+    """The arguments every search starts from: (compute dtype, arena (refreshed), max_length, pad, eos, mask_id, feat)."""
+    cfg = model.config
+    cd = compute_dtype_of(model)
+    ar = Arena.of(model, cd)
+    ar.refresh_shadow()
+    max_length = max_length if max_length is not None else cfg.max_length
+    pad = pad_token_id if pad_token_id is not None else cfg.pad_token_id
+    eos = eos_token_id if eos_token_id is not None else cfg.eos_token_id
+    tok = getattr(model, "tokenizer", None)
+    mask_id = tok.mask_token_id if tok is not None else cfg.mask_token_id
+    return cd, ar, max_length, pad, eos, mask_id, image_feature.to(cd).contiguous()
+
+
+def _alloc_cache(model, rows, n_img, max_length, cd, device):
+    """Zeroed K and V caches ``[layers][rows, nH, cap, hd]``: the prefix, max_length tokens and the [MASK] slot."""
+    cfg = model.config
+    nH = cfg.num_attention_heads
+    shape = (rows, nH, n_img + 2 + max_length + 1, cfg.hidden_size // nH)
+    nl = len(model.MVLBert.encoder.layer)
+    return ([torch.zeros(shape, dtype=cd, device=device) for _ in range(nl)],
+            [torch.zeros(shape, dtype=cd, device=device) for _ in range(nl)])
+
+
+def _step0(mv, feat, mask_col, kc, vc, stride=1):
+    """Step 0: [CLS] img [SEP] [MASK], the full seq2seq forward on the B images (model.py:110-160), eager.  The prefix goes
+    into every ``stride``-th row of the caller's caches, in place (stride = num_beams: the first row of every sample).
+    Returns (last hidden row [B, H], a view; prefix length = the position the first 2-token step writes)."""
+    B, n_img, H = feat.shape
+    nH = mv.config.num_attention_heads
+    hidden, _, saved = mv._forward(feat, mask_col, mask_col, None, True, True)
+    L0 = n_img + 3
+    for i in range(len(mv.encoder.layer)):
+        _fill_cache_from_qkv(saved["layers"][i][1], B, L0, nH, H // nH, kc[i][::stride], vc[i][::stride], L0 - 1)
+    return hidden[:, -1], L0 - 1
+
+
+def _step2(mv, ar, new_ids, past, kc, vc, cd, out_last=None, beam=None):
+    """The cached forward of the 2 tokens ``new_ids`` [rows, 2] = [last token, MASK] at positions past, past + 1
+    (model.py:82-108, :587-591) -> the [MASK] rows [rows, H], a view of the [rows * 2, H] output (``out_last`` when given)."""
+    rows, H = new_ids.shape[0], mv.config.hidden_size
+    x = _embed_new(mv, new_ids, past, cd).view(rows * 2, H)
+    return _layers_cached(mv, ar, x, kc, vc, past, 2, out_last=out_last, beam=beam).view(rows, 2, H)[:, -1]
+
+
+def _head(model, ar, hlast):
+    """(t2, W, bias): the head transform of ``hlast`` and the decoder's operands.  ``hlast`` is read where it lies: the graphs
+    hand over the [MASK] rows of their [rows, 2, H] buffer at row stride 2 H."""
+    hd = model.MLM_head_seq2seq
+    _, _, t2, _, _ = hd._transform(ar, hlast, False)
+    return t2, ar.compute(hd.predictions.decoder.weight), hd.predictions.decoder.bias.data
+
+
 @torch.no_grad()
 def cached_forward(mv, text_idx, image_feature, past_key_values, seq2seq_mask):
     """``MVLBert.forward(..., past_key_values=..., use_cache=True)`` API (model.py:59-62):
@@ -151,7 +263,38 @@ def _no_graph():
     return None
 
 
-class _GreedyGraph:
+class _DecodeGraph:
+    """What the replayed decode graphs share.  A subclass keeps its static device buffers and ``body()``, the per-token work; the
+    graph of a model lives in ``model.__dict__[slot]`` until a call arrives with another ``key``."""
+
+    def __reduce__(self):                 # captured graphs do not survive pickling: rebuilt on the next call
+        return (_no_graph, ())
+
+    @classmethod
+    def of(cls, model, slot, key, *args):
+        g = model.__dict__.get(slot)
+        if g is None or g.key != key:
+            g = cls(model, key, *args)
+            g.capture()
+            model.__dict__[slot] = g
+        return g
+
+    def capture(self):
+        # scratch buffers (split-K workspace) used inside the graph get their own tag: the captured pointers must
+        # never be freed or handed to other work by a later, larger request on the main stream
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side), ops.on_stream(side, "graph"):     # warm-up outside the capture (allocator, lazy state)
+            self.body()
+        torch.cuda.current_stream().wait_stream(side)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            with ops.on_stream(torch.cuda.current_stream(), "graph"):
+                self.body()
+        self.graph = g
+
+
+class _GreedyGraph(_DecodeGraph):
     """The whole per-token work of greedy decoding -- last-row MLM head + argmax + [END]/PAD bookkeeping + the
     2-token cached forward -- captured ONCE as a HIP graph and replayed per token.  Everything a replay needs
     lives in static device buffers: the cache position (``past``: read by the embedding and attention kernels
@@ -159,18 +302,11 @@ class _GreedyGraph:
     unfinished flags, and the [B, max_length] output matrices.  The host only replays and, every 8 tokens, reads
     the all-finished flags back."""
 
-    def __reduce__(self):                 # captured graphs do not survive pickling: rebuilt on the next call
-        return (_no_graph, ())
-
-    def __init__(self, model, B, n_img, max_length, cd, pad, eos, mask_id, key, mode='greedy', temperature=1.0, top_k=0, top_p=1.0):
-        mv, cfg = model.MVLBert, model.config
+    def __init__(self, model, key, B, n_img, max_length, cd, pad, eos, mask_id, mode='greedy', temperature=1.0, top_k=0, top_p=1.0):
         dev = next(model.parameters()).device
-        H, nH = cfg.hidden_size, cfg.num_attention_heads
-        nl = len(mv.encoder.layer)
-        self.key, self.model, self.B, self.max_length, self.eos, self.pad = key, model, B, max_length, eos, pad
-        cap = n_img + 2 + max_length + 1
-        self.kc = [torch.zeros((B, nH, cap, H // nH), dtype=cd, device=dev) for _ in range(nl)]
-        self.vc = [torch.zeros((B, nH, cap, H // nH), dtype=cd, device=dev) for _ in range(nl)]
+        H = model.config.hidden_size
+        self.key, self.model, self.cd, self.graph = key, model, cd, None
+        self.kc, self.vc = _alloc_cache(model, B, n_img, max_length, cd, dev)
         self.past = torch.zeros(1, dtype=torch.int32, device=dev)
         self.col = torch.zeros(1, dtype=torch.int64, device=dev)
         self.new_ids = torch.full((B, 2), mask_id, dtype=torch.int64, device=dev)       # [last token, MASK]
@@ -181,7 +317,6 @@ class _GreedyGraph:
         self.ids = torch.zeros((B, max_length), dtype=torch.int64, device=dev)
         self.scores = torch.zeros((B, max_length), dtype=torch.float32, device=dev)
         self.alive = torch.ones(max_length, dtype=torch.int64, device=dev)
-        self.cd, self.graph = cd, None
         # device-side state of the greedy loop, handed to mvlt_gemm_argmax_greedy: the pick, PAD for finished samples, the
         # EOS flags, the ids / scores columns, the next input id, `past` and `col` are all advanced by its finishing launch
         # (mode 'sample': mvlt_gemm_sample_step, the same state plus the seed cell the loop fills before the first replay)
@@ -199,87 +334,104 @@ class _GreedyGraph:
 
     def head(self):
         """token <- argmax(MLM head(hlast)); record it in column `col`; past += 1; col += 1 (all on the device)."""
-        model = self.model
-        ar = Arena.of(model, self.cd)
-        hd = model.MLM_head_seq2seq
-        _, _, t2, _, _ = hd._transform(ar, self.hlast, False)
         # decoder GEMM fused with the greedy pick and its bookkeeping: the [B, 30522] logits are never written
-        W, bias = ar.compute(hd.predictions.decoder.weight), hd.predictions.decoder.bias.data
+        t2, W, bias = _head(self.model, Arena.of(self.model, self.cd), self.hlast)
         if self.mode != 'greedy' and (self.top_k, self.top_p) != (0, 1.0):
             ops.gemm_sample_filtered_step(t2, W, bias, self.state, self.top_k, self.top_p)
-            return
-        pick = ops.gemm_argmax_greedy if self.mode == 'greedy' else ops.gemm_sample_step
-        pick(t2, W, bias, self.state)
+        elif self.mode != 'greedy':
+            ops.gemm_sample_step(t2, W, bias, self.state)
+        else:
+            ops.gemm_argmax_greedy(t2, W, bias, self.state)
 
-    def forward2(self):
-        """2-token cached forward of [last token, MASK] at positions past, past+1 (model.py:82-108).  `past` was advanced by
-        the pick that produced the token: the previous step's [MASK] slot is overwritten (model.py:890-894)."""
-        mv = self.model.MVLBert
-        ar = Arena.of(self.model, self.cd)
-        B, H = self.B, mv.config.hidden_size
-        x = _embed_new(mv, self.new_ids, self.past, self.cd).view(B * 2, H)
-        _layers_cached(mv, ar, x, self.kc, self.vc, self.past, 2, out_last=self.hfull)
-
-    def capture(self):
-        # scratch buffers (split-K workspace) used inside the graph get their own tag: the captured pointers must
-        # never be freed or handed to other work by a later, larger request on the main stream
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), ops.on_stream(side, "graph"):     # warm-up outside the capture (allocator, lazy state)
-            self.head(); self.forward2()
-        torch.cuda.current_stream().wait_stream(side)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            with ops.on_stream(torch.cuda.current_stream(), "graph"):
-                self.head(); self.forward2()
-        self.graph = g
+    def body(self):
+        """The pick, then the 2-token cached forward of [last token, MASK] at positions past, past+1.  `past` was advanced by the
+        pick that produced the token: the previous step's [MASK] slot is overwritten (model.py:890-894)."""
+        self.head()
+        _step2(self.model.MVLBert, Arena.of(self.model, self.cd), self.new_ids, self.past, self.kc, self.vc, self.cd, out_last=self.hfull)
 
 
-def _greedy_graph_loop(model, feat, max_length, pad, eos, mask_id, cd, mode='greedy', seed=0, temperature=1.0, top_k=0, top_p=1.0):
-    mv, cfg = model.MVLBert, model.config
-    B, n_img, H = feat.shape
-    nH = cfg.num_attention_heads
-    nl = len(mv.encoder.layer)
-    ar = Arena.of(model, cd)
+def _greedy_graph_loop(model, ar, feat, max_length, pad, eos, mask_id, cd, mode, seed, temperature, top_k, top_p):
+    B, n_img, _ = feat.shape
     key = (B, n_img, max_length, cd, pad, eos, mask_id, ar.flat.data_ptr(), feat.device.index)
     slot = "_mvlt_greedy_graph"
     if mode != 'greedy':          # a graph of its own beside the greedy one: neither recaptures the other
         key, slot = key + (mode, float(temperature)), "_mvlt_sample_graph"
         if (top_k, top_p) != (0, 1.0):          # a filtered graph takes the sampled graph's slot, like a new temperature
             key = key + (top_k, top_p)
-    gg = model.__dict__.get(slot)
-    if gg is None or gg.key != key:
-        gg = _GreedyGraph(model, B, n_img, max_length, cd, pad, eos, mask_id, key, mode, temperature, top_k, top_p)
-        gg.capture()
-        model.__dict__[slot] = gg
+    gg = _GreedyGraph.of(model, slot, key, B, n_img, max_length, cd, pad, eos, mask_id, mode, temperature, top_k, top_p)
     gg.seed.fill_(ops.s64(int(seed) & ((1 << 64) - 1)))
-    # ---- step 0: [CLS] img [SEP] [MASK], full seq2seq forward (model.py:110-160), eager
-    mask_col = gg.new_ids[:, 1:2].contiguous()
-    hidden, _, saved = mv._forward(feat, mask_col, mask_col, None, True, True)
-    L0 = n_img + 3
-    for i in range(nl):
-        _fill_cache_from_qkv(saved["layers"][i][1], B, L0, nH, H // nH, gg.kc[i], gg.vc[i], L0 - 1)
-    del saved
-    gg.past.fill_(L0 - 2); gg.col.zero_(); gg.unfinished.fill_(1); gg.alive.zero_(); gg.ticket.zero_()      # (the first pick advances `past` to L0 - 1; the picks raise `alive`)
-    gg.hlast.copy_(hidden[:, -1])
+    hlast, past = _step0(model.MVLBert, feat, gg.new_ids[:, 1:2].contiguous(), gg.kc, gg.vc)
+    gg.past.fill_(past - 1); gg.col.zero_(); gg.unfinished.fill_(1); gg.alive.zero_(); gg.ticket.zero_()      # (the first pick advances `past`; the picks raise `alive`)
+    gg.hlast.copy_(hlast)
     done = 0
     for t in range(max_length - 1):
         gg.graph.replay()                        # token t, then the forward that prepares token t+1
         done = t + 1
-        if eos is not None and done % 8 == 0 and 0 in gg.alive[done - 8:done].tolist():   # one host sync per 8 tokens
+        if _sync_due(eos, done) and 0 in gg.alive[done - SYNC_EVERY:done].tolist():
             break
     else:
         gg.head()                                # last token: head only
         done = max_length
-    flags = gg.alive[:done].tolist() if eos is not None else []
-    if 0 in flags:       # cut where the reference's per-token check stops; it breaks before appending that step's score
-        n_out = flags.index(0) + 1
-        n_scores = n_out - 1
-    else:
-        n_out = n_scores = done
+    n_out, n_scores = _cut(gg.alive[:done].tolist() if eos is not None else [], done)
     ids = gg.ids[:, :n_out].clone()
     scores = gg.scores[:, :n_scores].t().reshape(-1).clone() if n_scores > 0 else torch.empty(0, device=feat.device)
     return ids, scores
+
+
+def _greedy_eager_loop(model, ar, feat, max_length, pad, eos, mask_id, cd, pick, seed, temperature, top_k, top_p):
+    mv = model.MVLBert
+    B, n_img, _ = feat.shape
+    dev = feat.device
+    head = model.MLM_head_seq2seq
+    V = head.predictions.decoder.out_features
+    kc, vc = _alloc_cache(model, B, n_img, max_length, cd, dev)
+    mask_col = torch.full((B, 1), mask_id, dtype=torch.int64, device=dev)
+
+    def next_from(hlast):
+        t2, W, bias = _head(model, ar, hlast.contiguous())
+        tag = SAMPLE_TAG0 + len(ids_cols)
+        if pick == 'gemm_argmax':
+            return ops.gemm_argmax(t2, W, bias)
+        if pick == 'filtered':        # stand-alone filtered pick; rows beyond 64 in chunks, the noise indexed by the batch row
+            parts = [ops.gemm_sample_filtered(t2[r0:r0 + 64], W, bias, seed, tag, temperature, top_k, top_p, row0=r0)
+                     for r0 in range(0, t2.shape[0], 64)]
+            return torch.cat([a for a, _ in parts]), torch.cat([b for _, b in parts])
+        if pick == 'gemm_sample':     # the pick of the graph loop, stand-alone: same seed, tag and column -> same tokens
+            return ops.gemm_sample(t2, W, bias, seed, tag, temperature)
+        logits, _ = head._logits(ar, t2)
+        if pick == 'argmax':
+            nxt = ops.argmax(logits, V)
+            return nxt, logits[:, :V].float().gather(1, nxt[:, None]).squeeze(1)
+        probs = ops.softmax_rows(logits, V)
+        nxt = torch.multinomial(probs, num_samples=1, replacement=True).squeeze(1)
+        return nxt, torch.log(probs.gather(1, nxt[:, None])).squeeze(1)
+
+    hlast, past = _step0(mv, feat, mask_col, kc, vc)
+    unfinished = torch.ones(B, dtype=torch.int64, device=dev)
+    ids_cols, scores, alive, flags = [], [], [], []        # `alive`: device scalars, one per column; `flags`: what was read back
+    while len(ids_cols) < max_length:
+        nxt, score = next_from(hlast)
+        if eos is not None:
+            nxt = nxt * unfinished + pad * (1 - unfinished)
+            unfinished = unfinished * (nxt != eos).long()
+            alive.append(unfinished.max())
+        ids_cols.append(nxt[:, None])
+        if _sync_due(eos, len(ids_cols), last=max_length):
+            block = torch.stack(alive[-SYNC_EVERY:]).tolist()
+            flags[len(alive) - len(block):] = block
+            if 0 in block:
+                break
+        scores.append(score)
+        if len(ids_cols) >= max_length:
+            break
+        new_ids = torch.cat([nxt[:, None], mask_col], dim=1)              # [last_token, MASK] (model.py:587-591)
+        hlast = _step2(mv, ar, new_ids, past, kc, vc, cd)
+        past += 1                                                         # drop the [MASK] slot (model.py:890-894)
+    n_out, n_scores = _cut(flags, len(ids_cols))
+    ids_cols, scores = ids_cols[:n_out], scores[:n_scores]
+    input_ids = torch.cat(ids_cols, dim=-1) if ids_cols else None
+    token_scores = torch.cat(scores, dim=-1) if scores else torch.empty(0, device=dev)
+    return input_ids, token_scores
 
 
 @torch.no_grad()
@@ -298,110 +450,19 @@ def greedy_search(model, image_feature, learning_strategy='unilm', sample_mode='
     top_k, top_p = ops.check_sample_filter(top_k, top_p)
     if learning_strategy != 'unilm':
         raise NotImplementedError("only learning_strategy='unilm' is coherent with the KV cache (SURVEY.md 3.3)")
-    mv, cfg = model.MVLBert, model.config
-    cd = compute_dtype_of(model)
-    ar = Arena.of(model, cd)
-    ar.refresh_shadow()
-    max_length = max_length if max_length is not None else cfg.max_length
-    pad = pad_token_id if pad_token_id is not None else cfg.pad_token_id
-    eos = eos_token_id if eos_token_id is not None else cfg.eos_token_id
-    tok = getattr(model, "tokenizer", None)
-    mask_id = tok.mask_token_id if tok is not None else cfg.mask_token_id
-    feat = image_feature.to(cd).contiguous()
+    cd, ar, max_length, pad, eos, mask_id, feat = _resolve(model, image_feature, max_length, pad_token_id, eos_token_id)
     V = model.MLM_head_seq2seq.predictions.decoder.out_features
     top_k, top_p = (top_k if top_k < V else 0), min(top_p, 1.0)          # the values that mean "off" in one spelling each
-    filtered = (top_k, top_p) != (0, 1.0)
-    if filtered and sample_mode != 'sample':
-        raise ValueError("top_k / top_p filter the sampled pick: they need sample_mode='sample'")
-    # (the fused decoder-GEMM + argmax of the graph path holds the whole batch in one 64-row tile)
-    if sample_mode == 'greedy' and os.environ.get("MVLT_DECODE_GRAPH", "1") == "1" and feat.shape[0] <= 64:
-        return _greedy_graph_loop(model, feat, max_length, pad, eos, mask_id, cd)
-    fused_sample = sample_mode == 'sample' and (feat.shape[0] <= 64 or filtered)
-    if fused_sample:
+    loop, pick = _greedy_route(sample_mode, feat.shape[0], (top_k, top_p) != (0, 1.0), _env()[0])
+    if sample_mode == 'greedy':
+        seed, temperature = 0, 1.0               # unused by the greedy pick, and no part of its graph's key
+    elif pick != 'multinomial':
         if not float(temperature) > 0.0:
             raise ValueError("temperature must be positive")
         if seed is None:
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
-        if os.environ.get("MVLT_DECODE_GRAPH", "1") == "1" and feat.shape[0] <= 64:
-            return _greedy_graph_loop(model, feat, max_length, pad, eos, mask_id, cd, 'sample', seed, temperature, top_k, top_p)
-    B, n_img, H = feat.shape
-    nH = cfg.num_attention_heads
-    hd = H // nH
-    nl = len(mv.encoder.layer)
-    dev = feat.device
-    head = model.MLM_head_seq2seq
-    cap = n_img + 2 + max_length + 1
-    kc = [torch.zeros((B, nH, cap, hd), dtype=cd, device=dev) for _ in range(nl)]
-    vc = [torch.zeros((B, nH, cap, hd), dtype=cd, device=dev) for _ in range(nl)]
-    mask_col = torch.full((B, 1), mask_id, dtype=torch.int64, device=dev)
-
-    def next_from(hlast):
-        pre, t1, t2, _, _ = head._transform(ar, hlast.contiguous(), False)
-        if sample_mode == 'greedy' and t2.shape[0] <= 64:
-            return ops.gemm_argmax(t2, ar.compute(head.predictions.decoder.weight), head.predictions.decoder.bias.data)
-        if filtered:                  # stand-alone filtered pick; rows beyond 64 in chunks, the noise indexed by the batch row
-            W, bias = ar.compute(head.predictions.decoder.weight), head.predictions.decoder.bias.data
-            parts = [ops.gemm_sample_filtered(t2[r0:r0 + 64], W, bias, seed, SAMPLE_TAG0 + len(ids_cols), temperature, top_k, top_p, row0=r0)
-                     for r0 in range(0, t2.shape[0], 64)]
-            return torch.cat([a for a, _ in parts]), torch.cat([b for _, b in parts])
-        if fused_sample:              # the pick of the graph loop, stand-alone: same seed, tag and column -> same tokens
-            return ops.gemm_sample(t2, ar.compute(head.predictions.decoder.weight), head.predictions.decoder.bias.data,
-                                   seed, SAMPLE_TAG0 + len(ids_cols), temperature)
-        logits, _ = head._logits(ar, t2)
-        if sample_mode == 'greedy':
-            nxt = ops.argmax(logits, V)
-            score = logits[:, :V].float().gather(1, nxt[:, None]).squeeze(1)
-        elif sample_mode == 'sample':
-            probs = ops.softmax_rows(logits, V)
-            nxt = torch.multinomial(probs, num_samples=1, replacement=True).squeeze(1)
-            score = torch.log(probs.gather(1, nxt[:, None])).squeeze(1)
-        else:
-            raise ValueError("sample mode error!")
-        return nxt, score
-
-    # ---- step 0: [CLS] img [SEP] [MASK], full seq2seq forward (model.py:110-160)
-    hidden, _, saved = mv._forward(feat, mask_col, mask_col, None, True, True)
-    L0 = n_img + 3
-    past = L0 - 1
-    for i in range(nl):
-        _fill_cache_from_qkv(saved["layers"][i][1], B, L0, nH, hd, kc[i], vc[i], past)
-    del saved
-    unfinished = torch.ones(B, dtype=torch.int64, device=dev)
-    ids_cols, scores, alive = [], [], []
-    hlast = hidden[:, -1]
-    cur_len = 0
-    n_out = None                     # number of generated columns once every sequence has emitted [END]
-    # The reference asks the device "all finished?" after every token (model.py:954), which serialises host and
-    # GPU.  Finished sequences only emit PAD, so running a few steps past the end changes nothing that is kept:
-    # the flag of every step is recorded on the device, read back every `sync_every` steps, and the outputs are
-    # cut at the exact step the reference would have stopped at.
-    sync_every = 8
-    while cur_len < max_length:
-        nxt, score = next_from(hlast)
-        if eos is not None:
-            nxt = nxt * unfinished + pad * (1 - unfinished)
-            unfinished = unfinished * (nxt != eos).long()
-            alive.append(unfinished.max())
-        ids_cols.append(nxt[:, None])
-        if eos is not None and (len(alive) % sync_every == 0 or cur_len + 1 >= max_length):
-            flags = torch.stack(alive[-sync_every:]).tolist()          # one host sync per `sync_every` tokens
-            if 0 in flags:
-                n_out = len(alive) - len(flags) + flags.index(0) + 1
-                break
-        cur_len += 1
-        scores.append(score)
-        if cur_len >= max_length:
-            break
-        new_ids = torch.cat([nxt[:, None], mask_col], dim=1)              # [last_token, MASK] (model.py:587-591)
-        x = _embed_new(mv, new_ids, past, cd).view(B * 2, H)
-        h = _layers_cached(mv, ar, x, kc, vc, past, 2).view(B, 2, H)
-        past += 1                                                         # drop the [MASK] slot (model.py:890-894)
-        hlast = h[:, -1]
-    if n_out is not None:            # the reference breaks before appending the score of the finishing step
-        ids_cols, scores = ids_cols[:n_out], scores[:n_out - 1]
-    input_ids = torch.cat(ids_cols, dim=-1) if ids_cols else None
-    token_scores = torch.cat(scores, dim=-1) if scores else torch.empty(0, device=dev)
-    return input_ids, token_scores
+    search = _greedy_graph_loop if loop == 'graph' else _greedy_eager_loop
+    return search(model, ar, feat, max_length, pad, eos, mask_id, cd, pick, seed, temperature, top_k, top_p)
 
 
 # ----------------------------------------------------------------------------- beam search (model.py:636-816)
@@ -564,110 +625,66 @@ class BeamDeviceState:
         return sc, host["seq"][:, :n].tolist(), host["beam_scores"].tolist()
 
 
-def _beam_device_step0(model, ar, feat, st, kc, vc, W, bias, ws=None):
-    """Step 0 of the device-scorer routes, eager: the full forward on the B images, the prefix into the first cache row of every
-    sample, the candidates of the one scored row per sample into ``st.cand``.  Returns the prefix length."""
-    mv, cfg = model.MVLBert, model.config
-    B, n_img, H = feat.shape
-    nH = cfg.num_attention_heads
-    nb = st.nb
-    mask_col = st.new_ids[::nb, 1:2].contiguous()
-    hidden, _, saved = mv._forward(feat, mask_col, mask_col, None, True, True)
-    L0 = n_img + 3
-    for i in range(len(mv.encoder.layer)):
-        _fill_cache_from_qkv(saved["layers"][i][1], B, L0, nH, H // nH, kc[i][::nb], vc[i][::nb], L0 - 1)
-    del saved
-    st.reset(L0 - 2)
-    _, _, t2, _, _ = model.MLM_head_seq2seq._transform(ar, hidden[:, -1].contiguous(), False)
-    ops.gemm_beam_candidates(t2, W, bias, torch.zeros(B, dtype=torch.float32, device=feat.device), 1, 2 * nb, out=st.cand, ws=ws)
-    return L0 - 1
-
-
-class _BeamGraph:
+class _BeamGraph(_DecodeGraph):
     """Beam search per token as one replayed HIP graph, after the model of ``_GreedyGraph``: [mvlt_beam_step, the 2-token cached
     forward over the B * beams rows, the head transform, mvlt_gemm_beam_candidates], captured on one stream (no parallel
     branches).  All state is static: ``BeamDeviceState``, the caches, the hidden rows, the logits workspace.  The captured
     beam step carries src_beams = num_beams also for the lists of step 0 (their beam index is 0, which both values admit)."""
 
-    def __reduce__(self):                 # captured graphs do not survive pickling: rebuilt on the next call
-        return (_no_graph, ())
-
-    def __init__(self, model, B, nb, n_img, max_length, cd, pad, eos, mask_id, key, log):
-        mv, cfg = model.MVLBert, model.config
+    def __init__(self, model, key, B, nb, n_img, max_length, cd, pad, eos, mask_id, log):
         dev = next(model.parameters()).device
-        H, nH = cfg.hidden_size, cfg.num_attention_heads
-        nl = len(mv.encoder.layer)
+        H = model.config.hidden_size
         rows = B * nb
-        self.key, self.model, self.B, self.nb, self.cd, self.graph = key, model, B, nb, cd, None
+        self.key, self.model, self.nb, self.cd, self.graph = key, model, nb, cd, None
         self.prefix = n_img + 2
-        cap = n_img + 2 + max_length + 1
-        self.kc = [torch.zeros((rows, nH, cap, H // nH), dtype=cd, device=dev) for _ in range(nl)]
-        self.vc = [torch.zeros((rows, nH, cap, H // nH), dtype=cd, device=dev) for _ in range(nl)]
+        self.kc, self.vc = _alloc_cache(model, rows, n_img, max_length, cd, dev)
         self.log = torch.zeros((max_length, B, 3, 2 * nb), dtype=torch.int32, device=dev) if log else None
         self.st = BeamDeviceState(B, nb, max_length, pad, eos, mask_id, dev, cand_log=self.log)
         self.hfull = torch.zeros((rows * 2, H), dtype=cd, device=dev)
         self.hlast = self.hfull.view(rows, 2, H)[:, 1]
         V = model.MLM_head_seq2seq.predictions.decoder.out_features
         self.ws = torch.empty(rows * ((V + 3) // 4 * 4), dtype=torch.float32, device=dev)
+        self.st.reset(self.prefix - 1)          # a valid position for the warm-up and the capture pass: both really run
 
     def step(self):
         ops.beam_step(self.st.struct)
 
-    def forward2(self):
-        """The cached forward of [kept token, MASK] at positions past, past + 1, then the candidates of the next token."""
+    def body(self):
+        """The beam step, the cached forward of [kept token, MASK] at positions past, past + 1, the candidates of the next token."""
         model, st = self.model, self.st
-        mv = model.MVLBert
         ar = Arena.of(model, self.cd)
-        hd = model.MLM_head_seq2seq
-        H = mv.config.hidden_size
-        x = _embed_new(mv, st.new_ids, st.past, self.cd).view(self.B * self.nb * 2, H)
-        _layers_cached(mv, ar, x, self.kc, self.vc, st.past, 2, out_last=self.hfull, beam=(self.nb, self.prefix, st.slot))
-        _, _, t2, _, _ = hd._transform(ar, self.hlast, False)
-        ops.gemm_beam_candidates(t2, ar.compute(hd.predictions.decoder.weight), hd.predictions.decoder.bias.data, st.beam_scores,
-                                 self.nb, 2 * self.nb, out=st.cand, ws=self.ws)
-
-    def capture(self):
-        self.st.reset(self.prefix - 1)          # a valid position for the warm-up and the capture pass: both really run
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), ops.on_stream(side, "graph"):     # warm-up outside the capture (allocator, lazy state)
-            self.step(); self.forward2()
-        torch.cuda.current_stream().wait_stream(side)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            with ops.on_stream(torch.cuda.current_stream(), "graph"):
-                self.step(); self.forward2()
-        self.graph = g
+        self.step()
+        _step2(model.MVLBert, ar, st.new_ids, st.past, self.kc, self.vc, self.cd, out_last=self.hfull, beam=(self.nb, self.prefix, st.slot))
+        t2, W, bias = _head(model, ar, self.hlast)
+        ops.gemm_beam_candidates(t2, W, bias, st.beam_scores, self.nb, 2 * self.nb, out=st.cand, ws=self.ws)
 
 
-def _beam_device_search(model, feat, nb, max_length, pad, eos, mask_id, cd, cand_log):
-    """beam_search with the scorer on the device (``mvlt_beam_step``): no per-token read-back.  MVLT_DECODE_GRAPH=0: the eager
-    loop; otherwise one graph replay per token (``_BeamGraph``).  The host reads ``alive`` back every 8 tokens; the steps that run
-    past the point where every sample is done change no pool (done samples are skipped).  ``finalize`` is the host scorer's."""
-    mv, cfg = model.MVLBert, model.config
-    B, n_img, H = feat.shape
-    nH = cfg.num_attention_heads
-    nl = len(mv.encoder.layer)
+def _beam_device(model, ar, feat, nb, max_length, pad, eos, mask_id, cd, graph_on, cand_log):
+    """beam_search with the scorer on the device (``mvlt_beam_step``): no per-token read-back.  ``graph_on``: one graph replay per
+    token (``_BeamGraph``), else the eager loop.  The host reads ``alive`` back every 8 tokens; the steps that run past the
+    point where every sample is done change no pool (done samples are skipped).  ``finalize`` is the host scorer's."""
+    B, n_img, _ = feat.shape
     dev = feat.device
-    ar = Arena.of(model, cd)
-    head = model.MLM_head_seq2seq
-    W, bias = ar.compute(head.predictions.decoder.weight), head.predictions.decoder.bias.data
-    rows = B * nb
-
-    def all_done(t):          # after the beam step of token t: one host sync per 8 tokens
-        return eos is not None and (t + 1) % 8 == 0 and 0 in st.alive[t - 7:t + 1].tolist()
-
-    if os.environ.get("MVLT_DECODE_GRAPH", "1") == "1":
+    if graph_on:
         key = (B, nb, n_img, max_length, cd, pad, eos, mask_id, ar.flat.data_ptr(), dev.index, cand_log is not None)
-        bg = model.__dict__.get("_mvlt_beam_graph")
-        if bg is None or bg.key != key:
-            bg = _BeamGraph(model, B, nb, n_img, max_length, cd, pad, eos, mask_id, key, cand_log is not None)
-            bg.capture()
-            model.__dict__["_mvlt_beam_graph"] = bg
-        st = bg.st
+        bg = _BeamGraph.of(model, "_mvlt_beam_graph", key, B, nb, n_img, max_length, cd, pad, eos, mask_id, cand_log is not None)
+        st, kc, vc, ws = bg.st, bg.kc, bg.vc, bg.ws
         if bg.log is not None:
             bg.log.zero_()
-        _beam_device_step0(model, ar, feat, st, bg.kc, bg.vc, W, bias, ws=bg.ws)
+    else:
+        st = BeamDeviceState(B, nb, max_length, pad, eos, mask_id, dev, cand_log=cand_log)
+        kc, vc = _alloc_cache(model, B * nb, n_img, max_length, cd, dev)
+        ws = None
+    # ---- step 0: the prefix into the first cache row of every sample, the candidates of the one scored row per sample
+    hlast, prefix = _step0(model.MVLBert, feat, st.new_ids[::nb, 1:2].contiguous(), kc, vc, stride=nb)
+    st.reset(prefix - 1)
+    t2, W, bias = _head(model, ar, hlast.contiguous())
+    ops.gemm_beam_candidates(t2, W, bias, torch.zeros(B, dtype=torch.float32, device=dev), 1, 2 * nb, out=st.cand, ws=ws)
+
+    def all_done(t):          # after the beam step of token t
+        return _sync_due(eos, t + 1) and 0 in st.alive[t + 1 - SYNC_EVERY:t + 1].tolist()
+
+    if graph_on:
         for t in range(max_length - 1):
             bg.graph.replay()                    # the beam step of token t, then the forward and candidates of token t + 1
             if all_done(t):
@@ -677,25 +694,107 @@ def _beam_device_search(model, feat, nb, max_length, pad, eos, mask_id, cd, cand
         if cand_log is not None:
             cand_log.copy_(bg.log)
     else:
-        st = BeamDeviceState(B, nb, max_length, pad, eos, mask_id, dev, cand_log=cand_log)
-        cap = n_img + 2 + max_length + 1
-        kc = [torch.zeros((rows, nH, cap, H // nH), dtype=cd, device=dev) for _ in range(nl)]
-        vc = [torch.zeros((rows, nH, cap, H // nH), dtype=cd, device=dev) for _ in range(nl)]
-        prefix = _beam_device_step0(model, ar, feat, st, kc, vc, W, bias)
         for t in range(max_length):
             ops.beam_step(st.struct, 1 if t == 0 else nb)
             if t + 1 >= max_length or all_done(t):
                 break
-            x = _embed_new(mv, st.new_ids, st.past, cd).view(rows * 2, H)
-            h = _layers_cached(mv, ar, x, kc, vc, st.past, 2, beam=(nb, prefix, st.slot)).view(rows, 2, H)
-            _, _, t2, _, _ = head._transform(ar, h[:, -1].contiguous(), False)
+            hlast = _step2(model.MVLBert, ar, st.new_ids, st.past, kc, vc, cd, beam=(nb, prefix, st.slot))
+            t2, W, bias = _head(model, ar, hlast.contiguous())
             ops.gemm_beam_candidates(t2, W, bias, st.beam_scores, nb, 2 * nb, out=st.cand)
     scorer, seqs, scores = st.scorer()
-    out = scorer.finalize(seqs, scores, cfg.max_length, pad, eos)
+    out = scorer.finalize(seqs, scores, model.config.max_length, pad, eos)
     return torch.tensor(out, dtype=torch.int64, device=dev)
 
 
-BEAM_STEP_STAGE = 8192          # num_beams * max_length int32 words mvlt_beam_step stages in LDS (csrc/beam.hip BS_STAGE)
+def _host_beam_step(scorer, input_ids, cur_len, cands, pad, eos, dev):
+    """The host scorer over the candidates ``cands`` = (scores, tokens, beams) of a token, as [B][2 * beams] lists, and the lines
+    the reference runs behind it (:743-756) -> (grown hypotheses, beam scores, kept tokens, beam indices: device tensors)."""
+    s_l, t_l, i_l = scorer.process(input_ids, *cands, pad, eos)
+    input_ids = [[t] for t in t_l] if cur_len == 0 else [input_ids[i] + [t] for i, t in zip(i_l, t_l)]
+    return (input_ids, torch.tensor(s_l, dtype=torch.float32, device=dev), torch.tensor(t_l, dtype=torch.int64, device=dev),
+            torch.tensor(i_l, dtype=torch.int64, device=dev))
+
+
+def _beam_fused(model, ar, feat, nb, max_length, pad, eos, mask_id, cd, mask_col, mask2):
+    """The default route: candidates from ``mvlt_gemm_beam_candidates``, the cache never reordered (the attention follows the slot
+    table), the scorer on the host with one read-back per token."""
+    mv = model.MVLBert
+    B, n_img, _ = feat.shape
+    dev = feat.device
+    scorer = BeamScorer(B, nb)
+
+    def candidates(hlast, scores, beams):
+        """-> (scores, tokens, beams) of the 2 * nb candidates per sample as host lists: one read-back."""
+        t2, W, bias = _head(model, ar, hlast.contiguous())
+        out, _ = ops.gemm_beam_candidates(t2, W, bias, scores, beams, 2 * nb)
+        host = out.cpu()
+        return host[0].view(torch.float32).tolist(), host[2].tolist(), host[1].tolist()
+
+    # ---- step 0 on the B images: only beam 0 of a sample carries score 0 (:681-682), so its candidates are those of ONE row,
+    # and the prefix lives in the first row of every sample, once
+    kc, vc = _alloc_cache(model, B * nb, n_img, max_length, cd, dev)
+    hlast, prefix = _step0(mv, feat, mask_col, kc, vc, stride=nb)
+    past = prefix
+    own = (torch.arange(B * nb, device=dev) % nb).to(torch.int32)
+    slot = torch.zeros((B * nb, max_length), dtype=torch.int32, device=dev)      # [row, generated position] -> cache row in the sample
+    cands = candidates(hlast, torch.zeros(B, dtype=torch.float32, device=dev), 1)
+    input_ids = [[mask_id] for _ in range(B * nb)]        # what the reference hands the scorer at step 0 (:701-702)
+    for cur_len in range(max_length):
+        input_ids, beam_scores, beam_tok, beam_idx = _host_beam_step(scorer, input_ids, cur_len, cands, pad, eos, dev)
+        if scorer.is_done or cur_len + 1 >= max_length:
+            break
+        # the beam reorder (model.py:758-763) moves table rows, not cache rows.  A finished sample gets beam_idx 0 (a row of
+        # sample 0): only the slot VALUES travel, and the kernel clamps them into the sample
+        slot = slot.index_select(0, beam_idx)
+        hlast = _step2(mv, ar, torch.cat([beam_tok[:, None], mask2], dim=1), past, kc, vc, cd, beam=(nb, prefix, slot))
+        slot[:, past - prefix] = own                     # position `past` of every hypothesis now lives in its own row
+        past += 1
+        cands = candidates(hlast, beam_scores, nb)
+    seqs = scorer.finalize(input_ids, beam_scores.tolist(), model.config.max_length, pad, eos)
+    return torch.tensor(seqs, dtype=torch.int64, device=dev)
+
+
+def _beam_plain(model, ar, feat, nb, max_length, pad, eos, mask_id, cd, mask_col, mask2):
+    """The route of the reference: bf16 logits, ``log_softmax``, ``topk`` and a gather of every layer's cache by beam index per
+    token (model.py:758-763), the scorer on the host."""
+    mv = model.MVLBert
+    B, n_img, _ = feat.shape
+    dev = feat.device
+    head = model.MLM_head_seq2seq
+    V = head.predictions.decoder.out_features
+    scorer = BeamScorer(B, nb)
+
+    def logp_of(hlast):
+        t2, _, _ = _head(model, ar, hlast.contiguous())
+        logits, _ = head._logits(ar, t2)
+        return torch.log_softmax(logits[:, :V].float(), dim=-1)
+
+    # ---- step 0 on the B images; caches replicated to the beams afterwards
+    kc, vc = _alloc_cache(model, B, n_img, max_length, cd, dev)
+    hlast, past = _step0(mv, feat, mask_col, kc, vc)
+    rep = torch.arange(B, device=dev).repeat_interleave(nb)
+    kc, vc = [k.index_select(0, rep) for k in kc], [v.index_select(0, rep) for v in vc]
+    logp = logp_of(hlast).index_select(0, rep)                                # [B*nb, V]
+    beam_scores = torch.zeros((B, nb), dtype=torch.float32, device=dev)
+    beam_scores[:, 1:] = -1e9
+    beam_scores = beam_scores.view(-1)
+    input_ids = [[mask_id] for _ in range(B * nb)]        # what the reference hands the scorer at step 0 (:701-702)
+    for cur_len in range(max_length):
+        scores = (logp + beam_scores[:, None]).view(B, nb * V)
+        top_s, top_t = torch.topk(scores, 2 * nb, dim=1, largest=True, sorted=True)
+        top_i = torch.div(top_t, V, rounding_mode="floor")
+        top_t = top_t % V
+        cands = top_s.tolist(), top_t.tolist(), top_i.tolist()
+        input_ids, beam_scores, beam_tok, beam_idx = _host_beam_step(scorer, input_ids, cur_len, cands, pad, eos, dev)
+        if scorer.is_done or cur_len + 1 >= max_length:
+            break
+        for i in range(len(kc)):                             # beam reorder of the cache (model.py:758-763)
+            kc[i] = kc[i].index_select(0, beam_idx)
+            vc[i] = vc[i].index_select(0, beam_idx)
+        logp = logp_of(_step2(mv, ar, torch.cat([beam_tok[:, None], mask2], dim=1), past, kc, vc, cd))
+        past += 1
+    seqs = scorer.finalize(input_ids, beam_scores.tolist(), model.config.max_length, pad, eos)
+    return torch.tensor(seqs, dtype=torch.int64, device=dev)
 
 
 @torch.no_grad()
@@ -711,120 +810,15 @@ def beam_search(model, image_feature, num_beams, learning_strategy='unilm', max_
     int32 device tensor [max_length, B, 3, 2 * num_beams] that receives the candidate lists every step consumed."""
     if learning_strategy != 'unilm':
         raise NotImplementedError("only learning_strategy='unilm' is coherent with the KV cache (SURVEY.md 3.3)")
-    mv, cfg = model.MVLBert, model.config
-    cd = compute_dtype_of(model)
-    ar = Arena.of(model, cd)
-    ar.refresh_shadow()
-    max_length = max_length if max_length is not None else cfg.max_length
-    pad = pad_token_id if pad_token_id is not None else cfg.pad_token_id
-    eos = eos_token_id if eos_token_id is not None else cfg.eos_token_id
-    tok = getattr(model, "tokenizer", None)
-    mask_id = tok.mask_token_id if tok is not None else cfg.mask_token_id
-    feat = image_feature.to(cd).contiguous()
-    B, n_img, H = feat.shape
-    nH = cfg.num_attention_heads
-    hd = H // nH
-    nl = len(mv.encoder.layer)
-    dev = feat.device
-    head = model.MLM_head_seq2seq
-    V = head.predictions.decoder.out_features
-    nb = num_beams
-    cap = n_img + 2 + max_length + 1
-    scorer = BeamScorer(B, nb)
-
-    def logp_of(hlast):
-        _, _, t2, _, _ = head._transform(ar, hlast.contiguous(), False)
-        logits, _ = head._logits(ar, t2)
-        return torch.log_softmax(logits[:, :V].float(), dim=-1)
-
-    mask_col = torch.full((B, 1), mask_id, dtype=torch.int64, device=dev)
-    mask2 = torch.full((B * nb, 1), mask_id, dtype=torch.int64, device=dev)
-    L0 = n_img + 3
-    past = L0 - 1
-    input_ids = [[mask_id] for _ in range(B * nb)]        # what the reference hands the scorer at step 0 (:701-702)
-    cur_len = 0
-    # the fused route needs what its two entry points need; everything else decodes the way the reference does
-    fused = os.environ.get("MVLT_BEAM_FUSED", "1") != "0" and 1 <= nb <= ops.BEAM_MAX_BEAMS and 2 * nb <= ops.BEAM_MAX_CAND and hd == 64
-    if device_scorer is None:
-        device_scorer = os.environ.get("MVLT_BEAM_DEVICE", "0") == "1"
-    if device_scorer and fused and nb * max_length <= BEAM_STEP_STAGE:
-        return _beam_device_search(model, feat, nb, max_length, pad, eos, mask_id, cd, cand_log)
-    if fused:
-        W, bias = ar.compute(head.predictions.decoder.weight), head.predictions.decoder.bias.data
-
-        def candidates(hlast, scores, beams):
-            """-> (scores, tokens, beams) of the 2 * nb candidates per sample as host lists: one read-back."""
-            _, _, t2, _, _ = head._transform(ar, hlast.contiguous(), False)
-            out, _ = ops.gemm_beam_candidates(t2, W, bias, scores, beams, 2 * nb)
-            host = out.cpu()
-            return host[0].view(torch.float32).tolist(), host[2].tolist(), host[1].tolist()
-
-        # ---- step 0 on the B images: only beam 0 of a sample carries score 0 (:681-682), so its candidates are those of ONE row
-        hidden, _, saved = mv._forward(feat, mask_col, mask_col, None, True, True)
-        kc = [torch.zeros((B * nb, nH, cap, hd), dtype=cd, device=dev) for _ in range(nl)]
-        vc = [torch.zeros((B * nb, nH, cap, hd), dtype=cd, device=dev) for _ in range(nl)]
-        for i in range(nl):                                  # the prefix lives in the first row of every sample, once
-            _fill_cache_from_qkv(saved["layers"][i][1], B, L0, nH, hd, kc[i][::nb], vc[i][::nb], past)
-        del saved
-        prefix = past
-        own = (torch.arange(B * nb, device=dev) % nb).to(torch.int32)
-        slot = torch.zeros((B * nb, max_length), dtype=torch.int32, device=dev)      # [row, generated position] -> cache row in the sample
-        top_s, top_t, top_i = candidates(hidden[:, -1], torch.zeros(B, dtype=torch.float32, device=dev), 1)
-        while cur_len < max_length:
-            s_l, t_l, i_l = scorer.process(input_ids, top_s, top_t, top_i, pad, eos)
-            beam_scores = torch.tensor(s_l, dtype=torch.float32, device=dev)
-            beam_tok = torch.tensor(t_l, dtype=torch.int64, device=dev)
-            beam_idx = torch.tensor(i_l, dtype=torch.int64, device=dev)
-            input_ids = [[t] for t in t_l] if cur_len == 0 else [input_ids[i] + [t] for i, t in zip(i_l, t_l)]
-            cur_len += 1
-            if scorer.is_done or cur_len >= max_length:
-                break
-            # the beam reorder (model.py:758-763) moves table rows, not cache rows.  A finished sample gets beam_idx 0 (a row of
-            # sample 0): only the slot VALUES travel, and the kernel clamps them into the sample
-            slot = slot.index_select(0, beam_idx)
-            new_ids = torch.cat([beam_tok[:, None], mask2], dim=1)
-            x = _embed_new(mv, new_ids, past, cd).view(B * nb * 2, H)
-            h = _layers_cached(mv, ar, x, kc, vc, past, 2, beam=(nb, prefix, slot)).view(B * nb, 2, H)
-            slot[:, past - prefix] = own                     # position `past` of every hypothesis now lives in its own row
-            past += 1
-            top_s, top_t, top_i = candidates(h[:, -1], beam_scores, nb)
-        seqs = scorer.finalize(input_ids, beam_scores.tolist(), cfg.max_length, pad, eos)
-        return torch.tensor(seqs, dtype=torch.int64, device=dev)
-
-    # ---- step 0 on the B images; caches replicated to the beams afterwards
-    hidden, _, saved = mv._forward(feat, mask_col, mask_col, None, True, True)
-    rep = torch.arange(B, device=dev).repeat_interleave(nb)
-    kc, vc = [], []
-    for i in range(nl):
-        k1 = torch.zeros((B, nH, cap, hd), dtype=cd, device=dev)
-        v1 = torch.zeros((B, nH, cap, hd), dtype=cd, device=dev)
-        _fill_cache_from_qkv(saved["layers"][i][1], B, L0, nH, hd, k1, v1, past)
-        kc.append(k1.index_select(0, rep)); vc.append(v1.index_select(0, rep))
-    del saved
-    logp = logp_of(hidden[:, -1]).index_select(0, rep)                        # [B*nb, V]
-    beam_scores = torch.zeros((B, nb), dtype=torch.float32, device=dev)
-    beam_scores[:, 1:] = -1e9
-    beam_scores = beam_scores.view(-1)
-    while cur_len < max_length:
-        scores = (logp + beam_scores[:, None]).view(B, nb * V)
-        top_s, top_t = torch.topk(scores, 2 * nb, dim=1, largest=True, sorted=True)
-        top_i = torch.div(top_t, V, rounding_mode="floor")
-        top_t = top_t % V
-        s_l, t_l, i_l = scorer.process(input_ids, top_s.tolist(), top_t.tolist(), top_i.tolist(), pad, eos)
-        beam_scores = torch.tensor(s_l, dtype=torch.float32, device=dev)
-        beam_tok = torch.tensor(t_l, dtype=torch.int64, device=dev)
-        beam_idx = torch.tensor(i_l, dtype=torch.int64, device=dev)
-        input_ids = [[t] for t in t_l] if cur_len == 0 else [input_ids[i] + [t] for i, t in zip(i_l, t_l)]
-        cur_len += 1
-        if scorer.is_done or cur_len >= max_length:
-            break
-        for i in range(nl):                                  # beam reorder of the cache (model.py:758-763)
-            kc[i] = kc[i].index_select(0, beam_idx)
-            vc[i] = vc[i].index_select(0, beam_idx)
-        new_ids = torch.cat([beam_tok[:, None], mask2], dim=1)
-        x = _embed_new(mv, new_ids, past, cd).view(B * nb * 2, H)
-        h = _layers_cached(mv, ar, x, kc, vc, past, 2).view(B * nb, 2, H)
-        past += 1
-        logp = logp_of(h[:, -1])
-    seqs = scorer.finalize(input_ids, beam_scores.tolist(), cfg.max_length, pad, eos)
-    return torch.tensor(seqs, dtype=torch.int64, device=dev)
+    cd, ar, max_length, pad, eos, mask_id, feat = _resolve(model, image_feature, max_length, pad_token_id, eos_token_id)
+    cfg = model.config
+    B, nb = feat.shape[0], num_beams
+    # the [MASK] columns of step 0 and of the cached steps (filled ahead of the route; the device route has its own in its state)
+    mask_col = torch.full((B, 1), mask_id, dtype=torch.int64, device=feat.device)
+    mask2 = torch.full((B * nb, 1), mask_id, dtype=torch.int64, device=feat.device)
+    graph_on, fused_on, device_on = _env()
+    route = _beam_route(nb, cfg.hidden_size // cfg.num_attention_heads, max_length, fused_on, device_scorer, device_on)
+    if route == 'device':
+        return _beam_device(model, ar, feat, nb, max_length, pad, eos, mask_id, cd, graph_on, cand_log)
+    search = _beam_fused if route == 'fused' else _beam_plain
+    return search(model, ar, feat, nb, max_length, pad, eos, mask_id, cd, mask_col, mask2)

@@ -13,8 +13,9 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import sample_ref as S  # noqa: E402
-from conftest import hash_sd, rel_err, synth_batch  # noqa: E402
+from conftest import rel_err, synth_batch  # noqa: E402
 from gemm_ref import check_bound  # noqa: E402
+from tiny_caption import tiny_caption as _tiny  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -178,20 +179,6 @@ def test_refusals_write_nothing(M):
 
 
 # ------------------------------------------------------------------------------------------------ model level
-def _tiny(M, specs_hash, cd, max_length=8, eos=None):
-    cfg = M.MVLBertConfigForImageCaption(hidden_size=256, num_hidden_layers=2, num_attention_heads=4, intermediate_size=1024,
-                                         vocab_size=3000)
-    cfg.swin.update(embed_dim=32, depths=[2, 2, 2, 2], num_heads=[1, 2, 4, 8], drop_path_rate=0.2)
-    cfg.max_length = max_length
-    cfg.eos_token_id = eos
-    tok = type("Tok", (), {"mask_token_id": 103, "sep_token_id": 102})()
-    model = M.MVLBertForImageCaption(cfg, tokenizer=tok)
-    sd = hash_sd(specs_hash["hash_tiny_caption"])
-    _, unexpected = model.load_state_dict(sd, strict=False)
-    assert not unexpected
-    return M.set_compute_dtype(model.cuda().eval(), cd), sd
-
-
 def _tiny_oracle_cfgs():
     from oracle import mvlt_oracle as O
     scfg = O.SwinCfg(embed_dim=32, depths=(2, 2, 2, 2), num_heads=(1, 2, 4, 8), drop_path_rate=0.2)
