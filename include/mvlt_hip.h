@@ -320,7 +320,13 @@ int mvlt_recall_counts(const int32_t* rank, int n, const int32_t* ks, int nk, in
  * acc[s][M][N] (f32, k_splits slabs) = A[:, k-slice s] B[:, k-slice s]^T, M <= 64, both operands k-contiguous, no epilogue;
  * k_splits workgroups share every 16-column tile, each WRITES the slab of its slice (plain stores: no float atomics, nothing
  * to zero, bit-reproducible).  Pair it with mvlt_layernorm_acc_fwd(nsplit = k_splits), which adds the slabs in slice order
- * and applies bias + residual + LayerNorm (the BertSelfOutput / BertOutput tail, modeling_bert.py:282-293,340-351). */
+ * and applies bias + residual + LayerNorm (the BertSelfOutput / BertOutput tail, modeling_bert.py:282-293,340-351).
+ * Slice rule (pinned by tests/test_decode_tail_gpu.py): with nkb = K / k-block (k-block = 32 elements in bf16, 16 in f32) and
+ * per = ceil(nkb / k_splits), slice s covers the k-blocks [s * per, min(nkb, (s + 1) * per)); a slice with no blocks is
+ * written as zeros (the consumer sums ALL k_splits slabs); exactly [k_splits][M][N] floats are written, nothing behind them.
+ * MVLT_ERR_ARG: NULL pointers, k_splits outside 1 .. 64.  MVLT_ERR_UNSUPPORTED: M > 64, a k-major operand, a non-zero
+ * epilogue, K not a multiple of the k-block, lda / ldb not a multiple of 8 (bf16) / 4 (f32) elements or A / B not 16-byte
+ * aligned.  A refused call writes nothing. */
 int mvlt_gemm_skinny_accum(const MvltGemm* p, float* acc, int k_splits, void* stream);
 
 /* column sums: out[n] = sum_m x[m*ld + n]  (bias gradients), f32 out.
@@ -379,7 +385,9 @@ typedef struct MvltLayerNormBwd {
 int mvlt_layernorm_bwd(const MvltLayerNormBwd* p, void* stream);
 int mvlt_layernorm_bwd_workspace_rows(void);
 /* y[r,:] = LayerNorm(sum_s acc[s][r,:] + bias + residual[r,:]) * gamma + beta, rows <= a few hundred, C <= 2048; acc = the
- * nsplit slabs [nsplit][rows][C] (f32) of mvlt_gemm_skinny_accum (read only).  residual may be NULL. */
+ * nsplit slabs [nsplit][rows][C] (f32) of mvlt_gemm_skinny_accum (read only).  residual may be NULL.  The row is formed in
+ * f32: slabs in slice order, then bias, then residual; mean and variance are two passes over it.
+ * MVLT_ERR_ARG (nothing written): nsplit outside 1 .. 64, rows < 1, C < 1, C % 4 != 0 or C > 2048, a NULL pointer. */
 int mvlt_layernorm_acc_fwd(int dtype, const float* acc, int nsplit, const float* bias, const void* residual, const float* gamma,
                            const float* beta, float eps, int rows, int C, void* y, void* stream);
 /* deferred parameter-gradient reduction: one launch per 96 LayerNorms instead of one per LayerNorm.

@@ -116,8 +116,9 @@ def _layers_cached(mv, ar, x, kc, vc, past, n_new, out_last=None, beam=None):
     H = cfg.hidden_size
     nH = cfg.num_attention_heads
     rows = x.shape[0]
-    # the two N = H products of a layer (attention output, FFN-out) split their reduction over workgroups and meet in
-    # an f32 accumulator; bias + residual + LayerNorm read it (and zero it again) in the launch that follows anyway
+    # the two N = H products of a layer (attention output, FFN-out) split their reduction over workgroups, every k-slice into
+    # an f32 slab of its own; bias + residual + LayerNorm add the slabs (read only: every product OVERWRITES its slabs, nothing
+    # is zeroed) in the launch that follows anyway
     # (bf16 only: the exact-f32 parity mode keeps the deterministic summation order of the plain skinny kernel)
     split = _SKINNY_SPLIT and rows <= 64 and x.dtype == torch.bfloat16
     acc = None

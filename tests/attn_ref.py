@@ -291,10 +291,14 @@ def cached_ref(qkv_new, k_cache, v_cache, past, scale):
     return ref.out[rows], ref.out_b[rows]
 
 
-def layernorm_ref(x, gamma, beta, eps):
-    """LayerNorm in float64 and its bound for an f32 evaluation rounded to bf16: the mean and the variance are f32 sums
-    over C (C_ACC 2^-24 sqrt(C) each), the normalised value and the affine map a few f32 roundings (4 2^-24), the output
-    rounding U_BF16.  Returns (y, bound) of the rows of x."""
+def layernorm_ref(x, gamma, beta, eps, out_dtype=torch.bfloat16, dv=None):
+    """LayerNorm in float64 and its bound for an f32 evaluation rounded to out_dtype: the mean and the variance are f32
+    sums over C (C_ACC 2^-24 sqrt(C) each), the normalised value and the affine map a few f32 roundings (4 2^-24), the
+    output rounding U_OUT (2^-8 for bf16, 2^-24 for f32).
+    dv: optional per-element bound on the error of the row the kernel normalises against x (a row the kernel forms itself
+    in f32, mvlt_layernorm_acc_fwd: the additions of the slabs, the bias and the residual).  To first order a perturbation
+    d of the row moves y by gamma rstd (d - mean(d) - xh mean(xh d)), so dv enters as
+    |gamma| rstd (dv + mean(dv) + |xh| mean(|xh| dv)).  Returns (y, bound) of the rows of x."""
     x = x.double()
     C = x.shape[1]
     g, b = gamma.double().to(x.device), beta.double().to(x.device)
@@ -305,5 +309,9 @@ def layernorm_ref(x, gamma, beta, eps):
     y = xh * g + b
     sq = C_ACC * U32 * math.sqrt(C)
     d_mu = sq * x.abs().mean(1, keepdim=True)
-    est = g.abs() * (d_mu * rstd + (sq + 4 * U32) * xh.abs()) + 4 * U32 * b.abs() + U_BF16 * y.abs()
+    u_out = U32 if out_dtype == torch.float32 else U_BF16
+    est = g.abs() * (d_mu * rstd + (sq + 4 * U32) * xh.abs()) + 4 * U32 * b.abs() + u_out * y.abs()
+    if dv is not None:
+        dv = dv.double().to(x.device)
+        est = est + g.abs() * rstd * (dv + dv.mean(1, keepdim=True) + xh.abs() * (xh.abs() * dv).mean(1, keepdim=True))
     return y, SAFETY * est + 1e-30

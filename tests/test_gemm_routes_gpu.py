@@ -4,10 +4,11 @@ tests/gemm_ref.py with a PER-ELEMENT bound, not a relative norm over the whole o
 Each row of ROUTES names the kernel it targets and the gemm_dispatch condition that sends it there, and asserts the
 planner's (bm, bn, split) first: a planner change that moves a shape off its route fails here and the row gets
 re-pointed instead of quietly testing another kernel (the plan does not say LDS-DMA vs register-staged, or wide vs
-narrow epilogue: the comment does).  Every run also checks what the kernel must leave alone, pre-filled with NaN:
-the padding columns N..ldc, a guard row behind the output, and the rows at or beyond a row-major A's device-side row
-count (m_dev) -- every route here promises that.  Operand padding (lda / ldb beyond the extent) and the operand rows
-beyond m_dev hold NaN too: the kernel must not use them."""
+narrow epilogue: the comment does; rows with route= also assert mvlt_gemm_route's answer for the same struct, so a row
+pointed at the wrong kernel fails there and does not pass on another kernel's arithmetic).  Every run also checks what
+the kernel must leave alone, pre-filled with NaN: the padding columns N..ldc, a guard row behind the output, and the
+rows at or beyond a row-major A's device-side row count (m_dev) -- every route here promises that.  Operand padding
+(lda / ldb beyond the extent) and the operand rows beyond m_dev hold NaN too: the kernel must not use them."""
 import ctypes as C
 
 import pytest
@@ -21,12 +22,17 @@ BF, F32 = torch.bfloat16, torch.float32
 RD = 301                     # labelled rows of a B = 32, T = 80 step (the MLM head's m_dev): inside the fifth 64-row tile
 
 
-def R(id, dt, M, N, K, ak=False, bk=False, pad=(0, 0, 0), epi=(), split=0, mdev=None, plan=None):
+def R(id, dt, M, N, K, ak=False, bk=False, pad=(0, 0, 0), epi=(), split=0, mdev=None, plan=None, route=None):
     """pad: extra elements per row of A / B / C storage (lda, ldb, ldc beyond the extent); epi: subset of bias, gelu
-    (+ saved pre-activation), dropout, rowscale, rowmap, aux (x gelu'), residual, f32 (output), accum, colsum;
-    mdev: None or the device-side row count (a row-major A's rows, a k-major A's reduction)."""
+    (+ saved pre-activation), gelu_nopre (GELU alone: what the cached decode step issues for FFN-in), dropout, rowscale,
+    rowmap, aux (x gelu'), residual, f32 (output), accum, colsum;
+    mdev: None or the device-side row count (a row-major A's rows, a k-major A's reduction);
+    route: None or the name (_lib.GEMM_ROUTES) mvlt_gemm_route must answer for the filled struct, with plan[2] k-slices."""
     return pytest.param(dict(dt=dt, M=M, N=N, K=K, ak=ak, bk=bk, pad=pad, epi=set(epi), split=split, mdev=mdev,
-                             plan=plan), id=id)
+                             plan=plan, route=route), id=id)
+
+
+SK = dict(plan=(64, 16, 1), route="SKINNY")          # what mvlt_gemm_plan / mvlt_gemm_route answer for a skinny product
 
 
 ROUTES = [
@@ -108,6 +114,47 @@ ROUTES = [
     # decoder weight gradient: both k-major, f32 out, a_colsum, m_dev = reduction; ragged last row tile (30522 % 128)
     R("mlm-decoder-wgrad", BF, 30522, 768, 2560, ak=True, bk=True, pad=(6, 0, 0), epi=("f32", "colsum"), mdev=RD,
       plan=(128, 128, 1)),
+    # ---- gemm_skinny_kernel<T, false> (csrc/skinny.hip; gemm_host.h is_skinny + skinny_loads_ok: M <= 64, both operands
+    #      k-contiguous, K % k-block == 0 (32 in bf16, 16 in f32), no split, lda / ldb % 8 (f32: 4) == 0, 16-byte aligned).
+    #      A workgroup = 16 columns x all rows; 8 waves x 3 k-blocks in flight; fast_epi = only bias / GELU / residual bits,
+    #      epi_vec and a whole 16-column tile, per lane a row < M: pre-fetched operands; everything else through epilogue4.
+    # the products of a cached decode step (decode._layers_cached) at B = 1 and B = 32 (2 new tokens per sample)
+    R("skinny-qkv-b1", BF, 2, 2304, 768, epi=("bias",), **SK),                       # one row tile, 2 of 16 rows live
+    R("skinny-qkv-b32", BF, 64, 2304, 768, epi=("bias",), **SK),
+    R("skinny-ffn-in-b1", BF, 2, 3072, 768, epi=("bias", "gelu_nopre"), **SK),         # the only GELU fast_epi takes
+    R("skinny-attn-out-b32", BF, 64, 768, 768, epi=("bias", "residual"), **SK),
+    R("skinny-ffn-out-b32", BF, 64, 768, 3072, epi=("bias", "residual"), **SK),        # 96 k-blocks: four full rounds of 8 x 3
+    R("skinny-f32-ffn-out-b32", F32, 64, 768, 3072, epi=("bias", "residual"), **SK),   # the exact-f32 decode: 192 k-blocks
+    # k-loop edges
+    R("skinny-k32", BF, 16, 64, 32, epi=("bias", "gelu_nopre", "residual"), **SK),     # one k-block: seven waves add zeros
+    R("skinny-k800", BF, 17, 64, 800, **SK),       # 25 blocks: round 2 = block 24 live + two reloaded (wave 0); no epilogue
+    R("skinny-f32-k16", F32, 1, 64, 16, epi=("bias", "residual"), **SK),               # f32 k-block = 16; M = 1
+    R("skinny-f32-k400", F32, 49, 96, 400, epi=("bias", "gelu"), **SK),                # 25 f32 blocks; GELU + pre: epilogue4
+    # row-tile edges: M = 1 (f32 above), 16 (k32), 17 (k800), 49; m_dev inside a 16-row tile, 0, beyond M
+    R("skinny-m1", BF, 1, 768, 768, epi=("bias", "gelu_nopre"), **SK),
+    R("skinny-m49-rowmap", BF, 49, 768, 768, epi=("bias", "rowscale", "rowmap"), **SK),   # epilogue4, last tile 1 row
+    R("skinny-mdev37", BF, 64, 768, 768, epi=("bias", "residual"), mdev=37, **SK),     # fast_epi per lane: rows 32..36 of tile 2
+    R("skinny-mdev0", BF, 64, 768, 768, epi=("bias",), mdev=0, **SK),                  # nothing written
+    R("skinny-mdev-big", BF, 33, 768, 768, epi=("bias", "dropout"), mdev=100, **SK),
+    # column edges: fast_epi off for the whole launch or for the last tile only
+    R("skinny-n30", BF, 33, 30, 64, epi=("bias", "residual"), **SK),                   # N % 4 != 0: scalar stores, 2 tiles
+    R("skinny-n2-classifier", BF, 5, 2, 768, epi=("bias",), **SK),
+    R("skinny-ldc-pad2", BF, 64, 768, 768, pad=(0, 0, 2), epi=("bias", "gelu"), **SK),   # ldc % 4 != 0: epi_vec false
+    R("skinny-n776", BF, 33, 776, 768, epi=("bias", "gelu_nopre", "residual"), **SK),  # 48 fast tiles + one of 8 columns
+    # the remaining epilogue bits at M <= 64 (epilogue4): GELU + saved pre-activation with vector stores (and a last tile
+    # of 8 columns), x gelu'(aux), accumulate, f32 output
+    R("skinny-gelu-pre", BF, 32, 3000, 256, epi=("bias", "gelu"), **SK),
+    R("skinny-aux-accum", BF, 49, 96, 64, epi=("aux", "accum"), **SK),
+    R("skinny-f32out-accum", BF, 33, 100, 96, epi=("bias", "f32", "accum"), **SK),
+    # strided A: the pooler's hidden[:, 0] of a [B, L, H] tensor with L = 3 (lda = 3 K), NaN in the gap
+    R("skinny-pooler-strided", BF, 32, 768, 768, pad=(2 * 768, 0, 0), epi=("bias",), **SK),
+    R("skinny-f32-strided", F32, 5, 2, 768, pad=(2 * 768, 0, 0), epi=("bias", "residual"), **SK),
+    # ---- M <= 64 that is NOT skinny: the tile kernels at a single, mostly empty row tile
+    R("short-ktail-reg", BF, 33, 768, 200, epi=("bias",), plan=(64, 64, 1), route="REG"),          # K % 32 != 0
+    # lda % 8 != 0: is_skinny holds (the plan says 64 x 16) but skinny_loads_ok does not: register-staged 64 x 64
+    R("short-lda-reg", BF, 33, 768, 768, pad=(4, 0, 0), epi=("bias", "residual"), plan=(64, 16, 1), route="REG"),
+    R("short-bk-glds", BF, 33, 768, 768, bk=True, epi=("aux",), plan=(64, 64, 1), route="GLDS"),   # k-major B
+    R("short-split2-glds", BF, 33, 768, 768, split=2, epi=("bias",), plan=(64, 64, 2), route="GLDS"),   # split_k = 2
 ]
 
 
@@ -122,8 +169,10 @@ def _rand(shape, dt, seed, scale=1.0):
     return (torch.randn(shape, generator=g) * scale).to(dt).cuda()
 
 
-def _plan(L, dt, M, N, K, A, B, out, *, ak, bk, split, epi_bits, m_dev, colsum, res, pre, aux, bias):
-    """mvlt_gemm_plan on the struct ops.gemm fills (the fields the planner reads)."""
+def _plan(L, ops, dt, M, N, K, A, B, out, *, ak, bk, split, epi_bits, m_dev, colsum, res, pre, aux, bias, rowscale=None,
+          rowmap=None, drop_p=0.0, want_route=False):
+    """mvlt_gemm_plan on the struct ops.gemm fills (the fields the planner reads) and, when asked, mvlt_gemm_route on the
+    same struct (the dispatch itself in its no-launch mode): ((bm, bn, split), (route name, k-slices) or None)."""
     q = L.MvltGemm()
     q.dtype, q.M, q.N, q.K = (L.BF16 if dt == BF else L.F32), M, N, K
     q.A, q.lda = A.data_ptr(), A.stride(0)
@@ -137,9 +186,29 @@ def _plan(L, dt, M, N, K, A, B, out, *, ak, bk, split, epi_bits, m_dev, colsum, 
     q.pre = pre.data_ptr() if pre is not None else None
     q.aux = aux.data_ptr() if aux is not None else None
     q.bias = bias.data_ptr() if bias is not None else None
+    if rowscale is not None:
+        q.rowscale, q.rows_per_scale = rowscale[0].data_ptr(), rowscale[1]
+    q.rowmap = rowmap.data_ptr() if rowmap is not None else None
+    q.dropout_p = drop_p
     bm, bn, sp = C.c_int(), C.c_int(), C.c_int()
     assert L.lib().mvlt_gemm_plan(C.byref(q), C.byref(bm), C.byref(bn), C.byref(sp)) == 0
-    return bm.value, bn.value, sp.value
+    route = None
+    if want_route:
+        need = L.lib().mvlt_gemm_workspace_bytes(C.byref(q))
+        if need:
+            ws = ops.workspace("gemm", need, A.device)
+            q.workspace, q.workspace_bytes = ws.data_ptr(), ws.numel()
+        route = L.gemm_route_name(L.lib().mvlt_gemm_route(C.byref(q)))
+    return (bm.value, bn.value, sp.value), route
+
+
+def _note(request, what, out, ref, bound):
+    """Print the worst ratio to the bound (pytest -s shows it; a correct kernel sits at <= 0.5 of the f32 terms, while
+    the rounding of a bf16 output alone reaches U_OUT |ref| by construction)."""
+    if ref.numel():
+        o = out.double()
+        ratio = torch.where(torch.isfinite(o), (o - ref).abs() / bound, torch.full_like(ref, float("inf")))
+        print(f"BOUND-RATIO {request.node.name} {what} {float(ratio.max()):.4f}")
 
 
 def _padded(rows, cols, pad, dt, seed, scale=1.0):
@@ -150,7 +219,7 @@ def _padded(rows, cols, pad, dt, seed, scale=1.0):
 
 
 @pytest.mark.parametrize("r", ROUTES)
-def test_gemm_route(ops, r):
+def test_gemm_route(ops, r, request):
     from mvlt_amd import _lib as L
     dt, M, N, K, ak, bk, epi, mdev = r["dt"], r["M"], r["N"], r["K"], r["ak"], r["bk"], r["epi"], r["mdev"]
     pa, pb, pc = r["pad"]
@@ -179,6 +248,9 @@ def test_gemm_route(ops, r):
     if "bias" in epi:
         kw["bias"] = ref_kw["bias"] = _rand((N,), F32, seed + 3)
     pre = None
+    if "gelu_nopre" in epi:
+        assert "gelu" not in epi
+        kw["gelu"] = ref_kw["gelu"] = True
     if "gelu" in epi:
         kw["gelu"] = ref_kw["gelu"] = True
         pre_buf = torch.full((rows_out + 1, N + pc), float("nan"), dtype=dt, device="cuda")
@@ -193,8 +265,9 @@ def test_gemm_route(ops, r):
         rowmap = torch.randperm(M, generator=torch.Generator().manual_seed(seed + 4)).int().cuda()
         kw["rowmap"] = ref_kw["rowmap"] = rowmap
     if "rowscale" in epi:
-        rps = 97
+        rps = 97 if M > 194 else max(1, (M + 2) // 3)          # at least two scale groups, one of them zero
         rs = (0.25 + (torch.arange((M + rps - 1) // rps) % 5).float()).cuda()
+        assert rs.numel() > 1
         rs[1] = 0.0
         kw["rowscale"] = ref_kw["rowscale"] = (rs, rps)
     aux = res = None
@@ -221,14 +294,17 @@ def test_gemm_route(ops, r):
     if m_dev is not None:
         kw["m_dev"] = m_dev
 
-    epi_bits = ((L.EPI_BIAS if "bias" in kw else 0) | (L.EPI_GELU if pre is not None else 0) |
+    epi_bits = ((L.EPI_BIAS if "bias" in kw else 0) | (L.EPI_GELU if "gelu" in kw else 0) |
                 (L.EPI_SAVE_PRE if pre is not None else 0) | (L.EPI_DROPOUT if keep is not None else 0) |
                 (L.EPI_ROWSCALE if "rowscale" in kw else 0) | (L.EPI_RESIDUAL if res is not None else 0) |
                 (L.EPI_ROWMAP if rowmap is not None else 0) | (L.EPI_MUL_GELU_GRAD if aux is not None else 0) |
                 (L.EPI_OUT_F32 if "f32" in epi else 0) | (L.EPI_ACCUM if "accum" in epi else 0))
-    plan = _plan(L, dt, M, N, K, A, B, out, ak=ak, bk=bk, split=r["split"], epi_bits=epi_bits, m_dev=m_dev, colsum=cs,
-                 res=res, pre=pre, aux=aux, bias=kw.get("bias"))
+    plan, route = _plan(L, ops, dt, M, N, K, A, B, out, ak=ak, bk=bk, split=r["split"], epi_bits=epi_bits, m_dev=m_dev,
+                        colsum=cs, res=res, pre=pre, aux=aux, bias=kw.get("bias"), rowscale=kw.get("rowscale"), rowmap=rowmap,
+                        drop_p=0.1 if keep is not None else 0.0, want_route=r["route"] is not None)
     assert plan == r["plan"], f"planner moved this shape off its route: {plan} != {r['plan']}"
+    if r["route"] is not None:
+        assert route == (r["route"], plan[2]), f"dispatch moved this shape off its kernel: {route} != {(r['route'], plan[2])}"
 
     got = ops.gemm(A, B, a_kmajor=ak, b_kmajor=bk, out=out, split_k=r["split"], **kw)
     torch.cuda.synchronize()
@@ -236,8 +312,10 @@ def test_gemm_route(ops, r):
 
     ref, pre_ref, bound, rows, pre_bound = gemm_ref(
         a64, b64, out_dtype=odt, k_eff=k_eff, m_eff=m_eff, prev=prev if "accum" in epi else None, **ref_kw)
+    _note(request, "out", out[rows], ref, bound)
     check_bound(out[rows], ref, bound, "output")
     if pre is not None:
+        _note(request, "pre", pre[rows], pre_ref, pre_bound)
         check_bound(pre[rows], pre_ref, pre_bound, "saved pre-activation")
     # nothing written where the kernel has no business: padding columns, the guard row, rows at / beyond m_dev
     written = torch.zeros(rows_out + 1, dtype=torch.bool, device="cuda")

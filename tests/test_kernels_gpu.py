@@ -402,31 +402,6 @@ def test_wgrad_group_device_row_count(ops, R, used):
 
 
 @pytest.mark.parametrize("dt", DT)
-@pytest.mark.parametrize("M,N,K", [(64, 2304, 768), (64, 768, 3072), (32, 3000, 256), (5, 2, 768), (33, 30, 64), (64, 16, 32)])
-def test_gemm_skinny(ops, dt, M, N, K):
-    """M <= 64 products (decode step, poolers, classifier heads) take gemm_skinny_kernel: same contract."""
-    import ctypes as C
-    from mvlt_amd import _lib as L
-    a, w = rnd((M, K), dt, 1, 0.5), rnd((N, K), dt, 2, 0.5)
-    bias = rnd((N,), torch.float32, 3)
-    res = rnd((M, N), dt, 4)
-    p = L.MvltGemm()
-    p.dtype, p.M, p.N, p.K = (L.BF16 if dt == torch.bfloat16 else L.F32), M, N, K
-    bm, bn, sp = C.c_int(), C.c_int(), C.c_int()
-    assert L.lib().mvlt_gemm_plan(C.byref(p), C.byref(bm), C.byref(bn), C.byref(sp)) == 0
-    assert (bm.value, bn.value, sp.value) == (64, 16, 1)
-    ref = a.float() @ w.float().t()
-    assert rel(ops.gemm(a, w), ref) < tol(dt)
-    assert rel(ops.gemm(a, w, bias=bias, residual=res), ref + bias + res.float()) < tol(dt)
-    pre = torch.empty((M, N), dtype=dt, device="cuda")
-    out = ops.gemm(a, w, bias=bias, gelu=True, save_pre=pre)
-    assert rel(out, F.gelu(ref + bias)) < tol(dt) and rel(pre, ref + bias) < tol(dt)
-    # strided A (rows of a [B, L, H] tensor: the pooler's hidden[:, 0])
-    big = rnd((M, 3, K), dt, 5, 0.5)
-    assert rel(ops.gemm(big[:, 1], w), big[:, 1].float() @ w.float().t()) < tol(dt)
-
-
-@pytest.mark.parametrize("dt", DT)
 @pytest.mark.parametrize("M,N,K", [(32, 30522, 768), (3, 3000, 256), (64, 17, 64)])
 def test_gemm_argmax_fused(ops, dt, M, N, K):
     """mvlt_gemm_argmax: greedy pick straight from the decoder GEMM == argmax of the materialised f32 logits."""
@@ -1468,27 +1443,6 @@ def test_ragged_cross_entropy(ops, dt):
     torch.nn.functional.cross_entropy(lg, labels[:R], ignore_index=-100).backward()
     assert rel(d[:R, :V].float().cpu(), lg.grad) < tol(dt) * 2
     assert bool(torch.isnan(d[R:].float()).all())                       # untouched
-
-
-def test_skinny_accum_and_layernorm_from_accumulator(ops):
-    """Decode tails: the reduction of A W^T split over workgroups, every k-slice into a slab of its own (mvlt_gemm_skinny_accum:
-    no atomics), then LayerNorm(sum of the slabs + bias + residual) (mvlt_layernorm_acc_fwd) -- bit-reproducible."""
-    for dt in DT:
-        M, N, K = 64, 768, 3072
-        a = rnd((M, K), dt, 12, K ** -0.5); w = rnd((N, K), dt, 13)
-        bias = torch.randn(N).cuda(); res = rnd((M, N), dt, 14)
-        g = (1.0 + 0.1 * torch.randn(N)).cuda(); b = (0.1 * torch.randn(N)).cuda()
-        for splits in (1, 2, 4):
-            acc = torch.full((splits, M, N), float("nan"), device="cuda")
-            ops.gemm_skinny_accum(a, w, acc, splits)
-            ref = a.float() @ w.float().t()
-            assert rel(acc.sum(0), ref) < tol(dt)
-            y = ops.layernorm_acc_fwd(acc, bias, res, g, b, 1e-12, dt)
-            yr = torch.nn.functional.layer_norm(ref + bias + res.float(), (N,), g, b, 1e-12)
-            assert rel(y, yr) < tol(dt) * 2
-            acc2 = torch.empty_like(acc)
-            ops.gemm_skinny_accum(a, w, acc2, splits)
-            assert torch.equal(acc, acc2) and torch.equal(y, ops.layernorm_acc_fwd(acc2, bias, res, g, b, 1e-12, dt))
 
 
 @pytest.mark.parametrize("dt", DT)
