@@ -174,5 +174,27 @@ MVLT_DEV void store4f(bf16_t* p, const f32x4& v) {
     *reinterpret_cast<bf16x4*>(p) = r;
 }
 
+// ---------------------------------------------------------------- LDS-DMA, counted waits, k-major swizzle
+// LDS-DMA as inline asm (16 bytes per lane to wave-uniform lds_dst + lane * 16): hipcc must NOT know that an LDS-DMA is
+// in flight -- knowing it, it puts s_waitcnt vmcnt(0) in front of every ds_read_b64_tr_b16 (the intrinsic carries no alias
+// information), which serialises the DMA of tile t+1 with the fragment reads of tile t (gemm8.hip: drains the ring in every
+// phase).  Callers count their vmcnt by hand (wait_vmcnt).  M0 (the LDS destination) is compiler-reserved: saved and
+// restored inside the statement.
+MVLT_DEV void glds16(const void* gsrc, unsigned lds_dst) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
+}
+// at most N of this wave's vector-memory requests still outstanding (vmcnt completes in order: exactly the youngest N)
+template <int N> MVLT_DEV void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
+
+// k-major bf16 tiles of 64 / 96 / 128 rows are stored (96: in 128-wide rows) with their 32-byte column chunks XOR-swizzled by a function
+// of k: a ds_read_b64_tr_b16 group of 32 lanes reads 8 k-rows {k0..k0+3, k0+8..k0+11} x 32 bytes, which padding alone
+// cannot spread over the 64 banks (rows k and k+8 alias for every pad that keeps 32-byte chunks aligned: 2-way conflicts,
+// 32 % of the LDS cycles of the weight-gradient kernels, profiles/r2_dominant_kernel_pmc.txt).
+template <int R> MVLT_DEV int kswz(int k) {
+    return R >= 96 ? ((k & 3) | ((k >> 1) & 4)) : (((k >> 1) & 1) | ((k >> 2) & 2));
+}
+
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }

@@ -29,31 +29,20 @@ static int g8_mode() { const char* e = getenv("MVLT_G8"); return e ? atoi(e) : 2
 
 namespace {
 
-// one output tile (bx, by) of one k-split bz
-template <typename T, int BM, int BN, bool AK, bool BK_, bool PF2, int DEEP = 0, bool WIDE = false>
-MVLT_DEV void gemm_body(const GemmDev& p_in, const int bx, const int by, const int bz, T* sA, T* sB) {
-    constexpr int FM = BM / 32, FN = BN / 32;
-    const GemmDev& p = p_in;                     // (already the effective problem: see gemm_kernel / gemm_group_kernel)
-    const int m0 = by * BM, n0 = bx * BN;
-    if (m0 >= p.M) return;                       // (uniform per workgroup; only with m_dev)
+// What the tile epilogues (gemm_dev.h) do not take, fragment by fragment: k-slices (f32 slabs in the workspace for splitk_reduce_kernel, or
+// with ATOMIC and p.atomic_out straight into the zeroed f32 output) and rows the vector epilogue cannot address (epilogue4).
+// acc[i][j][r] <-> n = n_base + 16 j + 4 (lane >> 4) + r, m = m_base + 16 i + (lane & 15).  ATOMIC is compile time: the LDS-DMA
+// kernel is never launched with atomic_out and does not test it.
+template <typename T, bool ATOMIC, int FM, int FN>
+MVLT_DEV void slow_tail(const GemmDev& p, const int m_base, const int n_base, const int bz, const f32x4 (&acc)[FM][FN]) {
     const int lane = threadIdx.x & 63;
-    const int wm = (threadIdx.x >> 6) >> 1, wn = (threadIdx.x >> 6) & 1;
-    f32x4 acc[FM][FN];
-    gemm_mainloop<T, BM, BN, AK, BK_, PF2, DEEP>(p, bx, by, bz, sA, sB, acc);          // gemm_dev.h
-
-    // acc[i][j][r] <-> n = nb + 4*(lane>>4) + r, m = mb + (lane & 15)
-    if (!p.atomic_out && p.split_k <= 1 && p.epi_vec && (p.N & 3) == 0) {
-        if constexpr (WIDE && sizeof(T) == 2 && FN % 2 == 0) tile_epilogue_wide<T, FM, FN>(p, m0 + wm * (BM / 2), n0 + wn * (BN / 2), acc);
-        else tile_epilogue<T, FM, FN>(p, m0 + wm * (BM / 2), n0 + wn * (BN / 2), acc);          // loads hoisted out of the store sequence
-        return;
-    }
 #pragma unroll
     for (int i = 0; i < FM; ++i) {
-        const int m = m0 + wm * (BM / 2) + i * 16 + (lane & 15);
+        const int m = m_base + i * 16 + (lane & 15);
 #pragma unroll
         for (int j = 0; j < FN; ++j) {
-            const int n = n0 + wn * (BN / 2) + j * 16 + 4 * (lane >> 4);
-            if (p.atomic_out) {
+            const int n = n_base + j * 16 + 4 * (lane >> 4);
+            if (ATOMIC && p.atomic_out) {
                 // k-slices of one output tile meet in the f32 output itself (zeroed by the launcher): no slabs, no
                 // reduce launch; the order of the 2..8 additions per element is not fixed (last-bit differences)
                 if (m < p.M) {
@@ -72,6 +61,23 @@ MVLT_DEV void gemm_body(const GemmDev& p_in, const int bx, const int by, const i
             }
         }
     }
+}
+
+// one output tile (bx, by) of one k-split bz
+template <typename T, int BM, int BN, bool AK, bool BK_, bool PF2, int DEEP = 0, bool WIDE = false>
+MVLT_DEV void gemm_body(const GemmDev& p_in, const int bx, const int by, const int bz, T* sA, T* sB) {
+    constexpr int FM = BM / 32, FN = BN / 32;
+    const GemmDev& p = p_in;                     // (already the effective problem: see gemm_kernel / gemm_group_kernel)
+    const int m0 = by * BM, n0 = bx * BN;
+    if (m0 >= p.M) return;                       // (uniform per workgroup; only with m_dev)
+    const int wm = (threadIdx.x >> 6) >> 1, wn = (threadIdx.x >> 6) & 1;
+    f32x4 acc[FM][FN];
+    gemm_mainloop<T, BM, BN, AK, BK_, PF2, DEEP>(p, bx, by, bz, sA, sB, acc);          // gemm_dev.h
+
+    if (!p.atomic_out && p.split_k <= 1 && p.epi_vec && (p.N & 3) == 0) {
+        if constexpr (WIDE && sizeof(T) == 2 && FN % 2 == 0) tile_epilogue_wide<T, FM, FN>(p, m0 + wm * (BM / 2), n0 + wn * (BN / 2), acc);
+        else tile_epilogue<T, FM, FN>(p, m0 + wm * (BM / 2), n0 + wn * (BN / 2), acc);          // loads hoisted out of the store sequence
+    } else slow_tail<T, true>(p, m0 + wm * (BM / 2), n0 + wn * (BN / 2), bz, acc);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -96,9 +102,7 @@ MVLT_DEV void glds_fill(const bf16_t* const (&src)[R / 32], bf16_t* lds_tile, in
 // BKM: the B operand is k-major (dgrad: dx = dy W reads the [N_out, K_in] weight along its rows).  Its tile image is
 // [64 k][BN] with the 32-byte units XOR-swizzled by kswz<BN>(k) (the layout tile_frag<T, BN, true> transposes out of with
 // ds_read_b64_tr_b16); one LDS-DMA instruction covers 1 KB = 8 (BN = 64) / 4 (BN = 128) k-rows, the swizzle again on the
-// source side.  With transposing reads in the loop the DMA is issued through inline asm (glds16_asm, gemm_dev.h).
-template <int N> MVLT_DEV void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
-
+// source side.  With transposing reads in the loop the DMA is issued through inline asm (glds16, common.h).
 template <int BM, int BN, bool BKM, bool WIDE, int NST = 2>
 __global__ __launch_bounds__(256, 2) void gemm_glds_kernel(const GemmDev p_in) {
     using T = bf16_t;
@@ -157,9 +161,9 @@ __global__ __launch_bounds__(256, 2) void gemm_glds_kernel(const GemmDev p_in) {
     auto fill = [&](int stage, int kt) {
         const unsigned sa = lds0 + (unsigned)(stage * STAGE) * 2u, sb = sa + (unsigned)(BM * BKE) * 2u;
 #pragma unroll
-        for (int j = 0; j < BM / 32; ++j) glds16_asm(srcA[j] + (long)kt * BKE, sa + (wave * (BM / 32) + j) * 1024);
+        for (int j = 0; j < BM / 32; ++j) glds16(srcA[j] + (long)kt * BKE, sa + (wave * (BM / 32) + j) * 1024);
 #pragma unroll
-        for (int j = 0; j < BN / 32; ++j) glds16_asm(srcB[j] + kt * kstep_b, sb + (wave * (BN / 32) + j) * 1024);
+        for (int j = 0; j < BN / 32; ++j) glds16(srcB[j] + kt * kstep_b, sb + (wave * (BN / 32) + j) * 1024);
     };
     f32x4 acc[FM][FN];
 #pragma unroll
@@ -197,25 +201,7 @@ __global__ __launch_bounds__(256, 2) void gemm_glds_kernel(const GemmDev p_in) {
     if (p.split_k <= 1 && p.epi_vec && (p.N & 3) == 0) {
         if constexpr (WIDE && sizeof(T) == 2 && FN % 2 == 0) tile_epilogue_wide<T, FM, FN>(p, m0 + wm * (BM / 2), n0 + wn * (BN / 2), acc);
         else tile_epilogue<T, FM, FN>(p, m0 + wm * (BM / 2), n0 + wn * (BN / 2), acc);          // loads hoisted out of the store sequence
-    } else {
-#pragma unroll
-    for (int i = 0; i < FM; ++i) {
-        const int m = m0 + wm * (BM / 2) + i * 16 + (lane & 15);
-#pragma unroll
-        for (int j = 0; j < FN; ++j) {
-            const int n = n0 + wn * (BN / 2) + j * 16 + 4 * (lane >> 4);
-            if (p.split_k > 1) {
-                if (m < p.M && n < p.N) {
-                    float* w = p.ws + ((long)bz * p.M + m) * p.N + n;
-                    if ((p.N & 3) == 0) store4f(w, acc[i][j]);
-                    else for (int r = 0; r < 4; ++r) if (n + r < p.N) w[r] = acc[i][j][r];
-                }
-            } else {
-                epilogue4<T>(p, m, n, acc[i][j]);
-            }
-        }
-    }
-    }
+    } else slow_tail<T, false>(p, m0 + wm * (BM / 2), n0 + wn * (BN / 2), bz, acc);
     asm volatile("" :: "v"(pfv));
 }
 
@@ -246,14 +232,16 @@ __global__ __launch_bounds__(256, 3) void gemm_kernel(const GemmDev p) {
 // (profiles/r6_ln_bwd.md).  Here the tiles go global -> LDS by LDS-DMA in the k-major image the transposing fragment reads
 // expect ([64 k][R] with the 32-byte units XOR-swizzled by kswz<R>(k), the swizzle applied to the per-lane SOURCE address
 // exactly as gemm_glds_kernel<.., BKM> does for its B tile): no staging registers, no ds_write pass.
-//   * K tail / ragged reductions (m_dev): k-rows at or beyond the reduction length are fetched from a 256-byte page of
-//     zeros instead of the operand (a per-lane pointer select per request), for BOTH operands (0 x NaN of an unwritten
+//   * K tail / ragged reductions (m_dev): k-rows at or beyond the reduction length are fetched from a page of
+//     zeros (g_zero_page) instead of the operand (a per-lane pointer select per request), for BOTH operands (0 x NaN of an unwritten
 //     tail row would poison the sum);
 //   * bias gradient db[m] = sum_k dY[k, m]: on the matrix pipe, dY^T . 1 (one extra MFMA per A fragment and k-block in the
 //     wn = 0 waves of the first column tile of every tile row; accumulator column 0 holds the sum) -- the staging registers
 //     the register form sums from do not exist here;
-//   * two LDS stages, one barrier per k-tile, counted by hand (the DMA is inline asm: gemm_dev.h).
-__device__ __attribute__((aligned(256))) unsigned char g_zero_page[256];          // zero-initialised device memory
+//   * two LDS stages, one barrier per k-tile, counted by hand (the DMA is inline asm: common.h).
+// The library's one page of device zeros (a request reads 16 lanes x 16 bytes of it); gemm8.hip takes its address from the
+// host through mvlt_gemm_zero_page below.
+__device__ __attribute__((aligned(256))) unsigned char g_zero_page[512];
 
 template <int BM, int BN, int NST>
 MVLT_DEV void wgrad_glds_tile(const GemmDev& p, const int bx, const int by, bf16_t* smem) {
@@ -295,10 +283,10 @@ MVLT_DEV void wgrad_glds_tile(const GemmDev& p, const int bx, const int by, bf16
         const int k0 = kt * BKE;
 #pragma unroll
         for (int j = 0; j < BM / 32; ++j)
-            glds16_asm(k0 + krowA[j] < ke ? srcA[j] + (long)k0 * p.lda : zero, sa + (wave * (BM / 32) + j) * 1024);
+            glds16(k0 + krowA[j] < ke ? srcA[j] + (long)k0 * p.lda : zero, sa + (wave * (BM / 32) + j) * 1024);
 #pragma unroll
         for (int j = 0; j < BN / 32; ++j)
-            glds16_asm(k0 + krowB[j] < ke ? srcB[j] + (long)k0 * p.ldb : zero, sb + (wave * (BN / 32) + j) * 1024);
+            glds16(k0 + krowB[j] < ke ? srcB[j] + (long)k0 * p.ldb : zero, sb + (wave * (BN / 32) + j) * 1024);
     };
     f32x4 acc[FM][FN], cacc[FM];
 #pragma unroll
@@ -566,6 +554,11 @@ Plan choose_plan(const MvltGemm* p) {
 }
 
 }  // namespace
+
+extern "C" __attribute__((visibility("hidden"))) const void* mvlt_gemm_zero_page() {
+    static const void* ptr = [] { void* q = nullptr; return hipGetSymbolAddress(&q, HIP_SYMBOL(g_zero_page)) == hipSuccess ? q : nullptr; }();
+    return ptr;
+}
 
 static bool is_skinny_any(const MvltGemm* p) {
     return p->dtype == MVLT_BF16 ? is_skinny<bf16_t>(p) : (p->dtype == MVLT_F32 && is_skinny<float>(p));

@@ -31,6 +31,9 @@
 #include "gemm_host.h"
 #include <cstdlib>
 
+// gemm.hip: the library's page of device zeros
+extern "C" __attribute__((visibility("hidden"))) const void* mvlt_gemm_zero_page();
+
 namespace {
 
 typedef __attribute__((address_space(3))) void lds_void_t;
@@ -49,19 +52,6 @@ __device__ long long* g_g8_trace = nullptr;
 
 #define G8_FENCE() __builtin_amdgcn_sched_barrier(0)
 #define G8_BARRIER() do { G8_FENCE(); __builtin_amdgcn_s_barrier(); G8_FENCE(); } while (0)
-#define G8_VMCNT(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory")
-
-// LDS-DMA as inline asm: hipcc must NOT know that an LDS-DMA is in flight -- knowing it, it puts s_waitcnt vmcnt(0) in
-// front of every ds_read_b64_tr_b16 (the intrinsic carries no alias information), which drains the ring in every phase.
-// The counted vmcnt waits of the loop are all written by hand anyway.  M0 (the LDS destination) is compiler-reserved:
-// saved and restored inside the statement.  lds_dst must be wave-uniform.
-MVLT_DEV void g8_glds16(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-
-MVLT_DEV int g8_kswz(int k) { return (k & 3) | ((k >> 1) & 4); }          // == kswz<128> of gemm.hip
 
 // fragment (16 operand rows x 32 k) of a k-contiguous half-tile image [128][64]
 MVLT_DEV bf16x8 g8_frag_rm(const char* half, int row0, int kb, int lane) {
@@ -73,8 +63,8 @@ MVLT_DEV bf16x8 g8_frag_rm(const char* half, int row0, int kb, int lane) {
 MVLT_DEV bf16x8 g8_frag_km(const char* half, int row0, int kb, int lane) {
     const int g = lane >> 4, i = lane & 15, q = i >> 2, pp = i & 3;
     const int k = kb * 32 + 8 * g + q, c = row0 >> 4;
-    const char* p0 = half + k * 256 + ((c ^ g8_kswz(k)) << 5) + 8 * pp;
-    const char* p1 = half + (k + 4) * 256 + ((c ^ g8_kswz(k + 4)) << 5) + 8 * pp;
+    const char* p0 = half + k * 256 + ((c ^ kswz<128>(k)) << 5) + 8 * pp;
+    const char* p1 = half + (k + 4) * 256 + ((c ^ kswz<128>(k + 4)) << 5) + 8 * pp;
     bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)p0);
     bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)p1);
     bf16x8 r;
@@ -410,7 +400,7 @@ __global__ __launch_bounds__(512, 1) void gemm8_kernel(const G8Group gp) {
             for (int h = 0; h < MH; ++h) {
                 if constexpr (AKM) {          // instruction = 4 k-rows x 256 B; lane = (k-row, 16-byte position x)
                     const int k = (wave * 2 + j) * 4 + (lane >> 4), x = lane & 15;
-                    const int chunk = (((x >> 1) ^ g8_kswz(k)) << 1) | (x & 1);
+                    const int chunk = (((x >> 1) ^ kswz<128>(k)) << 1) | (x & 1);
                     const int col = min(by * BM + h * 128 + chunk * 8, max(q.M - 8, 0));
                     is.pa[h][j] = A + (long)k * q.lda + col;
                 } else {                      // instruction = 8 rows x 128 B; lane = (row, chunk')
@@ -423,7 +413,7 @@ __global__ __launch_bounds__(512, 1) void gemm8_kernel(const G8Group gp) {
             for (int h = 0; h < NH; ++h) {
                 if constexpr (BKM) {
                     const int k = (wave * 2 + j) * 4 + (lane >> 4), x = lane & 15;
-                    const int chunk = (((x >> 1) ^ g8_kswz(k)) << 1) | (x & 1);
+                    const int chunk = (((x >> 1) ^ kswz<128>(k)) << 1) | (x & 1);
                     const int col = min(bx * BN + h * 128 + chunk * 8, max(q.N - 8, 0));
                     is.pb[h][j] = B + (long)k * q.ldb + col;
                 } else {
@@ -460,7 +450,7 @@ __global__ __launch_bounds__(512, 1) void gemm8_kernel(const G8Group gp) {
                 }
             }
 #ifndef G8_NO_GLDS          /* ablation build: no LDS-DMA (stale LDS is multiplied; outputs wrong) */
-            g8_glds16(src, slot + j * 1024);
+            glds16(src, slot + j * 1024);
 #else
             asm volatile("" :: "v"(src), "s"(slot));
 #endif
@@ -475,17 +465,17 @@ __global__ __launch_bounds__(512, 1) void gemm8_kernel(const G8Group gp) {
         issue(0, is.kt, 0); issue(1, is.kt, 0); issue(2, is.kt, 0); issue(3, is.kt, 0);
         advance();
         issue(0, is.kt, 1);
-        G8_VMCNT(6);
+        wait_vmcnt<6>();
     } else if constexpr (HPK == 3) {           // K-tiles 0 and 1; A0, B0 of K-tile 0 must have landed
         issue(0, is.kt, 0); issue(1, is.kt, 0); issue(MH == 2 ? 3 : 2, is.kt, 0);
         advance();
         issue(0, is.kt, 1); issue(1, is.kt, 1); issue(MH == 2 ? 3 : 2, is.kt, 1);
-        G8_VMCNT(8);
+        wait_vmcnt<8>();
     } else {
         issue(0, is.kt, 0); issue(1, is.kt, 0);
         advance();
         issue(0, is.kt, 1); issue(1, is.kt, 1);
-        G8_VMCNT(4);
+        wait_vmcnt<4>();
     }
     G8_STAMP(2);
     G8_BARRIER();
@@ -545,36 +535,36 @@ __global__ __launch_bounds__(512, 1) void gemm8_kernel(const G8Group gp) {
             if constexpr (MH == 2 && NH == 2) {
                 // slots A0 B0 B1 A1; phases (0,0) (0,1) (1,1) (1,0); one half-tile issued per phase, 5 half-tiles ahead
                 G8_READ_B(fb0, 1); G8_READ_A(0);
-                G8_FENCE(); issue(1, is.kt, (g + 1) % RING_KT); G8_VMCNT(6);
+                G8_FENCE(); issue(1, is.kt, (g + 1) % RING_KT); wait_vmcnt<6>();
                 G8_BARRIER(); G8_MMA(acc[0][0], fb0); G8_CS(0); G8_BARRIER();
                 G8_READ_B(fb1, 2);
-                G8_FENCE(); issue(2, is.kt, (g + 1) % RING_KT); G8_VMCNT(6);
+                G8_FENCE(); issue(2, is.kt, (g + 1) % RING_KT); wait_vmcnt<6>();
                 G8_BARRIER(); G8_MMA(acc[0][1], fb1); G8_BARRIER();
                 G8_READ_A(3);
-                G8_FENCE(); issue(3, is.kt, (g + 1) % RING_KT); G8_VMCNT(6);
+                G8_FENCE(); issue(3, is.kt, (g + 1) % RING_KT); wait_vmcnt<6>();
                 G8_BARRIER(); G8_MMA(acc[1][1], fb1); G8_CS(MH - 1); G8_BARRIER();
-                advance(); issue(0, is.kt, d); G8_VMCNT(6);
+                advance(); issue(0, is.kt, d); wait_vmcnt<6>();
                 G8_BARRIER(); G8_MMA(acc[1][0], fb0); G8_BARRIER();
             } else if constexpr (MH == 1 && NH == 2) {
                 // slots A0 B0 B1; phases (0,0) (0,1); K-tile g+2 is issued while K-tile g is multiplied
                 G8_READ_B(fb0, 1); G8_READ_A(0);
-                G8_FENCE(); advance(); issue(0, is.kt, (g + 2) % RING_KT); issue(1, is.kt, (g + 2) % RING_KT); G8_VMCNT(10);
+                G8_FENCE(); advance(); issue(0, is.kt, (g + 2) % RING_KT); issue(1, is.kt, (g + 2) % RING_KT); wait_vmcnt<10>();
                 G8_BARRIER(); G8_MMA(acc[0][0], fb0); G8_CS(0); G8_BARRIER();
                 G8_READ_B(fb1, 2);
-                G8_FENCE(); issue(2, is.kt, (g + 2) % RING_KT); G8_VMCNT(8);
+                G8_FENCE(); issue(2, is.kt, (g + 2) % RING_KT); wait_vmcnt<8>();
                 G8_BARRIER(); G8_MMA(acc[0][1], fb1); G8_BARRIER();
             } else if constexpr (MH == 2 && NH == 1) {
                 // slots A0 B0 A1; phases (0,0) (1,0)
                 G8_READ_B(fb0, 1); G8_READ_A(0);
-                G8_FENCE(); advance(); issue(0, is.kt, (g + 2) % RING_KT); issue(1, is.kt, (g + 2) % RING_KT); G8_VMCNT(10);
+                G8_FENCE(); advance(); issue(0, is.kt, (g + 2) % RING_KT); issue(1, is.kt, (g + 2) % RING_KT); wait_vmcnt<10>();
                 G8_BARRIER(); G8_MMA(acc[0][0], fb0); G8_CS(0); G8_BARRIER();
                 G8_READ_A(2);
-                G8_FENCE(); issue(3, is.kt, (g + 2) % RING_KT); G8_VMCNT(8);
+                G8_FENCE(); issue(3, is.kt, (g + 2) % RING_KT); wait_vmcnt<8>();
                 G8_BARRIER(); G8_MMA(acc[1][0], fb0); G8_CS(MH - 1); G8_BARRIER();
             } else {
                 // slots A0 B0; one phase; K-tile g+2 is issued while K-tile g is multiplied (ring of 4)
                 G8_READ_B(fb0, 1); G8_READ_A(0);
-                G8_FENCE(); advance(); issue(0, is.kt, (g + 2) % RING_KT); issue(1, is.kt, (g + 2) % RING_KT); G8_VMCNT(4);
+                G8_FENCE(); advance(); issue(0, is.kt, (g + 2) % RING_KT); issue(1, is.kt, (g + 2) % RING_KT); wait_vmcnt<4>();
                 G8_BARRIER(); G8_MMA(acc[0][0], fb0); G8_CS(0); G8_BARRIER();
             }
 #undef G8_CS
@@ -622,17 +612,17 @@ __global__ __launch_bounds__(512, 1) void gemm8_kernel(const G8Group gp) {
                         gp.cs_slabs[((long)un.tile * S + un.slice) * BM + a * 128 + wr * 64 + wc * 16 + lane] = cs[a][0];
                 }
             }
-            G8_VMCNT(0);
+            wait_vmcnt<0>();
             G8_BARRIER();
             if (threadIdx.x == 0) {
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-                G8_VMCNT(0);
+                wait_vmcnt<0>();
                 eff_lds[8] = __hip_atomic_fetch_add(gp.counters + un.tile, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             G8_BARRIER();
             finish = __builtin_amdgcn_readfirstlane(eff_lds[8]) == S - 1;
             if (finish) {
-                if (threadIdx.x == 0) { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); G8_VMCNT(0); }
+                if (threadIdx.x == 0) { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); wait_vmcnt<0>(); }
                 G8_BARRIER();
 #pragma unroll
                 for (int a = 0; a < MH; ++a)
@@ -687,12 +677,9 @@ __global__ __launch_bounds__(512, 1) void gemm8_kernel(const G8Group gp) {
     }
     if (wr == 0) G8_BARRIER();                                            // balance group 1's extra barrier
     G8_STAMP(6);
-    G8_VMCNT(0);                                                          // the overrun issues land before the LDS is released
+    wait_vmcnt<0>();                                                          // the overrun issues land before the LDS is released
     G8_STAMP(7);
 }
-
-// 512 zero bytes for the reduction rows beyond a ragged K (k-major A operand)
-__device__ __attribute__((aligned(256))) unsigned char g8_zero_page[512];
 
 // Persistent workgroups of a weight-gradient launch: HALF the CUs.  These launches run on the side stream beside the dgrad chain,
 // and one 8-wave workgroup takes a CU's whole LDS and register file: with 256 of them the chain's kernels found no CU at all while
@@ -732,11 +719,6 @@ int g8_launch(const G8Group& gp, long units, hipStream_t s, int* route) {
         if (wide) return g8_launch1<MH, NH, AKM, BKM, EPI, true>(gp, units, s, route);
     }
     return g8_launch1<MH, NH, AKM, BKM, EPI, false>(gp, units, s, route);
-}
-
-const void* g8_zero_ptr() {
-    static const void* ptr = [] { void* q = nullptr; return hipGetSymbolAddress(&q, HIP_SYMBOL(g8_zero_page)) == hipSuccess ? q : nullptr; }();
-    return ptr;
 }
 
 template <int MH, int NH>
@@ -856,7 +838,7 @@ extern "C" __attribute__((visibility("hidden"))) int mvlt_gemm8_try(const void* 
         gp.g[i] = d[i];
         gp.colsum[i] = colsum ? colsum[i] : nullptr;
     }
-    gp.zero_page = g8_zero_ptr();
+    gp.zero_page = mvlt_gemm_zero_page();          // reduction rows beyond a ragged K (k-major A operand)
     if (a_kmajor && !gp.zero_page) return 0;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (a_kmajor && b_kmajor) {

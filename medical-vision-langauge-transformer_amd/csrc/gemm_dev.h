@@ -359,16 +359,6 @@ MVLT_DEV void tile_epilogue_wide(const GemmDev& p, const int m_base, const int n
     }
 }
 
-// LDS-DMA as inline asm (16 bytes per lane to wave-uniform lds_dst + lane * 16): hipcc must NOT know that an LDS-DMA is
-// in flight -- knowing it, it puts s_waitcnt vmcnt(0) in front of every ds_read_b64_tr_b16 (the intrinsic carries no alias
-// information), which serialises the DMA of tile t+1 with the fragment reads of tile t.  Callers count their vmcnt by
-// hand.  M0 (the LDS destination) is compiler-reserved: saved and restored inside the statement.
-MVLT_DEV void glds16_asm(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-
 // XCD-aware tile order: workgroups are dealt round-robin to the 8 XCDs (each with its own
 // L2), so give every XCD one contiguous chunk of the tile list -> neighbouring tiles (same
 // A rows / B columns) hit the same L2.  Bijective for any count; speed only.
@@ -403,13 +393,6 @@ MVLT_DEV unsigned prefetch_lines(const GemmDev& p) {
     return acc;
 }
 
-// k-major bf16 tiles of 64 / 96 / 128 rows are stored (96: in 128-wide rows) with their 32-byte column chunks XOR-swizzled by a function
-// of k: a ds_read_b64_tr_b16 group of 32 lanes reads 8 k-rows {k0..k0+3, k0+8..k0+11} x 32 bytes, which padding alone
-// cannot spread over the 64 banks (rows k and k+8 alias for every pad that keeps 32-byte chunks aligned: 2-way conflicts,
-// 32 % of the LDS cycles of the weight-gradient kernels, profiles/r2_dominant_kernel_pmc.txt).
-template <int R> MVLT_DEV int kswz(int k) {
-    return R >= 96 ? ((k & 3) | ((k >> 1) & 4)) : (((k >> 1) & 1) | ((k >> 2) & 2));
-}
 template <typename T, int R, bool KMAJOR> struct TileGeom {
     static constexpr int E = TypeInfo<T>::E;
     static constexpr int BKE = 128 / (int)sizeof(T);          // k elements per tile

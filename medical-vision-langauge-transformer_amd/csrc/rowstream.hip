@@ -66,11 +66,10 @@ MVLT_DEV void rs_barrier() {
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 }
-template <int N> MVLT_DEV void rs_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
 // wait until at most rem * NIW of this wave's LDS-DMA instructions are outstanding (rem <= MAXR, wave-uniform)
 template <int NIW, int MAXR> MVLT_DEV void rs_wait_rem(int rem) {
-    if constexpr (MAXR == 0) rs_vmcnt<0>();
-    else { if (rem >= MAXR) rs_vmcnt<(MAXR * NIW)>(); else rs_wait_rem<NIW, MAXR - 1>(rem); }
+    if constexpr (MAXR == 0) wait_vmcnt<0>();
+    else { if (rem >= MAXR) wait_vmcnt<(MAXR * NIW)>(); else rs_wait_rem<NIW, MAXR - 1>(rem); }
 }
 
 // ---- bank-conflict-free row images (round 6).  A stage's rows land in LDS by LDS-DMA, which writes base + 16 lane: the image is
@@ -162,10 +161,10 @@ __global__ __launch_bounds__((2 * WN + 2) * 64) void rowstream_kernel(const RsAr
                 if (idx < NIX) {                                      // activation rows: one contiguous block, chunks swizzled inside each row
                     const int q = idx * 64 + lane, r = q / (K / 8), pos = q - r * (K / 8);
                     const long off = (long)(r0 + r) * K + RsSwz<K / 8>::template chunk<false>(r, pos) * 8;
-                    glds16_asm(X + (off < xlast ? off : xlast), slot + idx * 1024);
+                    glds16(X + (off < xlast ? off : xlast), slot + idx * 1024);
                 } else if constexpr (X2) {                            // row operand of the epilogue: [32, N] of an ld-strided matrix
                     const int q = (idx - NIX) * 64 + lane, r = q / (N / 8), pos = q - r * (N / 8);
-                    glds16_asm(E + (long)min(r0 + r, rows - 1) * lde + col0 + RsSwz<N / 8>::template chunk<true>(r, pos) * 8, slot + idx * 1024);
+                    glds16(E + (long)min(r0 + r, rows - 1) * lde + col0 + RsSwz<N / 8>::template chunk<true>(r, pos) * 8, slot + idx * 1024);
                 }
             }
         };
@@ -176,7 +175,7 @@ __global__ __launch_bounds__((2 * WN + 2) * 64) void rowstream_kernel(const RsAr
 #pragma unroll
             for (int j = 0; j < NIWW; ++j) {
                 const int idx = 2 * j + lw, q = idx * 64 + lane, k = q / (N / 8), pos = q - k * (N / 8);
-                glds16_asm(W + (long)k * p.ldb + col0 + (pos ^ rs_wswz<N>(k)) * 8, wdst + idx * 1024);
+                glds16(W + (long)k * p.ldb + col0 + (pos ^ rs_wswz<N>(k)) * 8, wdst + idx * 1024);
             }
             for (int s = 0; s < D0; ++s) if (s < ns) issue(s);
             rs_wait_rem<NIW, D0>(ns < D0 ? ns : D0);                  // the weight image has landed

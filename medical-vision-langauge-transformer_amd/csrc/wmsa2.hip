@@ -93,13 +93,8 @@ template <int CC> MVLT_DEV int xoff(int row, int chunk) {
 MVLT_DEV int hoff(int row, int chunk) { return row * 64 + (((chunk + 2 * (row >> 2)) & 3) << 4); }
 
 MVLT_DEV void vm_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-// LDS-DMA, 16 bytes per lane to wave-uniform lds_dst + 16 lane (inline asm: M0 saved and restored inside the statement; hipcc
-// does not see the request, the callers wait for it with vm_drain before the barrier that publishes the bytes)
-MVLT_DEV void glds16(const void* gsrc, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
+// LDS-DMA (glds16, common.h): hipcc does not see the request, the callers wait for it with vm_drain before the barrier that
+// publishes the bytes
 
 
 // -DW2_TRACE (diagnostic build only): thread 0 of every workgroup stamps the 100 MHz real-time counter at the phase
@@ -233,12 +228,12 @@ __global__ __launch_bounds__(64 * NWV) void wmsa2_fwd_kernel(const Wmsa2Dev p) {
         // wait until this wave's pieces of k-step kk have landed while `later` younger k-steps stay in flight
         auto wring_wait = [&](int later) {
             if (wpc == WPPW) {
-                if (later >= 2) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * WPPW) : "memory");
-                else if (later == 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(WPPW) : "memory");
+                if (later >= 2) wait_vmcnt<2 * WPPW>();
+                else if (later == 1) wait_vmcnt<WPPW>();
                 else vm_drain();
             } else {
-                if (later >= 2) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * (WPPW - 1)) : "memory");
-                else if (later == 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(WPPW - 1) : "memory");
+                if (later >= 2) wait_vmcnt<2 * (WPPW - 1)>();
+                else if (later == 1) wait_vmcnt<WPPW - 1>();
                 else vm_drain();
             }
         };

@@ -76,24 +76,17 @@ template <int CC> MVLT_DEV int xoff(int row, int chunk) {
     constexpr int GRP = CPR % 16 == 0 ? 16 : (CPR % 8 == 0 ? 8 : 4);
     return row * (CC * 2) + (((chunk & ~(GRP - 1)) | ((chunk ^ row) & (GRP - 1))) << 4);
 }
-MVLT_DEV int kswz8(int k) { return (k & 3) | ((k >> 1) & 4); }
 typedef __attribute__((address_space(3))) char lds_char;
 MVLT_DEV uint32_t lds_addr(const void* q) { return (uint32_t)(uintptr_t)(lds_char*)q; }
-MVLT_DEV void glds16(const void* gsrc, unsigned lds_dst) {          // LDS-DMA, 16 bytes per lane to lds_dst + 16 lane
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-template <int N> MVLT_DEV void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
 
 // first-operand fragment (rows n0 .. n0 + 15, k-slots 8 g .. 8 g + 7 of the 32 k-rows) of a k-major image [32][LD] whose 32-byte
-// units are swizzled by kswz8(k) -- the layout the ring fills below produce
+// units are swizzled by kswz<128>(k) -- the layout the ring fills below produce
 template <int LD> MVLT_DEV bf16x8 kfrag(const char* img, int n0) {
     const int l = threadIdx.x & 63;
     const int g = l >> 4, i = l & 15, q = i >> 2, pp = i & 3;
     const int k = 8 * g + q, c = n0 >> 4;
-    const char* p0 = img + k * (LD * 2) + ((c ^ kswz8(k)) << 5) + 8 * pp;
-    const char* p1 = img + (k + 4) * (LD * 2) + ((c ^ kswz8(k + 4)) << 5) + 8 * pp;
+    const char* p0 = img + k * (LD * 2) + ((c ^ kswz<128>(k)) << 5) + 8 * pp;
+    const char* p1 = img + (k + 4) * (LD * 2) + ((c ^ kswz<128>(k + 4)) << 5) + 8 * pp;
     const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)p0);
     const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)p1);
     bf16x8 r;
@@ -106,7 +99,7 @@ template <int LD> MVLT_DEV bf16x8 kfrag(const char* img, int n0) {
 template <int LD> MVLT_DEV void ring_piece(const T* src, long src_ld, int cols, int piece, int lane, unsigned dst_stage) {
     constexpr int CPRW = LD / 8;                            // 16-byte chunks per image row
     const int f = 64 * piece + lane, r = f / CPRW, x = f - r * CPRW;
-    const int ch = (((x >> 1) ^ kswz8(r)) << 1) | (x & 1);
+    const int ch = (((x >> 1) ^ kswz<128>(r)) << 1) | (x & 1);
     glds16(src + (long)r * src_ld + (ch * 8 < cols ? ch * 8 : 0), dst_stage + piece * 1024);
 }
 
@@ -256,7 +249,7 @@ __global__ __launch_bounds__(512) void wmsa2_bwd_kernel(const Wb2Dev p) {
                 // younger stages of THIS wave that may still be in flight (PW1 pieces each): all NST1 slots were requested up front,
                 // step kk >= 1 refills the slot of stage kk - 1
                 const int ahead = min(kk == 0 ? GM::NST1 - 1 : GM::NST1 - 2, NK1 - 1 - kk);
-                if (ahead >= 3) wait_vm<3 * PW1>(); else if (ahead == 2) wait_vm<2 * PW1>(); else if (ahead == 1) wait_vm<PW1>(); else wait_vm<0>();
+                if (ahead >= 3) wait_vmcnt<3 * PW1>(); else if (ahead == 2) wait_vmcnt<2 * PW1>(); else if (ahead == 1) wait_vmcnt<PW1>(); else wait_vmcnt<0>();
                 __syncthreads();
                 if (kk >= 1 && kk + GM::NST1 - 1 < NK1) fill1(kk + GM::NST1 - 1);
                 if (wave < OC / 16) {
@@ -445,7 +438,7 @@ __global__ __launch_bounds__(512) void wmsa2_bwd_kernel(const Wb2Dev p) {
                 for (int mt = 0; mt < GM::MT; ++mt) acc[ct][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll 1
             for (int kk = 0; kk < KS3; ++kk) {
-                if (kk + GM::NST3 - 2 < KS3) wait_vm<(GM::NST3 - 2) * PW3>(); else wait_vm<0>();
+                if (kk + GM::NST3 - 2 < KS3) wait_vmcnt<(GM::NST3 - 2) * PW3>(); else wait_vmcnt<0>();
                 __syncthreads();
                 if (kk + GM::NST3 - 1 < KS3) fill3(kk + GM::NST3 - 1);
                 const char* st = regA + (kk % GM::NST3 == 0 ? GM::SLOT0 : (kk % GM::NST3 - 1) * GM::ST3);

@@ -114,6 +114,14 @@ ROUTES = [
     # decoder weight gradient: both k-major, f32 out, a_colsum, m_dev = reduction; ragged last row tile (30522 % 128)
     R("mlm-decoder-wgrad", BF, 30522, 768, 2560, ak=True, bk=True, pad=(6, 0, 0), epi=("f32", "colsum"), mdev=RD,
       plan=(128, 128, 1)),
+    # ---- arms of the tile epilogues (csrc/gemm_dev.h) the rows above do not reach: the row map (the Swin projection scatter)
+    #      through tile_epilogue_wide and tile_epilogue, and the in-place accumulate of a bf16 output through tile_epilogue.
+    #      Three row tiles of 64 with a partial last row block (150 = 2 x 64 + 16 + 6: the clamped rows are read); forward
+    #      rule -> 64 x 64 tiles, 2 k-tiles: no k-slices.  (wide = N % 8 == 0 and ldc % 8 == 0, as in the first block above)
+    R("glds64x64-wide-rowmap", BF, 150, 256, 128, epi=("bias", "rowscale", "residual", "rowmap"), plan=(64, 64, 1), route="GLDS"),
+    R("glds64x64-narrow-rowmap", BF, 150, 192, 128, pad=(0, 0, 4), epi=("bias", "rowscale", "rowmap"), plan=(64, 64, 1),
+      route="GLDS"),                                                          # ldc % 8 == 4: 8 bytes per lane
+    R("reg64x64-accum", BF, 150, 192, 96, epi=("bias", "accum"), plan=(64, 64, 1), route="REG"),   # K % 64 != 0: register-staged
     # ---- gemm_skinny_kernel<T, false> (csrc/skinny.hip; gemm_host.h is_skinny + skinny_loads_ok: M <= 64, both operands
     #      k-contiguous, K % k-block == 0 (32 in bf16, 16 in f32), no split, lda / ldb % 8 (f32: 4) == 0, 16-byte aligned).
     #      A workgroup = 16 columns x all rows; 8 waves x 3 k-blocks in flight; fast_epi = only bias / GELU / residual bits,
