@@ -43,7 +43,8 @@ enum { MVLT_STRUCT_GEMM = 0, MVLT_STRUCT_LAYERNORM = 1, MVLT_STRUCT_LAYERNORM_BW
        MVLT_STRUCT_ATTN = 4, MVLT_STRUCT_SWIN_WMSA = 5, MVLT_STRUCT_EMBED = 6, MVLT_STRUCT_ATTN_CACHED = 7,
        MVLT_STRUCT_ZERO_ITEM = 8, MVLT_STRUCT_RANGE = 9, MVLT_STRUCT_MLM_MASK = 10, MVLT_STRUCT_GREEDY_STATE = 11, MVLT_STRUCT_SWIN_DBIAS_ITEM = 12,
        MVLT_STRUCT_SAMPLE_STATE = 13, MVLT_STRUCT_SAMPLE_FILTER = 14, MVLT_STRUCT_BEAM_CAND = 15, MVLT_STRUCT_ATTN_CACHED_BEAM = 16,
-       MVLT_STRUCT_HEAD_CE = 17, MVLT_STRUCT_RETRIEVAL_HEAD = 18, MVLT_STRUCT_BEAM_STEP = 19, MVLT_STRUCT_COUNT = 20 };
+       MVLT_STRUCT_HEAD_CE = 17, MVLT_STRUCT_RETRIEVAL_HEAD = 18, MVLT_STRUCT_BEAM_STEP = 19,
+       MVLT_STRUCT_LOGIT_RULES = 20, MVLT_STRUCT_COUNT = 21 };
 size_t mvlt_sizeof(int struct_id);
 
 /* ------------------------------------------------------------------ GEMM
@@ -213,6 +214,43 @@ int mvlt_gemm_sample_filtered(const MvltGemm* p, float* part_val, int32_t* part_
 /* The graph form: mvlt_gemm_sample_step (same state, same seed / tag0 + column convention) with the filtered pick. */
 int mvlt_gemm_sample_filtered_step(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltSampleFilter* filter,
                                    const MvltSampleState* g, void* stream);
+/* Logit rules of constrained decoding (HF RepetitionPenaltyLogitsProcessor, NoRepeatNGramLogitsProcessor, MinLengthLogitsProcessor),
+ * applied to the raw logits inside the head kernels, before temperature and top-k / top-p.  Per row m: c = *col tokens generated so
+ * far, h = ids[m, 0 .. c-1] exactly as stored (PAD of a finished row included), x = acc + bias in f32.
+ *   seen(n)    n occurs in h.  x' = x < 0 ? x * penalty : x / penalty, applied once however often n occurs (penalty > 0; 1.0: off)
+ *   banned(n)  n-grams (g = ngram >= 1 and c + 1 >= g): some i <= c - g has h[i .. i+g-2] == h[c-g+1 .. c-1] and h[i+g-1] == n
+ *              (g = 1 bans every seen token); min length (has_eos and c < min_length): n == eos_id
+ * A banned column takes part in nothing -- not in the maximum, the log-sum-exp, the Gumbel draw or the top-k / top-p sets -- and
+ * is never returned; the filtered route stores -inf for it.  The recorded scores follow the processed logits.  At most c + 1
+ * columns of a row are banned: the caller keeps N > the longest history so that a row always has a column left.
+ * Two launches share the struct.  The PLAN (one workgroup per row, M <= 64) rebuilds `seen` and `banned` from ids / col: bitmaps of
+ * ld_words >= ceil(V / 32) uint32 words per row, bit n & 31 of word n >> 5 = column n.  The rebuild is stateless (clear, then set):
+ * nothing carries over between tokens or calls, so a replayed graph has nothing to reset.  ids outside [0, V) set no bit.
+ * The _rules HEADS are the six head entry points above with the bitmaps and `penalty` applied in their epilogues; they read
+ * seen / banned / ld_words / penalty only (the caller runs the plan first, on the same stream).
+ * Refusals (MVLT_ERR_ARG, nothing launched, nothing written), ahead of the base entry point's own: rules, seen or banned NULL,
+ * ld_words < ceil(N / 32), penalty <= 0 or NaN, ngram < 0, M > 64 (M < 1); the plan also refuses ids or col NULL, ld_ids < 1,
+ * V < 1, min_length < 0. */
+typedef struct MvltLogitRules {
+    uint32_t* seen; uint32_t* banned; int64_t ld_words;       /* [M, ld_words] each */
+    float penalty;
+    const int64_t* ids; int64_t ld_ids; const int64_t* col;   /* the plan's history: ids[m, 0 .. *col - 1] */
+    int32_t ngram, min_length; int64_t eos_id; int32_t has_eos;
+} MvltLogitRules;
+int mvlt_decode_rules_plan(const MvltLogitRules* rules, int M, int V, void* stream);
+int mvlt_gemm_argmax_rules(const MvltGemm* p, float* part_val, int32_t* part_idx, int64_t* out_idx, float* out_val,
+                           const MvltLogitRules* rules, void* stream);
+int mvlt_gemm_argmax_greedy_rules(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltGreedyState* g,
+                                  const MvltLogitRules* rules, void* stream);
+int mvlt_gemm_sample_rules(const MvltGemm* p, float* part_val, int32_t* part_idx, int64_t* out_idx, float* out_logprob,
+                           uint64_t seed, uint32_t tag, float inv_temperature, const MvltLogitRules* rules, void* stream);
+int mvlt_gemm_sample_step_rules(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltSampleState* g,
+                                const MvltLogitRules* rules, void* stream);
+int mvlt_gemm_sample_filtered_rules(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltSampleFilter* filter,
+                                    int64_t* out_idx, float* out_logprob, uint64_t seed, uint32_t tag, float inv_temperature,
+                                    const MvltLogitRules* rules, void* stream);
+int mvlt_gemm_sample_filtered_step_rules(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltSampleFilter* filter,
+                                         const MvltSampleState* g, const MvltLogitRules* rules, void* stream);
 /* Last-row MLM head fused with the candidate step of beam search (model.py:700-720: log_softmax + beam score, top 2 * beams over
  * (beam, token)).  The M = G * num_beams rows of the product are the hypotheses of G samples, rows g * num_beams .. + num_beams
  * the beams of sample g.  Per row m, all in f32 with no fused multiply-add:

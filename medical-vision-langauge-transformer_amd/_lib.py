@@ -150,6 +150,11 @@ class MvltBeamCand(C.Structure):
                 ("cand_score", vp), ("cand_beam", vp), ("cand_tok", vp), ("lse", vp)]
 
 
+class MvltLogitRules(C.Structure):
+    _fields_ = [("seen", vp), ("banned", vp), ("ld_words", i64), ("penalty", f32), ("ids", vp), ("ld_ids", i64), ("col", vp),
+                ("ngram", i32), ("min_length", i32), ("eos_id", i64), ("has_eos", i32)]
+
+
 class MvltAttnCachedBeam(C.Structure):
     _fields_ = MvltAttnCached._fields_[:1] + [("rows", i32)] + MvltAttnCached._fields_[2:] + [
         ("num_beams", i32), ("prefix", i32), ("slot", vp), ("ld_slot", i64)]
@@ -192,6 +197,15 @@ SYMBOLS = {
     "mvlt_gemm_sample_step": (i32, [C.POINTER(MvltGemm), vp, vp, C.POINTER(MvltSampleState), vp]),
     "mvlt_gemm_sample_filtered": (i32, [C.POINTER(MvltGemm), vp, vp, C.POINTER(MvltSampleFilter), vp, vp, u64, u32, f32, vp]),
     "mvlt_gemm_sample_filtered_step": (i32, [C.POINTER(MvltGemm), vp, vp, C.POINTER(MvltSampleFilter), C.POINTER(MvltSampleState), vp]),
+    "mvlt_decode_rules_plan": (i32, [C.POINTER(MvltLogitRules), i32, i32, vp]),
+    "mvlt_gemm_argmax_rules": (i32, [C.POINTER(MvltGemm), vp, vp, vp, vp, C.POINTER(MvltLogitRules), vp]),
+    "mvlt_gemm_argmax_greedy_rules": (i32, [C.POINTER(MvltGemm), vp, vp, C.POINTER(MvltGreedyState), C.POINTER(MvltLogitRules), vp]),
+    "mvlt_gemm_sample_rules": (i32, [C.POINTER(MvltGemm), vp, vp, vp, vp, u64, u32, f32, C.POINTER(MvltLogitRules), vp]),
+    "mvlt_gemm_sample_step_rules": (i32, [C.POINTER(MvltGemm), vp, vp, C.POINTER(MvltSampleState), C.POINTER(MvltLogitRules), vp]),
+    "mvlt_gemm_sample_filtered_rules": (i32, [C.POINTER(MvltGemm), vp, vp, C.POINTER(MvltSampleFilter), vp, vp, u64, u32, f32,
+                                            C.POINTER(MvltLogitRules), vp]),
+    "mvlt_gemm_sample_filtered_step_rules": (i32, [C.POINTER(MvltGemm), vp, vp, C.POINTER(MvltSampleFilter), C.POINTER(MvltSampleState),
+                                                 C.POINTER(MvltLogitRules), vp]),
     "mvlt_gemm_beam_candidates": (i32, [C.POINTER(MvltGemm), C.POINTER(MvltBeamCand), vp]),
     "mvlt_mlm_head_ce": (i32, [C.POINTER(MvltGemm), C.POINTER(MvltHeadCE), vp]),
     "mvlt_mlm_head_ce_workspace_bytes": (sz, [i32, i32]),
@@ -262,7 +276,8 @@ SYMBOLS = {
 # ctypes mirror of every struct, in the order of the MVLT_STRUCT_* ids of the header
 STRUCTS = [MvltGemm, MvltLayerNorm, MvltLayerNormBwd, MvltLnReduceItem, MvltAttn, MvltSwinWmsa, MvltEmbed,
            MvltAttnCached, MvltZeroItem, MvltRange, MvltMlmMask, MvltGreedyState, MvltSwinDbiasItem,
-           MvltSampleState, MvltSampleFilter, MvltBeamCand, MvltAttnCachedBeam, MvltHeadCE, MvltRetrievalHead, MvltBeamStep]
+           MvltSampleState, MvltSampleFilter, MvltBeamCand, MvltAttnCachedBeam, MvltHeadCE, MvltRetrievalHead, MvltBeamStep,
+           MvltLogitRules]
 
 _lib = None
 

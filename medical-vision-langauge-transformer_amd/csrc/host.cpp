@@ -590,6 +590,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                                     (int64_t)sizeof(MvltRange), (int64_t)sizeof(MvltMlmMask), (int64_t)sizeof(MvltGreedyState),
                                     (int64_t)sizeof(MvltSwinDbiasItem), (int64_t)sizeof(MvltSampleState), (int64_t)sizeof(MvltSampleFilter),
                                     (int64_t)sizeof(MvltBeamCand), (int64_t)sizeof(MvltAttnCachedBeam), (int64_t)sizeof(MvltHeadCE),
-                                    (int64_t)sizeof(MvltRetrievalHead), (int64_t)sizeof(MvltBeamStep)};
+                                    (int64_t)sizeof(MvltRetrievalHead), (int64_t)sizeof(MvltBeamStep), (int64_t)sizeof(MvltLogitRules)};
     });
 }

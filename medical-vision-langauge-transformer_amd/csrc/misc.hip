@@ -876,6 +876,7 @@ extern "C" size_t mvlt_sizeof(int struct_id) {
         case MVLT_STRUCT_HEAD_CE: return sizeof(MvltHeadCE);
         case MVLT_STRUCT_RETRIEVAL_HEAD: return sizeof(MvltRetrievalHead);
         case MVLT_STRUCT_BEAM_STEP: return sizeof(MvltBeamStep);
+        case MVLT_STRUCT_LOGIT_RULES: return sizeof(MvltLogitRules);
         default: return 0;
     }
 }

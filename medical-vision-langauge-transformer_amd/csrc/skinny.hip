@@ -2,7 +2,8 @@
 // (mvlt_gemm_skinny_accum), and the MLM head fused with the pick of the next token -- greedy (mvlt_gemm_argmax,
 // mvlt_gemm_argmax_greedy), sampled (mvlt_gemm_sample, mvlt_gemm_sample_step) and sampled behind a top-k / top-p filter
 // (mvlt_gemm_sample_filtered, mvlt_gemm_sample_filtered_step) -- and the candidate step of beam search
-// (mvlt_gemm_beam_candidates: log-softmax + beam score + top-n per sample).  No LDS staging in the products: the weight matrix is
+// (mvlt_gemm_beam_candidates: log-softmax + beam score + top-n per sample).  The six picks also come with the logit rules of
+// constrained decoding in their epilogues (mvlt_gemm_*_rules, fed by mvlt_decode_rules_plan).  No LDS staging in the products: the weight matrix is
 // read once and nothing is reused inside a workgroup, so every wave loads its MFMA fragments straight from global memory.
 // Same argument block as the tile kernels of gemm.hip (gemm_dev.h); gemm.hip reaches the plain product through mvlt_skinny_try.
 #include "common.h"
@@ -209,14 +210,65 @@ __global__ __launch_bounds__(64) void argmax_parts_kernel(const float* part_val,
     if (threadIdx.x == 0) { out_idx[blockIdx.x] = bi; if (out_val) out_val[blockIdx.x] = best; }
 }
 
+// LOGIT RULES (mvlt_hip.h MvltLogitRules: repetition penalty, no-repeat n-grams, min length).  Two bitmaps per row, `seen` and
+// `banned`, one bit per vocabulary column; decode_rules_plan_kernel rebuilds them from the generated history before every pick and
+// the three wide head kernels read them in their epilogues.  A head kernel is rule-aware when it is instantiated with a trailing
+// RulesDev argument (the pack R): the instantiations without one have the argument list, and the code, they had before the rules
+// existed (two main-loop copies are scheduled differently as soon as anything around them moves: profiles/skinny_split_isa.md,
+// profiles/decode_rules.md holds the register table of both forms).
+struct RulesDev { const uint32_t* seen; const uint32_t* banned; long ld_words; float penalty; };
+MVLT_DEV const RulesDev& rules_arg(const RulesDev& r) { return r; }
+// A lane's four columns n0 + 4 g + r are 4-aligned and n0 is a multiple of 16, so they sit in ONE 32-bit word of a row's map, the
+// word of n0 (n0 < N: inside the row): bits (seen | banned << 4) of the four columns of row m, bit r = column n0 + 4 g + r.
+// Rows past M read row M - 1 (their result is dropped).
+MVLT_DEV uint32_t rules_bits(const RulesDev& rd, const int m, const int M, const int n) {
+    const long w = (long)min(m, M - 1) * rd.ld_words + (n >> 5);
+    const int sh = n & 31;
+    return ((rd.seen[w] >> sh) & 15u) | (((rd.banned[w] >> sh) & 15u) << 4);
+}
+// HF's repetition penalty on a seen column, two rounded operations
+MVLT_DEV float rules_penalise(const float x, const float penalty) { return x < 0.f ? __fmul_rn(x, penalty) : __fdiv_rn(x, penalty); }
+
+// The plan: one workgroup per row m rebuilds seen[m] and banned[m] from h = ids[m, 0 .. c-1], c = *col read on the device like
+// the pick kernels read it.  Stateless: both maps are cleared and set again every call (global atomicOr; a workgroup touches only
+// its own row), so a replayed graph carries nothing from token to token.  The n-gram rule is a scan over the start i of every
+// earlier g-gram, one thread per i: h[i .. i+g-2] == the last g-1 tokens bans h[i+g-1].  ids outside [0, V) set no bit.
+struct RulesPlan {
+    uint32_t* seen; uint32_t* banned; long ld_words; const int64_t* ids; long ld_ids; const int64_t* col;
+    int ngram, min_length; int64_t eos; int has_eos, V;
+};
+__global__ __launch_bounds__(256) void decode_rules_plan_kernel(const RulesPlan f) {
+    const int m = blockIdx.x, tid = threadIdx.x, nw = (f.V + 31) >> 5;
+    uint32_t* seen = f.seen + (long)m * f.ld_words;
+    uint32_t* banned = f.banned + (long)m * f.ld_words;
+    const int64_t* h = f.ids + (long)m * f.ld_ids;
+    const long c64 = f.col[0];
+    const int c = (int)(c64 < 0 ? 0 : (c64 > f.ld_ids ? f.ld_ids : c64));          // never past the row of ids
+    for (int w = tid; w < nw; w += 256) { seen[w] = 0u; banned[w] = 0u; }
+    __syncthreads();
+    const int g = f.ngram;
+    for (int i = tid; i < c; i += 256) {
+        const int64_t t = h[i];
+        if (t >= 0 && t < f.V) atomicOr(seen + (t >> 5), 1u << (t & 31));
+        if (g >= 1 && i + g <= c) {          // the g-gram starting at i ends before column c
+            bool same = true;
+            for (int j = 0; j < g - 1; ++j) same = same && h[i + j] == h[c - g + 1 + j];
+            const int64_t b = h[i + g - 1];
+            if (same && b >= 0 && b < f.V) atomicOr(banned + (b >> 5), 1u << (b & 31));
+        }
+    }
+    if (tid == 0 && f.has_eos && c64 < f.min_length && f.eos >= 0 && f.eos < f.V) atomicOr(banned + (f.eos >> 5), 1u << (f.eos & 31));
+}
+
 // Decoder GEMM of the last-row MLM head fused with the greedy pick, wide form (round 5): a workgroup = 128 vocabulary columns,
 // wave w = columns 16 w .. +16 over the WHOLE reduction -- no k-split across waves, so no LDS reduction and no barrier; the
 // 47 MB weight matrix is streamed once by 239 workgroups (one per CU) with UNR k-blocks in flight per wave, the 32-64
 // activation rows come from L1 / L2.  The 16-column form above launches 1,908 workgroups that each re-read the whole
 // activation matrix and meet in LDS: 29 us for a product whose bytes take 9 us.  Same partial layout (one (max, index) per row
 // and 16 columns), so the finishing kernel is shared.
-template <typename T, int NRT>
-__global__ __launch_bounds__(64 * SKINNY_WAVES) void gemm_argmax128_kernel(const GemmDev p, const ArgmaxOut am, int nparts) {
+template <typename T, int NRT, typename... R>
+__global__ __launch_bounds__(64 * SKINNY_WAVES) void gemm_argmax128_kernel(const GemmDev p, const ArgmaxOut am, int nparts, const R... rules) {
+    constexpr bool RULES = sizeof...(R) > 0;
     using M_ = Mma<T>;
     using Frag = typename M_::Frag;
     constexpr int KB = M_::KB, E = TypeInfo<T>::E, UNR = NRT <= 2 ? 12 : 8;          // k-blocks in flight per wave (12 KB of weights; K = 768 in two rounds)
@@ -259,10 +311,16 @@ __global__ __launch_bounds__(64 * SKINNY_WAVES) void gemm_argmax128_kernel(const
 #pragma unroll
     for (int i = 0; i < NRT; ++i) {
         float best = -3.0e38f; int bi = 0x7fffffff;
+        uint32_t bits = 0u;          // RULES: seen (bits 0-3) and banned (bits 4-7) of this lane's four columns
+        if constexpr (RULES) bits = rules_bits(rules_arg(rules...), 16 * i + r15, p.M, n0 + 4 * g);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int n = n0 + 4 * g + r;
-            const float x = acc[i][r] + bias4[r];
+            float x = acc[i][r] + bias4[r];
+            if constexpr (RULES) {
+                if ((bits >> r) & 1u) x = rules_penalise(x, rules_arg(rules...).penalty);
+                if ((bits >> (4 + r)) & 1u) continue;          // a banned column is skipped like a column n >= N
+            }
             if (n < p.N && x > best) { best = x; bi = n; }          // ascending n: ties keep the first index
         }
 #pragma unroll
@@ -349,8 +407,10 @@ __global__ __launch_bounds__(256) void greedy_pick_kernel(const float* part_val,
 // Per row and 16-column part it writes five values, part_val[j][m][part]: j = 0 max y, 1 x at that index, 2 max x,
 // 3 sum exp(x - max x); part_idx[m][part] = first index of max y.  Columns n >= N take part in neither.
 struct SampleIn { const uint64_t* seed_dev; uint64_t seed; const int64_t* col; uint32_t tag0; float inv_t; };
-template <typename T, int NRT>
-__global__ __launch_bounds__(64 * SKINNY_WAVES) void gemm_sample128_kernel(const GemmDev p, float* part_val, int* part_idx, int nparts, const SampleIn si) {
+template <typename T, int NRT, typename... R>
+__global__ __launch_bounds__(64 * SKINNY_WAVES) void gemm_sample128_kernel(const GemmDev p, float* part_val, int* part_idx, int nparts, const SampleIn si,
+                                                                           const R... rules) {
+    constexpr bool RULES = sizeof...(R) > 0;
     using M_ = Mma<T>;
     using Frag = typename M_::Frag;
     constexpr int KB = M_::KB, E = TypeInfo<T>::E, UNR = NRT <= 2 ? 12 : 8;
@@ -398,12 +458,20 @@ __global__ __launch_bounds__(64 * SKINNY_WAVES) void gemm_sample128_kernel(const
         const int m = 16 * i + r15;
         float x[4];
         float best = -3.0e38f, bx = 0.f, xm = -3.0e38f; int bi = 0x7fffffff;
+        uint32_t bits = 0u;          // RULES: seen (bits 0-3) and banned (bits 4-7) of this lane's four columns
+        if constexpr (RULES) bits = rules_bits(rules_arg(rules...), m, p.M, n0 + 4 * g);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int n = n0 + 4 * g + r;
-            x[r] = __fmul_rn(__fadd_rn(acc[i][r], bias4[r]), si.inv_t);
+            if constexpr (RULES) {          // the rules act on the raw logit, ahead of the temperature
+                float raw = __fadd_rn(acc[i][r], bias4[r]);
+                if ((bits >> r) & 1u) raw = rules_penalise(raw, rules_arg(rules...).penalty);
+                x[r] = __fmul_rn(raw, si.inv_t);
+            } else {
+                x[r] = __fmul_rn(__fadd_rn(acc[i][r], bias4[r]), si.inv_t);
+            }
             const float y = __fadd_rn(x[r], gumbel_noise(seed, tag, (uint32_t)m * (uint32_t)p.N + (uint32_t)n));
-            if (n < p.N) {
+            if (n < p.N && !(RULES && ((bits >> (4 + r)) & 1u))) {
                 if (y > best) { best = y; bi = n; bx = x[r]; }          // ascending n: ties keep the first index
                 xm = fmaxf(xm, x[r]);
             }
@@ -415,9 +483,10 @@ __global__ __launch_bounds__(64 * SKINNY_WAVES) void gemm_sample128_kernel(const
             xm = fmaxf(xm, __shfl_xor(xm, o, 64));
         }
         // (n0 < N: every part has a valid column, so xm is a logit; __expf of a non-positive argument: v_exp_f32 of x log2 e)
+        // RULES: a part whose 16 columns are all banned keeps xm = -3e38 and a zero sum, and the finish weighs it with exp(-3e38 - max) = 0
         float se = 0.f;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) se += (n0 + 4 * g + r < p.N) ? __expf(x[r] - xm) : 0.f;
+        for (int r = 0; r < 4; ++r) se += (n0 + 4 * g + r < p.N && !(RULES && ((bits >> (4 + r)) & 1u))) ? __expf(x[r] - xm) : 0.f;
         se += __shfl_xor(se, 16, 64);
         se += __shfl_xor(se, 32, 64);
         if (g == 0 && m < p.M) {
@@ -478,8 +547,12 @@ __global__ __launch_bounds__(256) void sample_pick_kernel(const float* part_val,
 // there; gemm_sample128_kernel itself is untouched): the same loads and MFMAs in the same order and the same two rounded
 // epilogue operations, so x is bit for bit the value that kernel forms.  It computes no noise.
 // vec: ldx % 4 == 0 and a 16-byte aligned workspace (whole 4-column groups go out as one 16-byte store).
-template <typename T, int NRT>
-__global__ __launch_bounds__(64 * SKINNY_WAVES) void gemm_logits128_kernel(const GemmDev p, float* xout, long ldx, int vec, float inv_t) {
+// RULES: x is the processed logit (penalty ahead of the temperature) and -inf in a banned column; sample_filter_pick_kernel needs
+// no change for that: -inf is below every finite key, weighs exp(-inf) = 0 in the masses and the sums, and y = -inf + G never beats
+// the initial best of the draw -- also when top_k exceeds the number of unbanned columns and the threshold falls to -inf.
+template <typename T, int NRT, typename... R>
+__global__ __launch_bounds__(64 * SKINNY_WAVES) void gemm_logits128_kernel(const GemmDev p, float* xout, long ldx, int vec, float inv_t, const R... rules) {
+    constexpr bool RULES = sizeof...(R) > 0;
     using M_ = Mma<T>;
     using Frag = typename M_::Frag;
     constexpr int KB = M_::KB, E = TypeInfo<T>::E, UNR = NRT <= 2 ? 12 : 8;
@@ -523,8 +596,18 @@ __global__ __launch_bounds__(64 * SKINNY_WAVES) void gemm_logits128_kernel(const
         const int m = 16 * i + r15, n = n0 + 4 * g;
         if (m >= p.M) continue;
         f32x4 x;
+        if constexpr (RULES) {
+            const uint32_t bits = rules_bits(rules_arg(rules...), m, p.M, n);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) x[r] = __fmul_rn(__fadd_rn(acc[i][r], bias4[r]), inv_t);
+            for (int r = 0; r < 4; ++r) {
+                float raw = __fadd_rn(acc[i][r], bias4[r]);
+                if ((bits >> r) & 1u) raw = rules_penalise(raw, rules_arg(rules...).penalty);
+                x[r] = ((bits >> (4 + r)) & 1u) ? -__builtin_inff() : __fmul_rn(raw, inv_t);
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) x[r] = __fmul_rn(__fadd_rn(acc[i][r], bias4[r]), inv_t);
+        }
         float* o = xout + (long)m * ldx + n;
         if (vec && n + 4 <= p.N) store4f(o, x);
         else
@@ -882,7 +965,8 @@ GemmDev skinny_dev(const MvltGemm* p) {
 int parts_of(const MvltGemm* p) { return ceil_div(p->N, 16); }          // one part per row and 16 columns
 
 // the (max, index) partials per row and 16 columns: wide streaming form for big vocabularies, else the 16-column skinny kernel
-int argmax_products(const MvltGemm* p, float* part_val, int32_t* part_idx, hipStream_t s) {
+// (`r`: the logit rules or nullptr; with rules always the wide form, which takes any N -- the 16-column kernel has no rule-aware sibling)
+int argmax_products(const MvltGemm* p, float* part_val, int32_t* part_idx, hipStream_t s, const RulesDev* r = nullptr) {
     MVLT_CHECK((p->epilogue & ~(MVLT_EPI_BIAS)) == 0, MVLT_ERR_UNSUPPORTED);
     return by_dtype(p->dtype, [&](auto t) -> int {
         using T = decltype(t);
@@ -891,20 +975,23 @@ int argmax_products(const MvltGemm* p, float* part_val, int32_t* part_idx, hipSt
         const int nblk = parts_of(p);
         const ArgmaxOut am{part_val, part_idx};
         const dim3 block(64 * SKINNY_WAVES);
-        if (p->N >= 4096) LAUNCH_NRT(gemm_argmax128_kernel, T, p->M, dim3(ceil_div(nblk, SKINNY_WAVES)), block, s, d, am, nblk);
+        if (r) LAUNCH_NRT(gemm_argmax128_kernel, T, p->M, dim3(ceil_div(nblk, SKINNY_WAVES)), block, s, d, am, nblk, *r);
+        else if (p->N >= 4096) LAUNCH_NRT(gemm_argmax128_kernel, T, p->M, dim3(ceil_div(nblk, SKINNY_WAVES)), block, s, d, am, nblk);
         else hipLaunchKernelGGL((gemm_skinny_kernel<T, true>), dim3(nblk), block, 0, s, d, am);
         return (int)MVLT_OK;
     });
 }
 
 // the sampled partials: always the wide streaming form (it handles any N; the 16-column skinny kernel has no sampled sibling)
-int sample_products(const MvltGemm* p, float* part_val, int32_t* part_idx, const SampleIn& si, hipStream_t s) {
+int sample_products(const MvltGemm* p, float* part_val, int32_t* part_idx, const SampleIn& si, hipStream_t s, const RulesDev* r = nullptr) {
     return by_dtype(p->dtype, [&](auto t) -> int {
         using T = decltype(t);
         MVLT_CHECK(skinny_ok<T>(p), MVLT_ERR_UNSUPPORTED);
         const GemmDev d = skinny_dev(p);
         const int nblk = parts_of(p);
-        LAUNCH_NRT(gemm_sample128_kernel, T, p->M, dim3(ceil_div(nblk, SKINNY_WAVES)), dim3(64 * SKINNY_WAVES), s, d, part_val, part_idx, nblk, si);
+        const dim3 grid(ceil_div(nblk, SKINNY_WAVES)), block(64 * SKINNY_WAVES);
+        if (r) LAUNCH_NRT(gemm_sample128_kernel, T, p->M, grid, block, s, d, part_val, part_idx, nblk, si, *r);
+        else LAUNCH_NRT(gemm_sample128_kernel, T, p->M, grid, block, s, d, part_val, part_idx, nblk, si);
         return (int)MVLT_OK;
     });
 }
@@ -932,6 +1019,14 @@ template <typename S> int greedy_state(const S* g, GreedyState& st) {
     return MVLT_OK;
 }
 
+// MvltLogitRules -> what the rule-aware heads read, for a product of M rows and N columns (the refusals of mvlt_hip.h)
+int rules_dev(const MvltLogitRules* r, const int M, const int N, RulesDev& rd) {
+    MVLT_CHECK(r && r->seen && r->banned && M >= 1 && M <= 64 && N >= 1, MVLT_ERR_ARG);
+    MVLT_CHECK(r->ld_words >= (long)ceil_div(N, 32) && r->penalty > 0.f && r->ngram >= 0, MVLT_ERR_ARG);          // (a NaN penalty fails > 0)
+    rd = RulesDev{r->seen, r->banned, (long)r->ld_words, r->penalty};
+    return MVLT_OK;
+}
+
 }  // namespace
 
 extern "C" __attribute__((visibility("hidden"))) int mvlt_skinny_try(const MvltGemm* p, const void* dev_block, void* stream, int* route) {
@@ -947,43 +1042,42 @@ extern "C" __attribute__((visibility("hidden"))) int mvlt_skinny_try(const MvltG
     return rc == MVLT_ERR_UNSUPPORTED ? 0 : rc;
 }
 
-extern "C" int mvlt_gemm_argmax(const MvltGemm* p, float* part_val, int32_t* part_idx, int64_t* out_idx, float* out_val,
-                                void* stream) {
+// The head entry points come in pairs: the plain form and its _rules form (the same checks and launches with the rule-aware
+// product, `r` = the checked rules; nullptr: none).
+namespace {
+int argmax_entry(const MvltGemm* p, float* part_val, int32_t* part_idx, int64_t* out_idx, float* out_val, const RulesDev* r, void* stream) {
     MVLT_CHECK(p && p->A && p->B && part_val && part_idx && out_idx, MVLT_ERR_ARG);
     MVLT_CHECK(p->M > 0 && p->N > 0 && p->K > 0 && p->lda > 0 && p->ldb > 0, MVLT_ERR_ARG);
     if (p->epilogue & MVLT_EPI_BIAS) MVLT_CHECK(p->bias, MVLT_ERR_ARG);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    { const int rc = argmax_products(p, part_val, part_idx, s); if (rc != MVLT_OK) return rc; }
+    { const int rc = argmax_products(p, part_val, part_idx, s, r); if (rc != MVLT_OK) return rc; }
     hipLaunchKernelGGL(argmax_parts_kernel, dim3(p->M), dim3(64), 0, s, part_val, part_idx, parts_of(p), out_idx, out_val);
     MVLT_LAUNCH_CHECK();
     return MVLT_OK;
 }
-
-extern "C" int mvlt_gemm_argmax_greedy(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltGreedyState* g, void* stream) {
+int argmax_greedy_entry(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltGreedyState* g, const RulesDev* r, void* stream) {
     MVLT_CHECK(g, MVLT_ERR_ARG);
     { const int rc = head_check(p, part_val, part_idx); if (rc != MVLT_OK) return rc; }
     GreedyState st;
     { const int rc = greedy_state(g, st); if (rc != MVLT_OK) return rc; }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    { const int rc = argmax_products(p, part_val, part_idx, s); if (rc != MVLT_OK) return rc; }
+    { const int rc = argmax_products(p, part_val, part_idx, s, r); if (rc != MVLT_OK) return rc; }
     hipLaunchKernelGGL(greedy_pick_kernel, dim3(p->M), dim3(256), 0, s, part_val, part_idx, parts_of(p), p->M, st);
     MVLT_LAUNCH_CHECK();
     return MVLT_OK;
 }
-
-extern "C" int mvlt_gemm_sample(const MvltGemm* p, float* part_val, int32_t* part_idx, int64_t* out_idx, float* out_logprob,
-                                uint64_t seed, uint32_t tag, float inv_temperature, void* stream) {
+int sample_entry(const MvltGemm* p, float* part_val, int32_t* part_idx, int64_t* out_idx, float* out_logprob, uint64_t seed, uint32_t tag,
+                 float inv_temperature, const RulesDev* r, void* stream) {
     { const int rc = sample_check(p, part_val, part_idx, inv_temperature); if (rc != MVLT_OK) return rc; }
     MVLT_CHECK(out_idx && out_logprob, MVLT_ERR_ARG);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const SampleIn si{nullptr, seed, nullptr, tag, inv_temperature};
-    { const int rc = sample_products(p, part_val, part_idx, si, s); if (rc != MVLT_OK) return rc; }
+    { const int rc = sample_products(p, part_val, part_idx, si, s, r); if (rc != MVLT_OK) return rc; }
     hipLaunchKernelGGL(sample_pick_kernel<false>, dim3(p->M), dim3(256), 0, s, part_val, part_idx, parts_of(p), p->M, GreedyState{}, out_idx, out_logprob);
     MVLT_LAUNCH_CHECK();
     return MVLT_OK;
 }
-
-extern "C" int mvlt_gemm_sample_step(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltSampleState* g, void* stream) {
+int sample_step_entry(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltSampleState* g, const RulesDev* r, void* stream) {
     MVLT_CHECK(g, MVLT_ERR_ARG);
     { const int rc = sample_check(p, part_val, part_idx, g->inv_temperature); if (rc != MVLT_OK) return rc; }
     MVLT_CHECK(g->seed, MVLT_ERR_ARG);
@@ -991,10 +1085,63 @@ extern "C" int mvlt_gemm_sample_step(const MvltGemm* p, float* part_val, int32_t
     { const int rc = greedy_state(g, st); if (rc != MVLT_OK) return rc; }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const SampleIn si{g->seed, 0, g->col, g->tag0, g->inv_temperature};
-    { const int rc = sample_products(p, part_val, part_idx, si, s); if (rc != MVLT_OK) return rc; }
+    { const int rc = sample_products(p, part_val, part_idx, si, s, r); if (rc != MVLT_OK) return rc; }
     hipLaunchKernelGGL(sample_pick_kernel<true>, dim3(p->M), dim3(256), 0, s, part_val, part_idx, parts_of(p), p->M, st, (int64_t*)nullptr, (float*)nullptr);
     MVLT_LAUNCH_CHECK();
     return MVLT_OK;
+}
+// the rules of a _rules call, checked ahead of everything else: rc != MVLT_OK refuses the call
+#define RULES_OF(rd, rules, p)                                                                  \
+    RulesDev rd;                                                                                \
+    { MVLT_CHECK(p, MVLT_ERR_ARG); const int rc_ = rules_dev(rules, (p)->M, (p)->N, rd); if (rc_ != MVLT_OK) return rc_; }
+}  // namespace
+
+extern "C" int mvlt_decode_rules_plan(const MvltLogitRules* r, int M, int V, void* stream) {
+    MVLT_CHECK(r && r->seen && r->banned && r->ids && r->col, MVLT_ERR_ARG);
+    MVLT_CHECK(M >= 1 && M <= 64 && V >= 1 && r->ld_ids >= 1 && r->ld_words >= (long)ceil_div(V, 32), MVLT_ERR_ARG);
+    MVLT_CHECK(r->penalty > 0.f && r->ngram >= 0 && r->min_length >= 0, MVLT_ERR_ARG);
+    const RulesPlan f{r->seen, r->banned, (long)r->ld_words, r->ids, (long)r->ld_ids, r->col, r->ngram, r->min_length, r->eos_id, r->has_eos, V};
+    hipLaunchKernelGGL(decode_rules_plan_kernel, dim3(M), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), f);
+    MVLT_LAUNCH_CHECK();
+    return MVLT_OK;
+}
+
+extern "C" int mvlt_gemm_argmax(const MvltGemm* p, float* part_val, int32_t* part_idx, int64_t* out_idx, float* out_val,
+                                void* stream) {
+    return argmax_entry(p, part_val, part_idx, out_idx, out_val, nullptr, stream);
+}
+extern "C" int mvlt_gemm_argmax_rules(const MvltGemm* p, float* part_val, int32_t* part_idx, int64_t* out_idx, float* out_val,
+                                      const MvltLogitRules* rules, void* stream) {
+    RULES_OF(rd, rules, p);
+    return argmax_entry(p, part_val, part_idx, out_idx, out_val, &rd, stream);
+}
+
+extern "C" int mvlt_gemm_argmax_greedy(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltGreedyState* g, void* stream) {
+    return argmax_greedy_entry(p, part_val, part_idx, g, nullptr, stream);
+}
+extern "C" int mvlt_gemm_argmax_greedy_rules(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltGreedyState* g,
+                                             const MvltLogitRules* rules, void* stream) {
+    RULES_OF(rd, rules, p);
+    return argmax_greedy_entry(p, part_val, part_idx, g, &rd, stream);
+}
+
+extern "C" int mvlt_gemm_sample(const MvltGemm* p, float* part_val, int32_t* part_idx, int64_t* out_idx, float* out_logprob,
+                                uint64_t seed, uint32_t tag, float inv_temperature, void* stream) {
+    return sample_entry(p, part_val, part_idx, out_idx, out_logprob, seed, tag, inv_temperature, nullptr, stream);
+}
+extern "C" int mvlt_gemm_sample_rules(const MvltGemm* p, float* part_val, int32_t* part_idx, int64_t* out_idx, float* out_logprob,
+                                      uint64_t seed, uint32_t tag, float inv_temperature, const MvltLogitRules* rules, void* stream) {
+    RULES_OF(rd, rules, p);
+    return sample_entry(p, part_val, part_idx, out_idx, out_logprob, seed, tag, inv_temperature, &rd, stream);
+}
+
+extern "C" int mvlt_gemm_sample_step(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltSampleState* g, void* stream) {
+    return sample_step_entry(p, part_val, part_idx, g, nullptr, stream);
+}
+extern "C" int mvlt_gemm_sample_step_rules(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltSampleState* g,
+                                           const MvltLogitRules* rules, void* stream) {
+    RULES_OF(rd, rules, p);
+    return sample_step_entry(p, part_val, part_idx, g, &rd, stream);
 }
 
 // the two launches of the filtered pick: x = the product (bit for bit gemm_sample128_kernel's), then a workgroup per row
@@ -1006,14 +1153,15 @@ int filter_check(const MvltGemm* p, const MvltSampleFilter* f) {
 }
 template <bool STEP>
 int filtered_launch(const MvltGemm* p, const MvltSampleFilter* f, const SampleIn& si, const GreedyState& st, int64_t* out_idx, float* out_logprob,
-                    hipStream_t s) {
+                    const RulesDev* r, hipStream_t s) {
     const int rc = by_dtype(p->dtype, [&](auto t) -> int {
         using T = decltype(t);
         MVLT_CHECK(skinny_ok<T>(p), MVLT_ERR_UNSUPPORTED);
         const GemmDev d = skinny_dev(p);
         const int vec = (f->ldx % 4 == 0 && aligned16(f->x)) ? 1 : 0;
-        LAUNCH_NRT(gemm_logits128_kernel, T, p->M, dim3(ceil_div(parts_of(p), SKINNY_WAVES)), dim3(64 * SKINNY_WAVES), s, d, f->x, (long)f->ldx, vec,
-                   si.inv_t);
+        const dim3 grid(ceil_div(parts_of(p), SKINNY_WAVES)), block(64 * SKINNY_WAVES);
+        if (r) LAUNCH_NRT(gemm_logits128_kernel, T, p->M, grid, block, s, d, f->x, (long)f->ldx, vec, si.inv_t, *r);
+        else LAUNCH_NRT(gemm_logits128_kernel, T, p->M, grid, block, s, d, f->x, (long)f->ldx, vec, si.inv_t);
         return (int)MVLT_OK;
     });
     if (rc != MVLT_OK) return rc;
@@ -1022,19 +1170,16 @@ int filtered_launch(const MvltGemm* p, const MvltSampleFilter* f, const SampleIn
     MVLT_LAUNCH_CHECK();
     return MVLT_OK;
 }
-}  // namespace
-
-extern "C" int mvlt_gemm_sample_filtered(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltSampleFilter* filter, int64_t* out_idx,
-                                         float* out_logprob, uint64_t seed, uint32_t tag, float inv_temperature, void* stream) {
+int filtered_entry(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltSampleFilter* filter, int64_t* out_idx, float* out_logprob,
+                   uint64_t seed, uint32_t tag, float inv_temperature, const RulesDev* r, void* stream) {
     { const int rc = sample_check(p, part_val, part_idx, inv_temperature); if (rc != MVLT_OK) return rc; }
     { const int rc = filter_check(p, filter); if (rc != MVLT_OK) return rc; }
     MVLT_CHECK(out_idx && out_logprob, MVLT_ERR_ARG);
     const SampleIn si{nullptr, seed, nullptr, tag, inv_temperature};
-    return filtered_launch<false>(p, filter, si, GreedyState{}, out_idx, out_logprob, reinterpret_cast<hipStream_t>(stream));
+    return filtered_launch<false>(p, filter, si, GreedyState{}, out_idx, out_logprob, r, reinterpret_cast<hipStream_t>(stream));
 }
-
-extern "C" int mvlt_gemm_sample_filtered_step(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltSampleFilter* filter,
-                                              const MvltSampleState* g, void* stream) {
+int filtered_step_entry(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltSampleFilter* filter, const MvltSampleState* g,
+                        const RulesDev* r, void* stream) {
     MVLT_CHECK(g, MVLT_ERR_ARG);
     { const int rc = sample_check(p, part_val, part_idx, g->inv_temperature); if (rc != MVLT_OK) return rc; }
     { const int rc = filter_check(p, filter); if (rc != MVLT_OK) return rc; }
@@ -1042,7 +1187,29 @@ extern "C" int mvlt_gemm_sample_filtered_step(const MvltGemm* p, float* part_val
     GreedyState st;
     { const int rc = greedy_state(g, st); if (rc != MVLT_OK) return rc; }
     const SampleIn si{g->seed, 0, g->col, g->tag0, g->inv_temperature};
-    return filtered_launch<true>(p, filter, si, st, nullptr, nullptr, reinterpret_cast<hipStream_t>(stream));
+    return filtered_launch<true>(p, filter, si, st, nullptr, nullptr, r, reinterpret_cast<hipStream_t>(stream));
+}
+}  // namespace
+
+extern "C" int mvlt_gemm_sample_filtered(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltSampleFilter* filter, int64_t* out_idx,
+                                         float* out_logprob, uint64_t seed, uint32_t tag, float inv_temperature, void* stream) {
+    return filtered_entry(p, part_val, part_idx, filter, out_idx, out_logprob, seed, tag, inv_temperature, nullptr, stream);
+}
+extern "C" int mvlt_gemm_sample_filtered_rules(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltSampleFilter* filter,
+                                               int64_t* out_idx, float* out_logprob, uint64_t seed, uint32_t tag, float inv_temperature,
+                                               const MvltLogitRules* rules, void* stream) {
+    RULES_OF(rd, rules, p);
+    return filtered_entry(p, part_val, part_idx, filter, out_idx, out_logprob, seed, tag, inv_temperature, &rd, stream);
+}
+
+extern "C" int mvlt_gemm_sample_filtered_step(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltSampleFilter* filter,
+                                              const MvltSampleState* g, void* stream) {
+    return filtered_step_entry(p, part_val, part_idx, filter, g, nullptr, stream);
+}
+extern "C" int mvlt_gemm_sample_filtered_step_rules(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltSampleFilter* filter,
+                                                    const MvltSampleState* g, const MvltLogitRules* rules, void* stream) {
+    RULES_OF(rd, rules, p);
+    return filtered_step_entry(p, part_val, part_idx, filter, g, &rd, stream);
 }
 
 // The beam candidates: the product in row chunks of <= 64 into the one workspace, then the selection.  Every chunk is checked

@@ -19,6 +19,10 @@ its head: the token of output column c is ``argmax_n (logit_n / T + G_n)`` with 
 through a workspace, a workgroup per row selects the threshold (top-k with ties kept, then the nucleus over what is left) and
 draws among the kept tokens with the same noise; the score is the log-probability under the renormalised distribution.  The
 eager loop calls the stand-alone entry point, for B > 64 in row chunks of 64 whose noise is indexed by the row of the batch.
+Logit rules (``repetition_penalty`` / ``no_repeat_ngram_size`` / ``min_length``, HF's three processors on the raw logits): a plan
+kernel rebuilds two bitmaps per row (tokens seen, tokens banned) from the device-side history before every pick and the ``_rules``
+forms of the head entry points apply them in their epilogues (``ops.LogitRules``) -- in the graph and in the eager loop alike, any B
+(rows in chunks of 64; rules never fall back to torch picks).  All rules off is the code path without them.
 Beam search (``beam_search``): same cached steps over B*beams rows, scorer bookkeeping on the host restated from HF
 transformers 4.16 (parity with the reference unpinned).  Default route (beams <= 8, head_dim 64): the candidates of a token come
 from ``mvlt_gemm_beam_candidates`` (head + log-softmax + beam score + top 2*beams per sample, f32 logits through a workspace) and
@@ -80,6 +84,26 @@ def _greedy_route(sample_mode, B, filtered, graph_on):
     if sample_mode == 'greedy':
         return 'eager', 'gemm_argmax' if B <= 64 else 'argmax'
     return 'eager', 'gemm_sample' if B <= 64 else 'multinomial'
+
+
+def check_logit_rules(repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, num_beams=1, V=None, max_length=None):
+    """(float penalty, int ngram, int min_length) of a constrained decode, or ValueError: penalty > 0 (1.0 = off, no NaN),
+    ngram >= 0 (0 = off), min_length >= 0 (0 = off); any rule switched on needs num_beams <= 1 (beam search has no rule-aware
+    candidate head) and, when ``V`` / ``max_length`` are given, V > max_length: a history of max_length - 1 tokens plus eos can ban
+    max_length columns, and a row must keep one."""
+    pen = float(repetition_penalty)
+    if not pen > 0.0 or pen == float("inf"):
+        raise ValueError("repetition_penalty must be a positive number (1.0 switches it off)")
+    for name, v in (("no_repeat_ngram_size", no_repeat_ngram_size), ("min_length", min_length)):
+        if (isinstance(v, float) and v != v) or int(v) != v or int(v) < 0:
+            raise ValueError(f"{name} must be a non-negative integer (0 switches it off)")
+    rules = pen, int(no_repeat_ngram_size), int(min_length)
+    if rules != (1.0, 0, 0):
+        if num_beams > 1:
+            raise ValueError("repetition_penalty / no_repeat_ngram_size / min_length are not implemented for beam search (num_beams > 1)")
+        if V is not None and max_length is not None and V <= max_length:
+            raise ValueError(f"logit rules can ban up to max_length = {max_length} columns: the vocabulary ({V}) must be larger")
+    return rules
 
 
 def _beam_route(num_beams, head_dim, max_length, fused_on, device_scorer, device_on=False):
@@ -303,7 +327,8 @@ class _GreedyGraph(_DecodeGraph):
     unfinished flags, and the [B, max_length] output matrices.  The host only replays and, every 8 tokens, reads
     the all-finished flags back."""
 
-    def __init__(self, model, key, B, n_img, max_length, cd, pad, eos, mask_id, mode='greedy', temperature=1.0, top_k=0, top_p=1.0):
+    def __init__(self, model, key, B, n_img, max_length, cd, pad, eos, mask_id, mode='greedy', temperature=1.0, top_k=0, top_p=1.0,
+                 rules=(1.0, 0, 0)):
         dev = next(model.parameters()).device
         H = model.config.hidden_size
         self.key, self.model, self.cd, self.graph = key, model, cd, None
@@ -332,17 +357,26 @@ class _GreedyGraph(_DecodeGraph):
         st.alive, st.new_ids, st.ld_new = self.alive.data_ptr(), self.new_ids.data_ptr(), 2
         self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
         st.ticket = self.ticket.data_ptr()
+        # logit rules: the graph owns the bitmaps; the plan reads the history where the picks write it (ids, col)
+        self.rules = None
+        if rules != (1.0, 0, 0):
+            V = model.MLM_head_seq2seq.predictions.decoder.out_features
+            self.rules = ops.LogitRules(V, *rules, eos, self.ids, self.col)
 
     def head(self):
         """token <- argmax(MLM head(hlast)); record it in column `col`; past += 1; col += 1 (all on the device)."""
         # decoder GEMM fused with the greedy pick and its bookkeeping: the [B, 30522] logits are never written
         t2, W, bias = _head(self.model, Arena.of(self.model, self.cd), self.hlast)
+        rules = None
+        if self.rules is not None:          # the bitmaps of this token, then the rule-aware form of the same head
+            self.rules.plan()
+            rules = self.rules.struct()
         if self.mode != 'greedy' and (self.top_k, self.top_p) != (0, 1.0):
-            ops.gemm_sample_filtered_step(t2, W, bias, self.state, self.top_k, self.top_p)
+            ops.gemm_sample_filtered_step(t2, W, bias, self.state, self.top_k, self.top_p, rules=rules)
         elif self.mode != 'greedy':
-            ops.gemm_sample_step(t2, W, bias, self.state)
+            ops.gemm_sample_step(t2, W, bias, self.state, rules=rules)
         else:
-            ops.gemm_argmax_greedy(t2, W, bias, self.state)
+            ops.gemm_argmax_greedy(t2, W, bias, self.state, rules=rules)
 
     def body(self):
         """The pick, then the 2-token cached forward of [last token, MASK] at positions past, past+1.  `past` was advanced by the
@@ -351,7 +385,7 @@ class _GreedyGraph(_DecodeGraph):
         _step2(self.model.MVLBert, Arena.of(self.model, self.cd), self.new_ids, self.past, self.kc, self.vc, self.cd, out_last=self.hfull)
 
 
-def _greedy_graph_loop(model, ar, feat, max_length, pad, eos, mask_id, cd, mode, seed, temperature, top_k, top_p):
+def _greedy_graph_loop(model, ar, feat, max_length, pad, eos, mask_id, cd, mode, seed, temperature, top_k, top_p, rules=(1.0, 0, 0)):
     B, n_img, _ = feat.shape
     key = (B, n_img, max_length, cd, pad, eos, mask_id, ar.flat.data_ptr(), feat.device.index)
     slot = "_mvlt_greedy_graph"
@@ -359,7 +393,9 @@ def _greedy_graph_loop(model, ar, feat, max_length, pad, eos, mask_id, cd, mode,
         key, slot = key + (mode, float(temperature)), "_mvlt_sample_graph"
         if (top_k, top_p) != (0, 1.0):          # a filtered graph takes the sampled graph's slot, like a new temperature
             key = key + (top_k, top_p)
-    gg = _GreedyGraph.of(model, slot, key, B, n_img, max_length, cd, pad, eos, mask_id, mode, temperature, top_k, top_p)
+    if rules != (1.0, 0, 0):          # a graph with rules takes the slot of its mode, like a new temperature
+        key = key + ("rules",) + tuple(rules)
+    gg = _GreedyGraph.of(model, slot, key, B, n_img, max_length, cd, pad, eos, mask_id, mode, temperature, top_k, top_p, rules)
     gg.seed.fill_(ops.s64(int(seed) & ((1 << 64) - 1)))
     hlast, past = _step0(model.MVLBert, feat, gg.new_ids[:, 1:2].contiguous(), gg.kc, gg.vc)
     gg.past.fill_(past - 1); gg.col.zero_(); gg.unfinished.fill_(1); gg.alive.zero_(); gg.ticket.zero_()      # (the first pick advances `past`; the picks raise `alive`)
@@ -379,7 +415,7 @@ def _greedy_graph_loop(model, ar, feat, max_length, pad, eos, mask_id, cd, mode,
     return ids, scores
 
 
-def _greedy_eager_loop(model, ar, feat, max_length, pad, eos, mask_id, cd, pick, seed, temperature, top_k, top_p):
+def _greedy_eager_loop(model, ar, feat, max_length, pad, eos, mask_id, cd, pick, seed, temperature, top_k, top_p, rules=(1.0, 0, 0)):
     mv = model.MVLBert
     B, n_img, _ = feat.shape
     dev = feat.device
@@ -387,10 +423,26 @@ def _greedy_eager_loop(model, ar, feat, max_length, pad, eos, mask_id, cd, pick,
     V = head.predictions.decoder.out_features
     kc, vc = _alloc_cache(model, B, n_img, max_length, cd, dev)
     mask_col = torch.full((B, 1), mask_id, dtype=torch.int64, device=dev)
+    lr = None
+    if rules != (1.0, 0, 0):          # the history the plan reads: the id matrix as the graph keeps it, and the column count
+        hist = torch.zeros((B, max_length), dtype=torch.int64, device=dev)
+        lr = ops.LogitRules(V, *rules, eos, hist, torch.zeros(1, dtype=torch.int64, device=dev))
 
     def next_from(hlast):
         t2, W, bias = _head(model, ar, hlast.contiguous())
         tag = SAMPLE_TAG0 + len(ids_cols)
+        if lr is not None:            # the fused picks in row chunks of 64 (pick: 'gemm_argmax' | 'gemm_sample' | 'filtered')
+            lr.plan()
+            parts = []
+            for r0 in range(0, B, 64):
+                a, rs = t2[r0:r0 + 64], lr.struct(r0)
+                if pick == 'gemm_argmax':
+                    parts.append(ops.gemm_argmax(a, W, bias, rules=rs))
+                elif pick == 'gemm_sample':
+                    parts.append(ops.gemm_sample(a, W, bias, seed, tag, temperature, rules=rs))
+                else:
+                    parts.append(ops.gemm_sample_filtered(a, W, bias, seed, tag, temperature, top_k, top_p, row0=r0, rules=rs))
+            return torch.cat([a for a, _ in parts]), torch.cat([b for _, b in parts])
         if pick == 'gemm_argmax':
             return ops.gemm_argmax(t2, W, bias)
         if pick == 'filtered':        # stand-alone filtered pick; rows beyond 64 in chunks, the noise indexed by the batch row
@@ -416,6 +468,9 @@ def _greedy_eager_loop(model, ar, feat, max_length, pad, eos, mask_id, cd, pick,
             nxt = nxt * unfinished + pad * (1 - unfinished)
             unfinished = unfinished * (nxt != eos).long()
             alive.append(unfinished.max())
+        if lr is not None:
+            lr.ids[:, len(ids_cols)] = nxt
+            lr.col.fill_(len(ids_cols) + 1)
         ids_cols.append(nxt[:, None])
         if _sync_due(eos, len(ids_cols), last=max_length):
             block = torch.stack(alive[-SYNC_EVERY:]).tolist()
@@ -437,7 +492,8 @@ def _greedy_eager_loop(model, ar, feat, max_length, pad, eos, mask_id, cd, pick,
 
 @torch.no_grad()
 def greedy_search(model, image_feature, learning_strategy='unilm', sample_mode='greedy', max_length=None,
-                  pad_token_id=None, eos_token_id=None, seed=None, temperature=1.0, top_k=0, top_p=1.0):
+                  pad_token_id=None, eos_token_id=None, seed=None, temperature=1.0, top_k=0, top_p=1.0,
+                  repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0):
     """Returns ``(input_ids [B, n_steps], token_scores)`` like the reference
     (model.py:984: scores of all but the final step, concatenated along dim -1).
     ``sample_mode='sample'``, B <= 64: Gumbel-max draws from softmax(logits / temperature), reproducible from ``seed``
@@ -447,14 +503,25 @@ def greedy_search(model, image_feature, learning_strategy='unilm', sample_mode='
     ``top_k`` (0 = off) / ``top_p`` (1.0 = off), 'sample' mode only: keep the top_k largest logits (ties at the threshold all
     kept), then the tokens whose probability mass strictly above them is below top_p of what is left; draw among those, score =
     log-probability under the renormalised distribution.  Any B (rows in chunks of 64 beyond that, same draws); a filter in
-    another mode, top_k < 0, top_p <= 0 or a NaN raises ValueError."""
+    another mode, top_k < 0, top_p <= 0 or a NaN raises ValueError.
+    ``repetition_penalty`` (1.0 = off) / ``no_repeat_ngram_size`` (0 = off) / ``min_length`` (0 = off): HF's
+    RepetitionPenaltyLogitsProcessor, NoRepeatNGramLogitsProcessor and MinLengthLogitsProcessor on the raw logits, ahead of the
+    temperature and the filters, over the history as stored (PAD of a finished row included); a banned token takes part in
+    nothing and the scores follow the processed logits.  Both modes, any B, graph and eager loop the same tokens; with all
+    three off the call is the one without them.  The vocabulary must exceed max_length (ValueError)."""
     top_k, top_p = ops.check_sample_filter(top_k, top_p)
+    rules = check_logit_rules(repetition_penalty, no_repeat_ngram_size, min_length)
     if learning_strategy != 'unilm':
         raise NotImplementedError("only learning_strategy='unilm' is coherent with the KV cache (SURVEY.md 3.3)")
     cd, ar, max_length, pad, eos, mask_id, feat = _resolve(model, image_feature, max_length, pad_token_id, eos_token_id)
     V = model.MLM_head_seq2seq.predictions.decoder.out_features
     top_k, top_p = (top_k if top_k < V else 0), min(top_p, 1.0)          # the values that mean "off" in one spelling each
     loop, pick = _greedy_route(sample_mode, feat.shape[0], (top_k, top_p) != (0, 1.0), _env()[0])
+    if rules != (1.0, 0, 0):
+        check_logit_rules(*rules, V=V, max_length=max_length)
+        # rules live in the fused heads only: the two torch picks of B > 64 become their chunked fused forms (a filtered pick with
+        # both filters off draws the unfiltered token bit for bit)
+        pick = {'argmax': 'gemm_argmax', 'multinomial': 'filtered'}.get(pick, pick)
     if sample_mode == 'greedy':
         seed, temperature = 0, 1.0               # unused by the greedy pick, and no part of its graph's key
     elif pick != 'multinomial':
@@ -463,7 +530,7 @@ def greedy_search(model, image_feature, learning_strategy='unilm', sample_mode='
         if seed is None:
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
     search = _greedy_graph_loop if loop == 'graph' else _greedy_eager_loop
-    return search(model, ar, feat, max_length, pad, eos, mask_id, cd, pick, seed, temperature, top_k, top_p)
+    return search(model, ar, feat, max_length, pad, eos, mask_id, cd, pick, seed, temperature, top_k, top_p, rules)
 
 
 # ----------------------------------------------------------------------------- beam search (model.py:636-816)

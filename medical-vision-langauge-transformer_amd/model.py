@@ -760,13 +760,17 @@ class MVLBertForImageCaption(MVLBertPretrainedModel):
         self.MLM_head_seq2seq = BertOnlyMLMHead(config)
 
     def forward(self, image, caption, num_beams, learning_strategy, sample_mode='greedy', seed=None, temperature=1.0, top_k=0, top_p=1.0,
-                labels=None):
+                labels=None, repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0):
         """Reference signature (model.py:479) plus ``labels`` (int64 [B, T], -100 = ignored): with it and ``num_beams == 0`` the
         call returns the scalar ``F.cross_entropy(logits, labels, ignore_index=-100)`` of the fine-tuning loop
         (run_report_generation_cxr.py:469-471) instead of the logits -- the mean over the labelled positions, NaN when there
-        are none -- computed on the labelled rows only, with the loss inside the decoder product (loss_forward)."""
+        are none -- computed on the labelled rows only, with the loss inside the decoder product (loss_forward).
+        ``repetition_penalty`` / ``no_repeat_ngram_size`` / ``min_length``: the logit rules of ``decode.greedy_search``
+        (``num_beams == 1``; with beams they raise ValueError -- the candidate head has no rules yet)."""
         if labels is not None and num_beams >= 1:
             raise ValueError("labels ask for the training loss: num_beams must be 0")
+        from .decode import check_logit_rules
+        rules = check_logit_rules(repetition_penalty, no_repeat_ngram_size, min_length, num_beams=num_beams)
         Arena.of(self, compute_dtype_of(self))
         image_feature = self.conv(image)
         if labels is not None:
@@ -777,7 +781,8 @@ class MVLBertForImageCaption(MVLBertPretrainedModel):
         if num_beams == 1:
             from .decode import greedy_search
             return greedy_search(self, image_feature, learning_strategy=learning_strategy, sample_mode=sample_mode,
-                                 seed=seed, temperature=temperature, top_k=top_k, top_p=top_p)
+                                 seed=seed, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=rules[0],
+                                 no_repeat_ngram_size=rules[1], min_length=rules[2])
         return self.encode_forward(image_feature, caption, learning_strategy)
 
     def encode_forward(self, image_feature, caption, learning_strategy):

@@ -344,25 +344,65 @@ def _head_parts(planes, M, N, device, tag=None):
     return buf
 
 
-def gemm_argmax(A, W, bias=None):
+class LogitRules:
+    """The logit rules of constrained decoding over ``rows`` rows of a V-column head (mvlt_hip.h MvltLogitRules): the two bitmaps
+    [rows, ceil(V / 32)] the plan kernel rebuilds per token from ``ids[:, :col]`` (int64 [rows, ld], the history as stored) and
+    ``col`` (int64 [1], the number of generated tokens) -- both device tensors this object keeps alive -- and the prepared structs.
+    ``struct(row0)``: the view of rows row0 .. of it (the entry points take at most 64 rows: larger batches go in chunks)."""
+
+    def __init__(self, V, penalty, ngram, min_length, eos, ids, col):
+        assert ids.dtype == torch.int64 and ids.dim() == 2 and ids.stride(1) == 1 and col.dtype == torch.int64
+        self.rows, self.V, self.ids, self.col = ids.shape[0], V, ids, col
+        self.ld_words = (V + 31) // 32
+        self.maps = torch.zeros((2, self.rows, self.ld_words), dtype=torch.int32, device=ids.device)
+        self.args = (float(penalty), int(ngram), int(min_length), eos)
+        self._structs = {}
+
+    def struct(self, row0=0):
+        r = self._structs.get(row0)
+        if r is None:
+            r = self._structs[row0] = L.MvltLogitRules()
+            penalty, ngram, min_length, eos = self.args
+            r.seen, r.banned, r.ld_words = _p(self.maps[0, row0:]), _p(self.maps[1, row0:]), self.ld_words
+            r.penalty, r.ngram, r.min_length = penalty, ngram, min_length
+            r.ids, r.ld_ids, r.col = _p(self.ids[row0:]), self.ids.stride(0), _p(self.col)
+            r.eos_id, r.has_eos = (eos if eos is not None else -1), int(eos is not None)
+        return r
+
+    def plan(self):
+        """Rebuild the bitmaps of every row from the history (mvlt_decode_rules_plan, a launch per 64 rows)."""
+        for r0 in range(0, self.rows, 64):
+            L.check(L.lib().mvlt_decode_rules_plan(C.byref(self.struct(r0)), min(64, self.rows - r0), self.V, _stream()),
+                    "mvlt_decode_rules_plan")
+
+
+def gemm_argmax(A, W, bias=None, rules=None):
     """argmax_n (A @ W^T + bias) and its value, without materialising the logits (greedy decoding).
-    A: [M <= 64, K], W: [N, K] -> (int64 [M], f32 [M])."""
+    A: [M <= 64, K], W: [N, K] -> (int64 [M], f32 [M]).  ``rules`` (here and in the five head functions below): a prepared
+    ``L.MvltLogitRules`` whose bitmaps the plan has filled -- the _rules form of the entry point applies them to the raw logits."""
     p, M, N = _head_gemm(A, W, bias)
     nblk = (N + 15) // 16
     pv = torch.empty((M, nblk), dtype=torch.float32, device=A.device)          # a stand-alone call: its scratch lives as long as the call
     pi = torch.empty((M, nblk), dtype=torch.int32, device=A.device)
     idx = torch.empty(M, dtype=torch.int64, device=A.device)
     val = torch.empty(M, dtype=torch.float32, device=A.device)
+    if rules is not None:
+        L.check(L.lib().mvlt_gemm_argmax_rules(C.byref(p), _p(pv), _p(pi), _p(idx), _p(val), C.byref(rules), _stream()), "mvlt_gemm_argmax_rules")
+        return idx, val
     L.check(L.lib().mvlt_gemm_argmax(C.byref(p), _p(pv), _p(pi), _p(idx), _p(val), _stream()), "mvlt_gemm_argmax")
     return idx, val
 
 
-def gemm_argmax_greedy(A, W, bias, state):
+def gemm_argmax_greedy(A, W, bias, state, rules=None):
     """Decoder GEMM + greedy pick + the per-token bookkeeping of greedy_search in two launches (mvlt_gemm_argmax_greedy).
     A: [M <= 64, K] (rows may be strided), W: [N, K]; ``state``: a prepared ``L.MvltGreedyState`` (decode._GreedyGraph)."""
     # A.stride(0), not _ld(A): the head reads the [MASK] rows in place, at row stride 2 H of the step's hidden states
     p, M, N = _head_gemm(A, W, bias, lda=A.stride(0))
     pv, pi = _head_parts(1, M, N, A.device)
+    if rules is not None:
+        L.check(L.lib().mvlt_gemm_argmax_greedy_rules(C.byref(p), _p(pv), _p(pi), C.byref(state), C.byref(rules), _stream()),
+                "mvlt_gemm_argmax_greedy_rules")
+        return
     L.check(L.lib().mvlt_gemm_argmax_greedy(C.byref(p), _p(pv), _p(pi), C.byref(state), _stream()), "mvlt_gemm_argmax_greedy")
 
 
@@ -371,7 +411,7 @@ def _sample_parts(M, N, device):
     return _head_parts(4, M, N, device, tag=_stream_cache[1])
 
 
-def gemm_sample(A, W, bias, seed, tag, temperature=1.0):
+def gemm_sample(A, W, bias, seed, tag, temperature=1.0, rules=None):
     """One draw per row from softmax((A @ W^T + bias) / temperature) by Gumbel-max and its log-probability, without
     materialising the logits (mvlt_gemm_sample; the noise is a pure function of (seed, tag, row, column)).
     A: [M <= 64, K] (rows may be strided), W: [N, K] -> (int64 [M], f32 [M])."""
@@ -379,16 +419,24 @@ def gemm_sample(A, W, bias, seed, tag, temperature=1.0):
     pv, pi = _sample_parts(M, N, A.device)
     idx = torch.empty(M, dtype=torch.int64, device=A.device)
     lp = torch.empty(M, dtype=torch.float32, device=A.device)
+    if rules is not None:
+        L.check(L.lib().mvlt_gemm_sample_rules(C.byref(p), _p(pv), _p(pi), _p(idx), _p(lp), int(seed) & ((1 << 64) - 1), int(tag) & 0xFFFFFFFF,
+                                               1.0 / float(temperature), C.byref(rules), _stream()), "mvlt_gemm_sample_rules")
+        return idx, lp
     L.check(L.lib().mvlt_gemm_sample(C.byref(p), _p(pv), _p(pi), _p(idx), _p(lp), int(seed) & ((1 << 64) - 1), int(tag) & 0xFFFFFFFF,
                                      1.0 / float(temperature), _stream()), "mvlt_gemm_sample")
     return idx, lp
 
 
-def gemm_sample_step(A, W, bias, state):
+def gemm_sample_step(A, W, bias, state, rules=None):
     """Decoder GEMM + sampled pick + the per-token bookkeeping of greedy_search in two launches (mvlt_gemm_sample_step).
     ``state``: a prepared ``L.MvltSampleState`` (decode._GreedyGraph, mode 'sample')."""
     p, M, N = _head_gemm(A, W, bias)
     pv, pi = _sample_parts(M, N, A.device)
+    if rules is not None:
+        L.check(L.lib().mvlt_gemm_sample_step_rules(C.byref(p), _p(pv), _p(pi), C.byref(state), C.byref(rules), _stream()),
+                "mvlt_gemm_sample_step_rules")
+        return
     L.check(L.lib().mvlt_gemm_sample_step(C.byref(p), _p(pv), _p(pi), C.byref(state), _stream()), "mvlt_gemm_sample_step")
 
 
@@ -420,7 +468,7 @@ def _sample_filter(M, N, device, top_k, top_p, row0):
     return f, ws
 
 
-def gemm_sample_filtered(A, W, bias, seed, tag, temperature=1.0, top_k=0, top_p=1.0, row0=0):
+def gemm_sample_filtered(A, W, bias, seed, tag, temperature=1.0, top_k=0, top_p=1.0, row0=0, rules=None):
     """gemm_sample behind a top-k / top-p filter (mvlt_gemm_sample_filtered): per row, keep the top_k largest logits (ties at
     the threshold all kept; 0 = off), then the tokens whose mass strictly above is below top_p of what is left (1.0 = off), draw
     among them by Gumbel-max and return the log-probability under the renormalised distribution.  ``row0``: index of row 0
@@ -432,18 +480,27 @@ def gemm_sample_filtered(A, W, bias, seed, tag, temperature=1.0, top_k=0, top_p=
     f, _ = _sample_filter(M, N, A.device, top_k, top_p, row0)
     idx = torch.empty(M, dtype=torch.int64, device=A.device)
     lp = torch.empty(M, dtype=torch.float32, device=A.device)
+    if rules is not None:
+        L.check(L.lib().mvlt_gemm_sample_filtered_rules(C.byref(p), _p(pv), _p(pi), C.byref(f), _p(idx), _p(lp), int(seed) & ((1 << 64) - 1),
+                                                        int(tag) & 0xFFFFFFFF, 1.0 / float(temperature), C.byref(rules), _stream()),
+                "mvlt_gemm_sample_filtered_rules")
+        return idx, lp
     L.check(L.lib().mvlt_gemm_sample_filtered(C.byref(p), _p(pv), _p(pi), C.byref(f), _p(idx), _p(lp), int(seed) & ((1 << 64) - 1),
                                               int(tag) & 0xFFFFFFFF, 1.0 / float(temperature), _stream()), "mvlt_gemm_sample_filtered")
     return idx, lp
 
 
-def gemm_sample_filtered_step(A, W, bias, state, top_k=0, top_p=1.0):
+def gemm_sample_filtered_step(A, W, bias, state, top_k=0, top_p=1.0, rules=None):
     """gemm_sample_step with the filtered pick as its finish (mvlt_gemm_sample_filtered_step); ``state``: a prepared
     ``L.MvltSampleState`` (decode._GreedyGraph, mode 'sample' with a filter)."""
     top_k, top_p = check_sample_filter(top_k, top_p)
     p, M, N = _head_gemm(A, W, bias)
     pv, pi = _sample_parts(M, N, A.device)
     f, _ = _sample_filter(M, N, A.device, top_k, top_p, 0)
+    if rules is not None:
+        L.check(L.lib().mvlt_gemm_sample_filtered_step_rules(C.byref(p), _p(pv), _p(pi), C.byref(f), C.byref(state), C.byref(rules), _stream()),
+                "mvlt_gemm_sample_filtered_step_rules")
+        return
     L.check(L.lib().mvlt_gemm_sample_filtered_step(C.byref(p), _p(pv), _p(pi), C.byref(f), C.byref(state), _stream()),
             "mvlt_gemm_sample_filtered_step")
 
