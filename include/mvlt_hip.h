@@ -709,6 +709,25 @@ int mvlt_ce_bwd_ragged(int dtype, const void* logits, int64_t ld, int rows, int 
 int mvlt_adamw(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16,
                int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
                int step, float grad_scale, void* stream);
+/* Global-norm gradient clipping and non-finite step skip, without a host round trip (three plain-argument entry points, no struct).
+ * mvlt_grad_sumsq: sum of squares of g[0..n) in f64 -- every element is widened before it is squared, so the squares are exact
+ * and 3e19 does not overflow -- over a FIXED grid of mvlt_grad_sumsq_parts() workgroups: workgroup b stores its sum to partial[b],
+ * or adds it to what is there when accumulate != 0.  Consecutive calls on one stream add the ranges of a step in a fixed order:
+ * no float atomics, bit-reproducible.  g 16-byte aligned, n >= 1, partial holds mvlt_grad_sumsq_parts() doubles. */
+int mvlt_grad_sumsq_parts(void);
+int mvlt_grad_sumsq(const float* g, int64_t n, double* partial, int accumulate, void* stream);
+/* sum = partial[0] + ... + partial[nparts - 1] (f64, index order);
+ *   out[0]   = norm = (float)(fabs(grad_scale) * sqrt(sum))
+ *   out[1]   = coef = min(1, max_norm / (norm + 1e-6f)) in f32 (torch.nn.utils.clip_grad_norm_; a NaN norm gives a NaN coef);
+ *                     1 when max_norm <= 0 (no clipping)
+ *   flags[0] = skip = skip_nonfinite && !isfinite(sum);   flags[1] += skip (running count) */
+int mvlt_grad_norm_finish(const double* partial, int nparts, float grad_scale, float max_norm, int skip_nonfinite,
+                          float* out, int32_t* flags, void* stream);
+/* mvlt_adamw with the gradient scale grad_scale * *coef_dev (one f32 product); writes NOTHING when *skip_dev != 0.  The element
+ * arithmetic is mvlt_adamw's own: with *coef_dev == 1 and *skip_dev == 0 the results are bit-identical. */
+int mvlt_adamw_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16,
+                       int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
+                       int step, float grad_scale, const float* coef_dev, const int32_t* skip_dev, void* stream);
 
 /* ------------------------------------------------------------------ decode (greedy, KV cache)
  * 2-token cached step attention (model.py:82-108): q rows = n_new new tokens,

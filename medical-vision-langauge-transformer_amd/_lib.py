@@ -263,6 +263,10 @@ SYMBOLS = {
     "mvlt_gelu_bwd": (i32, [i32, vp, vp, vp, i64, vp]),
     "mvlt_softmax_rows": (i32, [i32, vp, i64, i32, i32, vp, vp]),
     "mvlt_adamw": (i32, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp]),
+    "mvlt_adamw_guarded": (i32, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp, vp, vp]),
+    "mvlt_grad_sumsq_parts": (i32, []),
+    "mvlt_grad_sumsq": (i32, [vp, i64, vp, i32, vp]),
+    "mvlt_grad_norm_finish": (i32, [vp, i32, f32, f32, i32, vp, vp, vp]),
     "mvlt_attn_cached": (i32, [C.POINTER(MvltAttnCached), vp]),
     "mvlt_attn_cached_beam": (i32, [C.POINTER(MvltAttnCachedBeam), vp]),
     "mvlt_beam_step": (i32, [C.POINTER(MvltBeamStep), vp]),

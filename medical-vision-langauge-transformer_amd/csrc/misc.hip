@@ -393,9 +393,10 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const T* logits, long ld, i
 }
 
 // ------------------------------------------------------------------ AdamW
-__global__ __launch_bounds__(256) void adamw_kernel(float* p, const float* g, float* m, float* v, bf16_t* sh, long n,
-                                                   float lr, float b1, float b2, float eps, float wd,
-                                                   float bc1, float bc2_sqrt, float gscale) {
+// The sweep of adamw_kernel and adamw_guarded_kernel: ONE body, so that the guarded launch with coef = 1 is bit for bit the plain one.
+MVLT_DEV void adamw_sweep(float* p, const float* g, float* m, float* v, bf16_t* sh, long n,
+                          float lr, float b1, float b2, float eps, float wd,
+                          float bc1, float bc2_sqrt, float gscale) {
     // torch.optim.AdamW (single tensor path): p *= 1-lr*wd; m,v update; p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps)
     const long nv = n / 4;
     // The fp32 master, both moments and the gradient are read and written once per step (28 of the 30 bytes per
@@ -428,6 +429,76 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* p, const float* g, fl
         p[i] = pp; m[i] = mm; v[i] = vv;
         if (sh) sh[i] = (bf16_t)pp;
     }
+}
+__global__ __launch_bounds__(256) void adamw_kernel(float* p, const float* g, float* m, float* v, bf16_t* sh, long n,
+                                                   float lr, float b1, float b2, float eps, float wd,
+                                                   float bc1, float bc2_sqrt, float gscale) {
+    adamw_sweep(p, g, m, v, sh, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale);
+}
+// The same sweep behind a clip coefficient and a skip flag that mvlt_grad_norm_finish left on the device: the gradient scale is
+// gscale * *coef (one f32 product), and a raised flag ends every workgroup before its first access -- a skipped step writes nothing.
+__global__ __launch_bounds__(256) void adamw_guarded_kernel(float* p, const float* g, float* m, float* v, bf16_t* sh, long n,
+                                                           float lr, float b1, float b2, float eps, float wd,
+                                                           float bc1, float bc2_sqrt, float gscale,
+                                                           const float* coef, const int32_t* skip) {
+    if (*skip != 0) return;
+    adamw_sweep(p, g, m, v, sh, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale * *coef);
+}
+
+// ------------------------------------------------------------------ gradient norm (clipping, non-finite step skip)
+// Sum of squares of one f32 range in f64: every element is widened BEFORE it is squared (the product of two f32 values is exact in
+// f64, and a gradient of 3e19 does not overflow), so the only rounding is that of the additions.  A FIXED grid of persistent
+// workgroups (an HBM stream, like the AdamW sweep); workgroup b owns partial[b] and stores its sum there or adds it to what is
+// there, so consecutive launches on one stream add the ranges of a step in a fixed order: no float atomics, bit-reproducible.
+// Addition chain of one partial per launch: ceil(n / 4 / (GRAD_SUMSQ_PARTS * 256)) vectors into four per-lane sums, 2 to fold the
+// four, 1 tail element, 6 butterfly levels, 3 to fold the four waves, 1 into partial[b].  Non-temporal loads: the gradients are
+// read again by the sweep right behind, out of HBM either way (730 MB); they must not evict what the next forward pass reads.
+constexpr int GRAD_SUMSQ_PARTS = 512, GRAD_SUMSQ_U = 4;
+MVLT_DEV void sumsq_acc(double (&s)[4], const f32x4 x) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { const double d = (double)x[e]; s[e] += d * d; }
+}
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* g, long n, double* partial, int accumulate) {
+    __shared__ double red[4];
+    const long nv = n / 4, stride = (long)gridDim.x * 256;
+    const f32x4* gv = reinterpret_cast<const f32x4*>(g);
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    long i = (long)blockIdx.x * 256 + threadIdx.x;
+    for (; i + (GRAD_SUMSQ_U - 1) * stride < nv; i += GRAD_SUMSQ_U * stride) {      // GRAD_SUMSQ_U loads in flight per lane
+        f32x4 x[GRAD_SUMSQ_U];
+#pragma unroll
+        for (int u = 0; u < GRAD_SUMSQ_U; ++u) x[u] = __builtin_nontemporal_load(gv + i + u * stride);
+#pragma unroll
+        for (int u = 0; u < GRAD_SUMSQ_U; ++u) sumsq_acc(s, x[u]);
+    }
+    for (; i < nv; i += stride) sumsq_acc(s, __builtin_nontemporal_load(gv + i));
+    double t = (s[0] + s[1]) + (s[2] + s[3]);
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) { const double d = (double)g[nv * 4 + threadIdx.x]; t += d * d; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = t;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        t = ((red[0] + red[1]) + red[2]) + red[3];
+        partial[blockIdx.x] = accumulate ? partial[blockIdx.x] + t : t;
+    }
+}
+// One wave; lane 0 adds the partials in index order (512 f64 additions, once per step) and derives everything the guarded sweep and
+// the host need.  coef as torch.nn.utils.clip_grad_norm_ computes it, in f32; a NaN norm stays NaN (fminf would drop it).
+__global__ __launch_bounds__(64) void grad_norm_finish_kernel(const double* partial, int nparts, float gscale, float max_norm,
+                                                             int skip_nonfinite, float* out, int32_t* flags) {
+    if (threadIdx.x != 0) return;
+    double sum = 0.0;
+#pragma unroll 16
+    for (int i = 0; i < nparts; ++i) sum += partial[i];
+    const float norm = (float)(fabs((double)gscale) * sqrt(sum));
+    float coef = 1.0f;
+    if (max_norm > 0.0f) { const float c = max_norm / (norm + 1e-6f); coef = c > 1.0f ? 1.0f : c; }
+    const int skip = (skip_nonfinite && !isfinite(sum)) ? 1 : 0;
+    out[0] = norm;
+    out[1] = coef;
+    flags[0] = skip;
+    flags[1] += skip;
 }
 
 // ------------------------------------------------------------------ decode: cached attention + argmax
@@ -1092,20 +1163,51 @@ extern "C" int mvlt_softmax_rows(int dtype, const void* x, int64_t ld, int rows,
     return MVLT_OK;
 }
 
+static int adamw_blocks() {
+    // TWO 256-thread workgroups per CU, not thousands: the sweep is seven interleaved streams (four read, three and a half written)
+    // and HBM serves them best when few waves walk them -- stand-alone 6.0-6.1 TB/s with 256-768 workgroups against 5.3 with 8192
+    // (scripts/adamw_probe.hip, 182.4 M parameters: 0.90 vs 1.03 ms); in the step 512 is the best of 256 / 384 / 512 / 1024 / 8192
+    // (optimizer phase 0.845 vs 0.88 ms on a box with fast HBM, step -0.08 ms on a slower one; profiles/r5_adamw_grid.txt)
+    static const int cap = [] { const char* e = getenv("MVLT_ADAMW_BLOCKS"); return e && atoi(e) > 0 ? atoi(e) : 512; }();
+    return cap;
+}
 extern "C" int mvlt_adamw(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16,
                           int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                           float grad_scale, void* stream) {
     MVLT_CHECK(param && grad && exp_avg && exp_avg_sq && n > 0 && step >= 1, MVLT_ERR_ARG);
     MVLT_CHECK(aligned16(param) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq), MVLT_ERR_ARG);
     const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
-    // TWO 256-thread workgroups per CU, not thousands: the sweep is seven interleaved streams (four read, three and a half written)
-    // and HBM serves them best when few waves walk them -- stand-alone 6.0-6.1 TB/s with 256-768 workgroups against 5.3 with 8192
-    // (scripts/adamw_probe.hip, 182.4 M parameters: 0.90 vs 1.03 ms); in the step 512 is the best of 256 / 384 / 512 / 1024 / 8192
-    // (optimizer phase 0.845 vs 0.88 ms on a box with fast HBM, step -0.08 ms on a slower one; profiles/r5_adamw_grid.txt)
-    static const int cap = [] { const char* e = getenv("MVLT_ADAMW_BLOCKS"); return e && atoi(e) > 0 ? atoi(e) : 512; }();
-    hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n / 4 + 1, 256, cap)), dim3(256), 0, STREAM(stream), param, grad, exp_avg,
+    hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n / 4 + 1, 256, adamw_blocks())), dim3(256), 0, STREAM(stream), param, grad, exp_avg,
                        exp_avg_sq, (bf16_t*)shadow_bf16, (long)n, lr, beta1, beta2, eps, weight_decay, (float)bc1,
                        (float)sqrt(bc2), grad_scale);
+    MVLT_LAUNCH_CHECK();
+    return MVLT_OK;
+}
+extern "C" int mvlt_adamw_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16,
+                                  int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
+                                  float grad_scale, const float* coef_dev, const int32_t* skip_dev, void* stream) {
+    MVLT_CHECK(param && grad && exp_avg && exp_avg_sq && coef_dev && skip_dev && n > 0 && step >= 1, MVLT_ERR_ARG);
+    MVLT_CHECK(aligned16(param) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq), MVLT_ERR_ARG);
+    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+    hipLaunchKernelGGL(adamw_guarded_kernel, dim3(grid_for(n / 4 + 1, 256, adamw_blocks())), dim3(256), 0, STREAM(stream), param,
+                       grad, exp_avg, exp_avg_sq, (bf16_t*)shadow_bf16, (long)n, lr, beta1, beta2, eps, weight_decay, (float)bc1,
+                       (float)sqrt(bc2), grad_scale, coef_dev, skip_dev);
+    MVLT_LAUNCH_CHECK();
+    return MVLT_OK;
+}
+
+extern "C" int mvlt_grad_sumsq_parts(void) { return GRAD_SUMSQ_PARTS; }
+extern "C" int mvlt_grad_sumsq(const float* g, int64_t n, double* partial, int accumulate, void* stream) {
+    MVLT_CHECK(g && partial && n >= 1 && aligned16(g), MVLT_ERR_ARG);
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(GRAD_SUMSQ_PARTS), dim3(256), 0, STREAM(stream), g, (long)n, partial, accumulate);
+    MVLT_LAUNCH_CHECK();
+    return MVLT_OK;
+}
+extern "C" int mvlt_grad_norm_finish(const double* partial, int nparts, float grad_scale, float max_norm, int skip_nonfinite,
+                                     float* out, int32_t* flags, void* stream) {
+    MVLT_CHECK(partial && out && flags && nparts >= 1, MVLT_ERR_ARG);
+    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(64), 0, STREAM(stream), partial, nparts, grad_scale, max_norm,
+                       skip_nonfinite, out, flags);
     MVLT_LAUNCH_CHECK();
     return MVLT_OK;
 }

@@ -1090,7 +1090,9 @@ def _wmsa2_raise(n):
     raise DeviceHandoffError(
         f"mvlt_swin_wmsa2_fwd: {n} hand-off wait(s) between head-group workgroups ran out (the groups of a window pair were "
         "not resident together -- another kernel or process was holding CUs / LDS).  The affected rows of the block output "
-        "were written as NaN.  Set MVLT_WMSA2=0 to use the kernels without an in-launch hand-off.")
+        "were written as NaN.  A training step that ran on them has applied NaN gradients (reload the last checkpoint) unless its "
+        "optimizer was built with skip_nonfinite=True, which refused that step: training can then continue.  "
+        "Set MVLT_WMSA2=0 to use the kernels without an in-launch hand-off.")
 
 
 def wmsa2_sync_errors():
@@ -1474,6 +1476,48 @@ def adamw(param, grad, exp_avg, exp_avg_sq, shadow, lr, beta1, beta2, eps, weigh
     L.check(L.lib().mvlt_adamw(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), _p(shadow), param.numel(),
                                float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step),
                                float(grad_scale), _stream()), "mvlt_adamw")
+
+
+def adamw_guarded(param, grad, exp_avg, exp_avg_sq, shadow, lr, beta1, beta2, eps, weight_decay, step, grad_scale, coef, skip):
+    """adamw with the gradient scale ``grad_scale * coef[0]`` (f32 on the device) that writes nothing when ``skip[0] != 0``
+    (int32 on the device): the consumer of grad_norm_finish."""
+    _need_cuda(param, coef, skip)
+    assert coef.dtype == torch.float32 and skip.dtype == torch.int32
+    L.check(L.lib().mvlt_adamw_guarded(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), _p(shadow), param.numel(),
+                                       float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step),
+                                       float(grad_scale), _p(coef), _p(skip), _stream()), "mvlt_adamw_guarded")
+
+
+def grad_sumsq_parts():
+    return int(L.lib().mvlt_grad_sumsq_parts())
+
+
+def grad_sumsq(g, partial=None, accumulate=False):
+    """partial[b] (f64 [grad_sumsq_parts()]) = or += the sum of squares workgroup b takes of the f32 range ``g``, every element
+    widened to f64 before it is squared.  The sum of ``partial`` is the squared L2 norm; no float atomics, bit-reproducible."""
+    _need_cuda(g)
+    assert g.dtype == torch.float32 and g.is_contiguous()
+    if partial is None:
+        assert not accumulate
+        partial = torch.empty(grad_sumsq_parts(), dtype=torch.float64, device=g.device)
+    assert partial.dtype == torch.float64 and partial.is_contiguous() and partial.numel() == grad_sumsq_parts()
+    L.check(L.lib().mvlt_grad_sumsq(_p(g), g.numel(), _p(partial), 1 if accumulate else 0, _stream()), "mvlt_grad_sumsq")
+    return partial
+
+
+def grad_norm_finish(partial, grad_scale=1.0, max_norm=0.0, skip_nonfinite=False, out=None, flags=None):
+    """out (f32 [2]) = (norm, clip coefficient), flags (int32 [2]) = (skip this step, running count of skipped steps) from the
+    partial sums of grad_sumsq; ``flags`` must be initialised (the count is added to)."""
+    _need_cuda(partial)
+    if out is None:
+        out = torch.empty(2, dtype=torch.float32, device=partial.device)
+    if flags is None:
+        flags = torch.zeros(2, dtype=torch.int32, device=partial.device)
+    assert partial.dtype == torch.float64 and out.dtype == torch.float32 and flags.dtype == torch.int32
+    assert out.numel() >= 2 and flags.numel() >= 2
+    L.check(L.lib().mvlt_grad_norm_finish(_p(partial), partial.numel(), float(grad_scale), float(max_norm),
+                                          1 if skip_nonfinite else 0, _p(out), _p(flags), _stream()), "mvlt_grad_norm_finish")
+    return out, flags
 
 
 def attn_cached(qkv_new, k_cache, v_cache, past, scale, out=None):

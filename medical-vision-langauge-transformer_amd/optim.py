@@ -15,7 +15,15 @@ all-reduce has been issued) is queued on a third HIP stream while the
 backward pass continues below it.  ``step()`` then only handles what is left
 and joins the stream.  Same arithmetic, same result; only for loops that call
 ``backward(); step()`` once each per batch (mvlt_amd.train.PretrainStep).
+
+``max_grad_norm`` / ``skip_nonfinite`` (opt-in; the reference does neither): the L2 norm of the live gradient set is
+taken on the device (``mvlt_grad_sumsq`` over the runs of the sweep, ``mvlt_grad_norm_finish``) and the sweep becomes
+``mvlt_adamw_guarded``, which reads the clip coefficient and the skip flag from device memory: global-norm clipping
+as ``torch.nn.utils.clip_grad_norm_`` defines it, and a step whose gradients hold a NaN or an Inf is not applied --
+no host synchronisation in either case.  With both options off the launches are the ones described above.
 """
+import math
+
 import torch
 
 from . import ops
@@ -85,7 +93,8 @@ class _OptTail:
 
 
 class FusedAdamW:
-    def __init__(self, model, lr=4e-5, betas=(0.9, 0.999), eps=1e-6, weight_decay=1e-4, grad_scale=1.0, defer_tail=False):
+    def __init__(self, model, lr=4e-5, betas=(0.9, 0.999), eps=1e-6, weight_decay=1e-4, grad_scale=1.0, defer_tail=False,
+                 max_grad_norm=None, skip_nonfinite=False):
         self.model = model
         # defer_tail (opt-in, mvlt_amd.train.PretrainStep(defer_optimizer_tail=True)): step() updates the parameters the next
         # forward pass reads FIRST (Swin tower, embeddings, BertLayer 0) and leaves the rest -- BertLayers 1.., pooler, heads:
@@ -101,8 +110,88 @@ class FusedAdamW:
         self._overlap = None                   # dict(reducer=, chunk=) when enabled
         self._stepped = set()                  # id(param) already updated during the current backward pass
         self._pending_hi = 0
+        # max_grad_norm: clip the global L2 norm of the gradients (grad_scale folded in, i.e. of the rank-averaged gradient under
+        # DDP) to this value, torch.nn.utils.clip_grad_norm_ semantics.  skip_nonfinite: a step whose norm is not finite never
+        # happened -- parameters, moments, bf16 copy and step counts stay as they were; ``steps_skipped`` counts them.  Both need
+        # every gradient of the step before the first update, so neither combines with overlap_with_backward() or defer_tail
+        # (ValueError, whichever is asked for first); both can be assigned later (opt.max_grad_norm = 1.0).
+        self._max_grad_norm, self._skip_nonfinite = None, False
+        self.last_grad_norm = None             # f32 device tensor [] of the last guarded step (no sync to obtain it)
+        self._guard_ws = None                  # dict(partial=, out=, flags=, host=) on the arena's device
+        self._guard_pending = None             # (arena, event, ids bumped by the last guarded step): see _reconcile
+        self._skipped = 0
+        self.max_grad_norm = max_grad_norm
+        self.skip_nonfinite = skip_nonfinite
+
+    @property
+    def max_grad_norm(self):
+        return self._max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, value):
+        if value is not None:
+            if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(value) or value <= 0:
+                raise ValueError(f"max_grad_norm must be a finite number > 0 (or None: no clipping), got {value!r}")
+            self._refuse_guard_beside_partial_sweeps()
+            value = float(value)
+        self._max_grad_norm = value
+
+    @property
+    def skip_nonfinite(self):
+        return self._skip_nonfinite
+
+    @skip_nonfinite.setter
+    def skip_nonfinite(self, value):
+        if value:
+            self._refuse_guard_beside_partial_sweeps()
+        self._skip_nonfinite = bool(value)
+
+    def _refuse_guard_beside_partial_sweeps(self) -> None:
+        if self.defer_tail:
+            raise ValueError("max_grad_norm / skip_nonfinite cannot be combined with defer_tail=True: the deferred part of the "
+                             "sweep runs after the next forward pass has started")
+        if self._overlap is not None:
+            raise ValueError("max_grad_norm / skip_nonfinite cannot be combined with overlap_with_backward(): the overlapped "
+                             "sweep starts before all gradients of the step exist")
+
+    @property
+    def _guarded(self) -> bool:
+        return self._max_grad_norm is not None or self._skip_nonfinite
+
+    @property
+    def steps_skipped(self) -> int:
+        """Steps that skip_nonfinite refused so far (waits for the last step's flag: may synchronise)."""
+        self._reconcile()
+        return self._skipped
+
+    def _reconcile(self) -> None:
+        """The step counts live on the host and are bumped when a step is LAUNCHED; whether the device applied it is known one
+        copy later.  The skip flag of the last guarded step travelled to pinned host memory behind its sweep: wait for it (in
+        steady state it is a whole step old) and take the bump back if that step was refused."""
+        pend = self._guard_pending
+        if pend is None:
+            return
+        self._guard_pending = None
+        ar, ev, bumped = pend
+        ev.synchronize()
+        if int(self._guard_ws["host"][0]):
+            self._skipped += 1
+            for pid in bumped:
+                ar.steps[pid] -= 1
+
+    def _guard_buffers(self, ar: Arena):
+        ws = self._guard_ws
+        if ws is None or ws["out"].device != ar.flat.device:
+            dev = ar.flat.device
+            ws = self._guard_ws = dict(partial=torch.zeros(ops.grad_sumsq_parts(), dtype=torch.float64, device=dev),
+                                       out=torch.zeros(2, dtype=torch.float32, device=dev),
+                                       flags=torch.zeros(2, dtype=torch.int32, device=dev),
+                                       host=torch.zeros(1, dtype=torch.int32).pin_memory())
+            self.last_grad_norm = ws["out"][0]
+        return ws
 
     def _state(self) -> Arena:
+        self._reconcile()                # (before a rebuilt arena inherits the step counts)
         ar = Arena.of(self.model, compute_dtype_of(self.model))
         if ar is not self._arena or ar.exp_avg is None:
             ar.exp_avg = torch.zeros_like(ar.flat)
@@ -209,6 +298,9 @@ class FusedAdamW:
 
     # ------------------------------------------------------------------ overlap with the backward pass
     def overlap_with_backward(self, reducer=None, chunk_bytes: int = 64 << 20) -> "FusedAdamW":
+        if self._guarded:
+            raise ValueError("overlap_with_backward() cannot be combined with max_grad_norm / skip_nonfinite: the overlapped sweep "
+                             "starts before all gradients of the step exist")
         self._overlap = dict(reducer=reducer, chunk=chunk_bytes // 4)
         self._hook(self._state())
         return self
@@ -264,7 +356,8 @@ class FusedAdamW:
 
     # ------------------------------------------------------------------ the torch.optim-style entry point
     def flush(self):
-        """Apply a deferred optimizer tail now (in stream order).  No-op otherwise."""
+        """Apply a deferred optimizer tail now (in stream order); settle the step counts of a guarded step.  No-op otherwise."""
+        self._reconcile()
         ar = self._arena
         if ar is not None and ar.__dict__.get("_opt_tail") is not None:
             ar._opt_tail.flush()
@@ -293,6 +386,28 @@ class FusedAdamW:
         self._tail_cache = (key, bounds)
         return bounds
 
+    def _guarded_sweep(self, ar: Arena, plan) -> None:
+        """Norm of the step's live gradients, clip coefficient and skip flag on the device, then the sweep that obeys them: all on
+        the current stream, no host sync.  The runs include the ALIGN padding of the gradient arena, which is allocated zeroed and
+        never written.  Every rank of a data-parallel run reads the same reduced bytes, so all ranks clip and skip alike."""
+        ws = self._guard_buffers(ar)
+        steps = ar.steps
+        b1, b2 = self.betas
+        for k, (lo, hi, _) in enumerate(plan):
+            ops.grad_sumsq(ar.grad[lo:hi], ws["partial"], accumulate=k > 0)
+        ops.grad_norm_finish(ws["partial"], self.grad_scale, self.max_grad_norm or 0.0, self.skip_nonfinite, ws["out"], ws["flags"])
+        coef, skip = ws["out"][1:], ws["flags"][:1]
+        for lo, hi, ids in plan:
+            ops.adamw_guarded(ar.flat[lo:hi], ar.grad[lo:hi], ar.exp_avg[lo:hi], ar.exp_avg_sq[lo:hi],
+                              ar.shadow[lo:hi] if ar.shadow is not None else None,
+                              self.lr, b1, b2, self.eps, self.weight_decay, steps[ids[0]] + 1, self.grad_scale, coef, skip)
+        if self.skip_nonfinite:
+            # (the pinned word is free: _state() has waited for the previous step's copy)
+            ws["host"].copy_(skip, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream())
+            self._guard_pending = (ar, ev, tuple(id(p) for p in ar._marked))
+
     @torch.no_grad()
     def step(self):
         ar = self._state()
@@ -315,6 +430,9 @@ class FusedAdamW:
                 if key is not None:
                     self._plans[key] = plan
             b1, b2 = self.betas
+            if self._guarded and plan:
+                self._guarded_sweep(ar, plan)
+                plan = ()
             bounds = self._tail_bounds(ar) if (self.defer_tail and ar.flat.is_cuda) else None
             tail = []                    # (lo, hi, step) pieces above the split, in arena order
             for lo, hi, ids in plan:

@@ -39,15 +39,23 @@ class PretrainStep:
     """loss = model(batch); loss.backward(); optimizer.step()  -- one call per step.
     ``reducer`` (mvlt_amd.ddp.GradReducer) makes it data parallel."""
 
-    def __init__(self, model, lr=None, reducer=None, world_size=1, overlap_optimizer=False, defer_optimizer_tail=False):
-        """defer_optimizer_tail (opt-in): the AdamW sweep over BertLayers 1.., pooler and heads is left to the NEXT call, which
+    def __init__(self, model, lr=None, reducer=None, world_size=1, overlap_optimizer=False, defer_optimizer_tail=False,
+                 max_grad_norm=None, skip_nonfinite=False):
+        """max_grad_norm / skip_nonfinite (opt-in, optim.FusedAdamW): clip the global L2 norm of the (rank-averaged) gradients; do
+        not apply a step whose gradients hold a NaN or an Inf.  Both are decided on the device, and under a ``reducer`` every rank
+        decides alike.  Neither combines with overlap_optimizer or defer_optimizer_tail (ValueError).
+        defer_optimizer_tail (opt-in): the AdamW sweep over BertLayers 1.., pooler and heads is left to the NEXT call, which
         runs it beside its encoder forward (optim.FusedAdamW(defer_tail=True)); between two calls those parameters are one
         update behind until something reads them -- a forward pass, ``flush()``, state_dict() / save_pretrained() all apply it."""
         self.model = model
+        if (max_grad_norm is not None or skip_nonfinite) and (overlap_optimizer or defer_optimizer_tail):
+            raise ValueError("max_grad_norm / skip_nonfinite need every gradient of the step before the first update: they cannot be "
+                             "combined with overlap_optimizer or defer_optimizer_tail")
         # the reducer hands out rank-averaged gradients by default (like torch DDP); a SUM reducer is rescaled here
         gs = 1.0 if (reducer is None or getattr(reducer, "average", False)) else 1.0 / world_size
         self.opt = FusedAdamW(model, lr=lr if lr is not None else model.config.lr, betas=(0.9, 0.999), eps=1e-6,
-                              weight_decay=1e-4, grad_scale=gs, defer_tail=defer_optimizer_tail and not overlap_optimizer)
+                              weight_decay=1e-4, grad_scale=gs, defer_tail=defer_optimizer_tail and not overlap_optimizer,
+                              max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
         self.reducer = reducer
         if overlap_optimizer:
             # opt-in: AdamW of finished arena slices is queued beside the rest of the backward pass.  On one
@@ -61,11 +69,13 @@ class PretrainStep:
         loss.backward()
         self.opt.step()
         # in-launch hand-offs (mvlt_swin_wmsa2_fwd) that timed out poison the loss with NaN AND raise here, one step late:
-        # the error counts travel to pinned host memory behind the step's kernels, no device sync (ops.wmsa2_check)
+        # the error counts travel to pinned host memory behind the step's kernels, no device sync (ops.wmsa2_check).
+        # By then the NaN gradients of that step have been applied -- reload the last checkpoint -- unless the optimizer runs with
+        # skip_nonfinite=True: it refused that step (opt.steps_skipped), the parameters are intact and training can continue.
         ops.wmsa2_check(sync=False)
         if self.reducer is not None:
             # data parallel: the error count of ALL ranks (it travelled with the label count): every rank raises, not only the one
-            # whose wait ran out.  By now the NaN gradients of that step have been applied -- reload the last checkpoint.
+            # whose wait ran out (and with skip_nonfinite every rank refused the step: they all saw the same reduced gradients)
             self.reducer.check_handoff()
         return loss
 
