@@ -805,6 +805,9 @@ def layernorm_bwd(dy, x, mean, rstd, gamma, dgamma, dbeta, *, dy_rowmap=None, y_
     defer=LnReduceQueue: the dgamma/dbeta partial rows are reduced later in one batched launch.
     dy_parts=True: dy is [parts, rows, C], 1 .. 4 partial tensors whose sum is the gradient (swin_wmsa2_bwd's dxn_parts)."""
     _need_cuda(dy, x)
+    if accumulate and defer is not None:
+        # the batched reduce writes dgamma / dbeta and has no accumulate form: the flag would be dropped silently
+        raise ValueError("layernorm_bwd: accumulate=True cannot be combined with defer (the batched parameter reduce overwrites)")
     Cn = gamma.numel()
     nrows = mean.numel()
     if dx is None:
