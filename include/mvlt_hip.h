@@ -64,12 +64,17 @@ size_t mvlt_sizeof(int struct_id);
  *   RESIDUAL  v += residual[m'*ldr + n]
  *   ACCUM     v += C[m',n]
  *   store C[m'*ldc + n]  (dtype, or f32 when OUT_F32)
+ * TAIL (with m_dev, a_kmajor = 0): rows m >= *m_dev do NOT leave; they run the epilogue above on a ZERO accumulator and are
+ *   stored like every other row (their rows of A are never read and may hold anything).  With ROWSCALE 0 and RESIDUAL that is
+ *   (0 + bias) * 0 + residual = the residual row, bit for bit; with no bias and no residual, zeros.  A tile entirely beyond
+ *   the count skips its K loop.  Honoured by the tile kernels (gemm_glds_kernel, gemm_kernel); k-slices refuse it
+ *   (MVLT_ERR_UNSUPPORTED: pass split_k = 1), the skinny, row-streaming and 8-wave routes hand the product to the tile kernels.
  * split_k > 1 computes K-slices into `workspace` (f32 slabs) and a second
  * kernel reduces them and applies the epilogue (deterministic, no atomics). */
 enum {
     MVLT_EPI_BIAS = 1, MVLT_EPI_GELU = 2, MVLT_EPI_SAVE_PRE = 4, MVLT_EPI_DROPOUT = 8,
     MVLT_EPI_ROWSCALE = 16, MVLT_EPI_RESIDUAL = 32, MVLT_EPI_ROWMAP = 64,
-    MVLT_EPI_MUL_GELU_GRAD = 128, MVLT_EPI_OUT_F32 = 256, MVLT_EPI_ACCUM = 512
+    MVLT_EPI_MUL_GELU_GRAD = 128, MVLT_EPI_OUT_F32 = 256, MVLT_EPI_ACCUM = 512, MVLT_EPI_TAIL = 1024
 };
 typedef struct MvltGemm {
     int dtype, M, N, K;
@@ -681,6 +686,18 @@ int mvlt_droppath_scale(float* scale, int B, float p, uint64_t seed, uint32_t ta
  * branches): scale [rows, B] f32, row r keeps sample b with probability 1 - probs[r] (device f32 [rows], each < 1) and
  * holds 1 / (1 - probs[r]) or 0; row r draws with tag + r */
 int mvlt_droppath_scales(float* scale, const float* probs, int rows, int B, uint64_t seed, uint32_t tag, void* stream);
+/* Row plans of the Swin blocks that run their Mlp branch only on the samples DropPath keeps, all blocks in one launch and with
+ * nothing read back: block i reads row row0 + i * row_step of `scale` ([*, B] f32; the tensor of mvlt_droppath_scales holds
+ * block i's Mlp branch in row 2 i + 1: row0 = 1, row_step = 2); a sample is kept iff its scale is not 0.  lt = DEVICE int32
+ * [nblk], the tokens per sample of block i (0, or rows_i = B * lt[i] > ld: the block takes no plan and its outputs are left
+ * alone).  For every other block:
+ *   perm[i * ld + j]  position j of the compact order -> logical row b * lt + t: the kept samples first, in sample order, the
+ *                     dropped ones behind them, tokens of a sample in order -- a full permutation of 0 .. rows_i - 1
+ *   inv[i * ld + r]   its inverse
+ *   count[i]          kept samples * lt[i] (the m_dev of the block's Mlp products)
+ * MVLT_ERR_ARG: a NULL pointer, nblk < 1, B < 1 or B > 4096, ld < 1, row0 < 0, row_step < 0. */
+int mvlt_droppath_plan(const float* scale, int row0, int row_step, const int32_t* lt, int nblk, int B, int64_t ld,
+                       int32_t* perm, int32_t* inv, int32_t* count, void* stream);
 
 /* ------------------------------------------------------------------ losses
  * F.cross_entropy(logits, labels, ignore_index=-100) (model.py:410,418):

@@ -16,7 +16,7 @@ ERRORS = {-1: "MVLT_ERR_ARG", -2: "MVLT_ERR_LAUNCH", -3: "MVLT_ERR_UNSUPPORTED"}
 
 EPI_BIAS, EPI_GELU, EPI_SAVE_PRE, EPI_DROPOUT = 1, 2, 4, 8
 EPI_ROWSCALE, EPI_RESIDUAL, EPI_ROWMAP, EPI_MUL_GELU_GRAD = 16, 32, 64, 128
-EPI_OUT_F32, EPI_ACCUM = 256, 512
+EPI_OUT_F32, EPI_ACCUM, EPI_TAIL = 256, 512, 1024
 ATTN_SWIN, ATTN_BIDIR, ATTN_SEQ2SEQ = 0, 1, 2
 # enum MvltAttnRoute (mvlt_attn_route)
 ATTN_ROUTES = ("UNSUPPORTED", "SWIN_FWD", "BERT_FWD_KT5", "BERT_FWD_KT9", "BERT_FWD_KT13", "SWIN_BWD_KS0", "SWIN_BWD_KS3",
@@ -256,6 +256,7 @@ SYMBOLS = {
     "mvlt_gumbel_noise": (i32, [u64, u32, i32, i32, vp, vp]),
     "mvlt_droppath_scale": (i32, [vp, i32, f32, u64, u32, vp]),
     "mvlt_droppath_scales": (i32, [vp, vp, i32, i32, u64, u32, vp]),
+    "mvlt_droppath_plan": (i32, [vp, i32, i32, vp, i32, i32, i64, vp, vp, vp, vp]),
     "mvlt_ce_fwd": (i32, [i32, vp, i64, i32, i32, vp, vp, vp, vp, vp]),
     "mvlt_ce_bwd": (i32, [i32, vp, i64, i32, i32, vp, vp, vp, f32, vp, vp, vp]),
     "mvlt_ce_fwd_ragged": (i32, [i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp]),

@@ -57,7 +57,9 @@ MVLT_DEV void slow_tail(const GemmDev& p, const int m_base, const int n_base, co
                     else for (int r = 0; r < 4; ++r) if (n + r < p.N) w[r] = acc[i][j][r];
                 }
             } else {
-                epilogue4<T>(p, m, n, acc[i][j]);
+                // MVLT_EPI_TAIL: rows at or beyond the count run the epilogue on a zero accumulator (gemm_dev.h tail_rows_zero)
+                const bool dead = (p.epi & MVLT_EPI_TAIL) && m >= p.m_valid;
+                epilogue4<T>(p, m, n, dead ? f32x4{0.f, 0.f, 0.f, 0.f} : acc[i][j]);
             }
         }
     }
@@ -72,7 +74,16 @@ MVLT_DEV void gemm_body(const GemmDev& p_in, const int bx, const int by, const i
     if (m0 >= p.M) return;                       // (uniform per workgroup; only with m_dev)
     const int wm = (threadIdx.x >> 6) >> 1, wn = (threadIdx.x >> 6) & 1;
     f32x4 acc[FM][FN];
-    gemm_mainloop<T, BM, BN, AK, BK_, PF2, DEEP>(p, bx, by, bz, sA, sB, acc);          // gemm_dev.h
+    if (!AK && m0 >= p.m_valid) {                // MVLT_EPI_TAIL only: a tile beyond the rows of A that exist skips its K loop
+#pragma unroll
+        for (int i = 0; i < FM; ++i)
+#pragma unroll
+            for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    } else {
+        GemmDev pl = p;                          // the loop reads the rows of A that exist (m_valid == M without MVLT_EPI_TAIL)
+        if (!AK) pl.M = p.m_valid;
+        gemm_mainloop<T, BM, BN, AK, BK_, PF2, DEEP>(pl, bx, by, bz, sA, sB, acc);          // gemm_dev.h
+    }
 
     if (!p.atomic_out && p.split_k <= 1 && p.epi_vec && (p.N & 3) == 0) {
         if constexpr (WIDE && sizeof(T) == 2 && FN % 2 == 0) tile_epilogue_wide<T, FM, FN>(p, m0 + wm * (BM / 2), n0 + wn * (BN / 2), acc);
@@ -120,14 +131,15 @@ __global__ __launch_bounds__(256, 2) void gemm_glds_kernel(const GemmDev p_in) {
     const int gy = min((int)gridDim.y, (p.M + BM - 1) / BM);
     const int orig = blockIdx.y * gx + blockIdx.x;
     if (orig >= gx * gy) return;
-    const int t = xcd_remap(orig, gx * gy);
     int by, bx;
-    tile_coords(t, gx, gy, p.xcs, by, bx);
+    tail_tile_order(orig, gx, gy, BM, p, by, bx);
     const int bz = blockIdx.z;
     const int m0 = by * BM, n0 = bx * BN;
     const int ks = bz * p.k_per_split;
     const int ke = min(p.K, ks + p.k_per_split);
-    const int nkt = (ke - ks) / BKE;
+    // MVLT_EPI_TAIL (m_valid < M): a tile beyond the rows of A that exist skips its K loop, one that straddles the count reads
+    // clamped copies of the last valid row; the epilogue zeroes those accumulators (gemm_dev.h tail_rows_zero)
+    const int nkt = m0 < p.m_valid ? (ke - ks) / BKE : 0;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int wm = wave >> 1, wn = wave & 1;
@@ -140,7 +152,7 @@ __global__ __launch_bounds__(256, 2) void gemm_glds_kernel(const GemmDev p_in) {
     const T* srcB[BN / 32];
 #pragma unroll
     for (int j = 0; j < BM / 32; ++j) {
-        const int row = min(m0 + (wave * (BM / 32) + j) * 8 + rin, p.M - 1);
+        const int row = min(m0 + (wave * (BM / 32) + j) * 8 + rin, max(p.m_valid, 1) - 1);
         srcA[j] = A + (long)row * p.lda + ks + chs * 8;
     }
 #pragma unroll
@@ -217,9 +229,8 @@ __global__ __launch_bounds__(256, 3) void gemm_kernel(const GemmDev p) {
     const int gy = AK ? (int)gridDim.y : min((int)gridDim.y, (q.M + BM - 1) / BM);
     const int orig = blockIdx.y * gx + blockIdx.x;
     if (orig < gx * gy) {
-        const int t = xcd_remap(orig, gx * gy);
         int by, bx;
-        tile_coords(t, gx, gy, q.xcs, by, bx);
+        tail_tile_order(orig, gx, gy, BM, q, by, bx);
         gemm_body<T, BM, BN, AK, BK_, PF2, 0, WIDE>(q, bx, by, blockIdx.z, sA, sB);
     }
     asm volatile("" :: "v"(pfv));
@@ -627,6 +638,7 @@ static int fill_dev(const MvltGemm* p, const Plan& pl, GemmDev& d) {
     d.wide = sizeof(T) == 2 && ev && !(epi & (MVLT_EPI_OUT_F32 | MVLT_EPI_ACCUM)) && p->N % 8 == 0 && p->ldc % 8 == 0 && pl.split <= 1 &&
              pl.bn != 96 && (!(epi & MVLT_EPI_RESIDUAL) || p->ldr % 8 == 0) && (!(epi & MVLT_EPI_BIAS) || aligned16(p->bias));
     d.xcs = gemm_pick_xcs(p->M, p->N, pl.bm, pl.bn);          // tile order (tile_coords)
+    d.m_valid = p->M;                                         // (the kernels take it from effective())
     return MVLT_OK;
 }
 
@@ -634,6 +646,10 @@ static int fill_dev(const MvltGemm* p, const Plan& pl, GemmDev& d) {
 template <typename T>
 static int gemm_dispatch(const MvltGemm* p, hipStream_t s, int* route = nullptr) {
     Plan pl = choose_plan(p);
+    // MVLT_EPI_TAIL lives in the tile epilogues of this file (gemm_dev.h tail_rows_zero, slow_tail).  k-slices cannot honour it
+    // (the slabs of the rows beyond the count are never written): refused, the caller asks for split_k = 1.  The skinny kernels,
+    // the row-streaming kernel and the 8-wave engine refuse it themselves (their *_try answer 0) and the tile kernels run.
+    if ((p->epilogue & MVLT_EPI_TAIL) && pl.split > 1) return MVLT_ERR_UNSUPPORTED;
     const bool skinny = is_skinny<T>(p);
     if (skinny) pl.split = 1;          // (no workspace was requested for it)
     GemmDev d;
@@ -765,6 +781,7 @@ static int check_gemm_args(const MvltGemm* p) {
     if (e & MVLT_EPI_MUL_GELU_GRAD) MVLT_CHECK(p->aux, MVLT_ERR_ARG);
     if (e & MVLT_EPI_DROPOUT) MVLT_CHECK(p->dropout_p >= 0.f && p->dropout_p < 1.f, MVLT_ERR_ARG);
     if (p->a_colsum) MVLT_CHECK(p->a_kmajor, MVLT_ERR_ARG);
+    if (e & MVLT_EPI_TAIL) MVLT_CHECK(p->m_dev && !p->a_kmajor, MVLT_ERR_ARG);
     return MVLT_OK;
 }
 

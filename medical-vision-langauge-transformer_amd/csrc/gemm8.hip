@@ -831,6 +831,7 @@ extern "C" __attribute__((visibility("hidden"))) int mvlt_gemm8_try(const void* 
     gp.n = n;
     for (int i = 0; i < n; ++i) {
         if (!d[i].a_vec || !d[i].b_vec || d[i].split_k > 1 || !d[i].epi_vec || d[i].epi != d[0].epi || d[i].a_colsum) return 0;
+        if (d[i].epi & MVLT_EPI_TAIL) return 0;          // this engine's epilogues drop the rows beyond *m_dev
         if (!(a_kmajor && b_kmajor) && (d[i].K % 64 != 0)) return 0;
         if (d[i].K < 64 || d[i].N % 4 != 0 || d[i].N < 4) return 0;
         if (a_kmajor && (d[i].M % 8 != 0)) return 0;

@@ -22,18 +22,39 @@ struct GemmDev {
     int a_kmajor;                        // A is k-major (weight gradients): m_dev then limits the reduction, not the rows
     int wide;                            // bf16 rows out with 16-byte aligned 8-column chunks (and operands): kernels built with WIDE
     int xcs;                             // column groups of the tile order (tile_coords below); 0 / 1 = plain row-major list
+    int m_valid;                         // rows of a k-contiguous A that exist (set by effective(): M, or *m_dev under MVLT_EPI_TAIL)
 };
 
 // Ragged batches planned on the GPU: the launch is sized for the upper bound, the kernel reads the real count.
 // k-contiguous A: M shrinks (tiles beyond it leave at once); k-major A (weight gradients): the reduction shrinks.
+// MVLT_EPI_TAIL (k-contiguous A only): M stays -- every row is stored -- and m_valid takes the count: rows at or beyond it are
+// never read from A and meet the epilogue with a zero accumulator (tail_rows_zero below).
 template <bool AK>
 MVLT_DEV GemmDev effective(const GemmDev& p) {
     GemmDev q = p;
     if (p.m_dev) {
         const int r = __builtin_amdgcn_readfirstlane(*p.m_dev);
-        if (AK) q.K = min(q.K, max(r, 0)); else q.M = min(q.M, max(r, 0));
+        if (AK) q.K = min(q.K, max(r, 0));
+        else if (p.epi & MVLT_EPI_TAIL) { q.m_valid = min(q.M, max(r, 0)); return q; }
+        else q.M = min(q.M, max(r, 0));
     }
+    q.m_valid = q.M;
     return q;
+}
+
+// MVLT_EPI_TAIL: the accumulators of the wave-tile rows at or beyond m_valid become zeros (a tile that straddles the count has
+// multiplied clamped copies of the last valid row there; a tile beyond it has skipped its K loop).  Uniform branch, off the
+// dense products' path.
+template <int FM, int FN>
+MVLT_DEV void tail_rows_zero(const GemmDev& p, const int m_base, f32x4 (&acc)[FM][FN]) {
+    if (!(p.epi & MVLT_EPI_TAIL) || m_base + FM * 16 <= p.m_valid) return;
+    const int mr = threadIdx.x & 15;
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+        if (m_base + i * 16 + mr >= p.m_valid) {
+#pragma unroll
+            for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
 }
 
 template <typename T>
@@ -129,6 +150,7 @@ MVLT_DEV f32x4 raw4_to_f(const f32x4& v) { return v; }
 template <typename T, int FM, int FN>
 MVLT_DEV void tile_epilogue(const GemmDev& p, const int m_base, const int n_base, f32x4 (&acc)[FM][FN]) {
     using R4 = typename Raw4<T>::type;
+    tail_rows_zero<FM, FN>(p, m_base, acc);
     const int lane = threadIdx.x & 63;
     const int mr = lane & 15, nq = 4 * (lane >> 4);
     const int epi = p.epi;
@@ -262,6 +284,7 @@ template <typename T, int FM, int FN>
 MVLT_DEV void tile_epilogue_wide(const GemmDev& p, const int m_base, const int n_base, f32x4 (&acc)[FM][FN]) {
     static_assert(sizeof(T) == 2 && FN % 2 == 0, "bf16 rows, fragment pairs");
     constexpr int NP = FN / 2;
+    tail_rows_zero<FM, FN>(p, m_base, acc);
     const int lane = threadIdx.x & 63;
     const int mr = lane & 15, g = lane >> 4;
     const int cofs = 16 * (g & 1) + 8 * (g >> 1);          // this lane's chunk inside the 32 columns of a fragment pair
@@ -379,6 +402,18 @@ MVLT_DEV void tile_coords(int t, int gx, int gy, int xcs, int& by, int& bx) {
     const int g = min(t / per, ng - 1), r = t - g * per;
     const int w = g == ng - 1 ? gx - g * hx : hx;
     by = r / w; bx = g * hx + (r - by * w);
+}
+
+// Workgroup `orig` of a gx x gy tile grid -> its tile.  The XCD remap deals CONTIGUOUS chunks of the list to the XCDs, so under
+// MVLT_EPI_TAIL the row tiles that have a K loop (those below m_valid) form a list of their own, remapped by itself: one list
+// would hand the tiles without a K loop, which sit at its end, to one or two XCDs and leave the others their full share (the
+// 64 x 64 Mlp products of a Swin block ran no faster for 17 % fewer live tiles).  The tiles beyond the count follow in plain
+// order.  Without the bit (m_valid == M) the live list is the whole grid: the order every other product has always had.
+MVLT_DEV void tail_tile_order(int orig, int gx, int gy, int bm, const GemmDev& p, int& by, int& bx) {
+    const int gyl = p.a_kmajor ? gy : min(gy, (p.m_valid + bm - 1) / bm), nl = gx * gyl;
+    if (orig < nl) { tile_coords(xcd_remap(orig, nl), gx, gyl, p.xcs, by, bx); return; }
+    const int t = orig - nl;
+    by = gyl + t / gx; bx = t - (by - gyl) * gx;
 }
 
 // MvltGemm.prefetch: every thread of the launch reads one dword of a few 128-byte lines of a byte range that a LATER kernel

@@ -94,12 +94,13 @@ struct KernelTimer {
     std::vector<hipEvent_t> ev;
     std::vector<double> mn2;          // per sample: 2 * sum_i (the two dimensions that are not ragged)
     std::vector<double> bfix, brow;   // per sample: ALGORITHMIC bytes = bfix + rows * brow (operands read once, outputs written once)
+    std::vector<double> ffix;         // per sample: FLOPs of the products of a group whose reduction is NOT the ragged one
     std::vector<int> bound;           // per sample: host-known upper bound of the ragged dimension
     int* dev_rows = nullptr;          // pinned host: ragged dimension read from the device (-1: none, use the bound)
     size_t used = 0, cap = 0;
     bool sample() { return on && (count++ % every) == 0 && used < cap; }
-    void begin(void* stream, double mn2_, int bound_, const int32_t* rows_dev, double bfix_ = 0.0, double brow_ = 0.0) {
-        mn2.push_back(mn2_); bound.push_back(bound_); bfix.push_back(bfix_); brow.push_back(brow_);
+    void begin(void* stream, double mn2_, int bound_, const int32_t* rows_dev, double bfix_ = 0.0, double brow_ = 0.0, double ffix_ = 0.0) {
+        mn2.push_back(mn2_); bound.push_back(bound_); bfix.push_back(bfix_); brow.push_back(brow_); ffix.push_back(ffix_);
         dev_rows[used] = -1;
         if (rows_dev) (void)hipMemcpyAsync(&dev_rows[used], rows_dev, sizeof(int), hipMemcpyDeviceToHost, static_cast<hipStream_t>(stream));
         (void)hipEventRecord(ev[3 * used], static_cast<hipStream_t>(stream));
@@ -115,7 +116,7 @@ struct KernelTimer {
     void reset(int every_, size_t cap_) {
         for (auto e : ev) (void)hipEventDestroy(e);
         if (dev_rows) (void)hipHostFree(dev_rows);
-        ev.clear(); mn2.clear(); bound.clear(); bfix.clear(); brow.clear(); dev_rows = nullptr; used = 0; count = 0;
+        ev.clear(); mn2.clear(); bound.clear(); bfix.clear(); brow.clear(); ffix.clear(); dev_rows = nullptr; used = 0; count = 0;
         on = cap_ > 0; every = std::max(1, every_); cap = cap_;
         if (!on) return;
         ev.resize(3 * cap);
@@ -130,7 +131,7 @@ struct KernelTimer {
             if (hipEventElapsedTime(&ms, ev[3 * i], ev[3 * i + 1]) != hipSuccess) continue;
             if (subtract_record_cost && hipEventElapsedTime(&over, ev[3 * i + 1], ev[3 * i + 2]) == hipSuccess && over < ms) ms -= over;
             const int rows = dev_rows[i] >= 0 ? std::min(dev_rows[i], bound[i]) : bound[i];
-            out.emplace_back(mn2[i] * rows, (double)ms, bfix[i] + brow[i] * rows);
+            out.emplace_back(mn2[i] * rows + ffix[i], (double)ms, bfix[i] + brow[i] * rows);
         }
         on = false;
         return out;
@@ -149,6 +150,7 @@ struct Epi {
     const int32_t* rowmap = nullptr; const void* aux = nullptr;
     bool out_f32 = false, accumulate = false; float* a_colsum = nullptr;
     const int32_t* m_dev = nullptr;          // valid storage rows of A on the device (ragged batches)
+    bool tail = false;                       // MVLT_EPI_TAIL: rows at or beyond *m_dev run the epilogue on a zero accumulator
 };
 
 void fill_gemm(MvltGemm& p, int dtype, int M, int N, int K, const void* A, int64_t lda, bool ak, const void* B, int64_t ldb,
@@ -166,6 +168,7 @@ void fill_gemm(MvltGemm& p, int dtype, int M, int N, int K, const void* A, int64
     if (e.aux) { epi |= MVLT_EPI_MUL_GELU_GRAD; p.aux = e.aux; }
     if (e.out_f32) epi |= MVLT_EPI_OUT_F32;
     if (e.accumulate) epi |= MVLT_EPI_ACCUM;
+    if (e.tail) { epi |= MVLT_EPI_TAIL; p.split_k = 1; }          // (k-slices refuse the bit)
     p.epilogue = epi;
     p.a_colsum = e.a_colsum;
     p.m_dev = e.m_dev;
@@ -201,8 +204,10 @@ inline void dgrad(const Tensor& dy, int64_t W, int K, Tensor& out, const Epi& e,
          e, stream, g_ws_main, dy);
 }
 
-struct WItem { const Tensor* dy; const Tensor* x; int64_t dw; int64_t db; };
+struct WItem { const Tensor* dy; const Tensor* x; int64_t dw; int64_t db; const int32_t* k_dev = nullptr; };
 // weight gradients of one layer: dW_i = dY_i^T X_i, db_i = colsum(dY_i)  (ops.wgrad_group)
+// k_dev: device row count that ends every item's reduction (packed BERT rows); an item's own k_dev goes before it (the two Mlp
+// products of a Swin block whose dropped samples sit behind the count, beside attention products over all rows)
 void wgrad_group(const std::vector<WItem>& items, void* stream, Scratch& ws, const int32_t* k_dev = nullptr) {
     const int n = (int)items.size();
     bool all128 = true, all96 = true;
@@ -218,28 +223,31 @@ void wgrad_group(const std::vector<WItem>& items, void* stream, Scratch& ws, con
     const bool slices_ok = dtype == MVLT_BF16;
     if (!(n > 1 && n <= 8 && bn && (tiles >= 200 || (slices_ok && items[0].dy->size(0) >= long_k)))) {
         for (auto& it : items) {
-            Epi e; e.out_f32 = true; e.a_colsum = P<float>(it.db); e.m_dev = k_dev;
+            Epi e; e.out_f32 = true; e.a_colsum = P<float>(it.db); e.m_dev = it.k_dev ? it.k_dev : k_dev;
             gemm(dtype, (int)it.dy->size(1), (int)it.x->size(1), (int)it.dy->size(0), dp(*it.dy), it.dy->size(1), true,
                  dp(*it.x), it.x->size(1), true, P(it.dw), it.x->size(1), e, stream, ws, *it.dy);
         }
         return;
     }
     MvltGemm arr[8];
-    double mn2 = 0, bfix = 0, brow = 0;        // algorithmic bytes: per reduction row both operand rows (bf16), once the f32 dW + db
+    double mn2 = 0, bfix = 0, brow = 0, ffix = 0;        // algorithmic bytes: per reduction row both operand rows (bf16), once the f32 dW + db
+    const int32_t* timed_dev = k_dev;          // the ONE device count a sampled launch reads back: the first one an item carries
+    for (int i = 0; i < n && !timed_dev; ++i) timed_dev = items[i].k_dev;
     for (int i = 0; i < n; ++i) {
         const auto& it = items[i];
-        Epi e; e.out_f32 = true; e.a_colsum = P<float>(it.db); e.m_dev = k_dev;
+        Epi e; e.out_f32 = true; e.a_colsum = P<float>(it.db); e.m_dev = it.k_dev ? it.k_dev : k_dev;
         fill_gemm(arr[i], dtype, (int)it.dy->size(1), (int)it.x->size(1), (int)it.dy->size(0), dp(*it.dy), it.dy->size(1), true,
                   dp(*it.x), it.x->size(1), true, P(it.dw), it.x->size(1), e);
         arr[i].split_k = 1;
-        mn2 += 2.0 * arr[i].M * arr[i].N;          // the reduction length (activation rows) is the ragged dimension here
-        brow += (double)(arr[i].M + arr[i].N) * it.dy->element_size();
+        const double f2 = 2.0 * arr[i].M * arr[i].N, br = (double)(arr[i].M + arr[i].N) * it.dy->element_size();
+        if (e.m_dev == timed_dev) { mn2 += f2; brow += br; }          // the reduction length (activation rows) is the ragged dimension here
+        else { ffix += f2 * arr[i].K; bfix += br * arr[i].K; }        // (an item over all rows beside ragged ones)
         bfix += ((double)arr[i].M * arr[i].N + arr[i].M) * 4.0;
     }
     const size_t need = mvlt_gemm_group_workspace_bytes(arr, n);          // k-slice slabs of the 8-wave engine
     if (need) { arr[0].workspace = workspace(ws, need, *items[0].dy); arr[0].workspace_bytes = (size_t)ws.buf.numel(); }
     const bool timed = g_timer.sample();
-    if (timed) g_timer.begin(stream, mn2, arr[0].K, k_dev, bfix, brow);
+    if (timed) g_timer.begin(stream, mn2, arr[0].K, timed_dev, bfix, brow, ffix);
     ck(mvlt_gemm_group(arr, n, stream), "mvlt_gemm_group");
     if (timed) g_timer.end(stream);
 }
@@ -398,8 +406,12 @@ Tensor bert_layer_bwd(const Tensor& dx, const std::vector<Tensor>& sv, const Ptr
 // w: compute-dtype weights [wqkv, wproj, wfc1, wfc2]; f: f32 [n1g, n1b, bqkv, bproj, table, n2g, n2b, bfc1, bfc2];
 // g: f32 gradients [dn1g, dn1b, dwqkv, dbqkv, dwproj, dbproj, dtable, dn2g, dn2b, dwfc1, dbfc1, dwfc2, dbfc2]
 // geo: [B, H(res), C, nH, shift, fused (0 | 1 wmsa.hip | 2 wmsa2.hip), sync workspace of wmsa2]; maps: [w2n, n2w] int32 device pointers; s1/s2: DropPath scales f32 [B] or 0
+// plan: {} or {perm, inv, count} of mvlt_droppath_plan for s2 (int32 [rows], [rows], [1]): the Mlp branch then runs only on the
+// rows of the samples DropPath keeps.  norm2 writes xn2 in the plan's compact order (kept samples first), fc1 / fc2 stop at
+// `count` rows, fc2 scatters back through `perm` and lets the rows of the dropped samples through its epilogue on a zero
+// accumulator (MVLT_EPI_TAIL: (0 + bias) * 0 + x1 = x1).  h / act rows at or beyond the count are never written.
 std::vector<Tensor> swin_block_fwd(const Tensor& x, const Ptrs& w, const Ptrs& f, const Ptrs& geo, const Ptrs& maps, double scale,
-                                   double eps, int64_t s1, int64_t s2, bool save, int64_t stream_) {
+                                   double eps, int64_t s1, int64_t s2, bool save, int64_t stream_, const std::vector<Tensor>& plan) {
     check_device(x);
     void* st = P(stream_);
     const int B = (int)geo[0], res = (int)geo[1], C = (int)geo[2], nH = (int)geo[3], shift = (int)geo[4];
@@ -447,13 +459,23 @@ std::vector<Tensor> swin_block_fwd(const Tensor& x, const Ptrs& w, const Ptrs& f
     Tensor xn2 = empty2(rows, C, x), stat2;
     float *m2 = nullptr, *r2 = nullptr;
     if (save) { stat2 = emptyf({2, rows}, x); m2 = fp(stat2); r2 = m2 + rows; }
-    ln_fwd(x1, (int)rows, C, f[5], f[6], (float)eps, xn2, m2, r2, nullptr, st);
+    const bool compact = !plan.empty();
+    const int32_t *perm = nullptr, *inv = nullptr, *count = nullptr;
+    if (compact) {
+        TORCH_CHECK(plan.size() == 3 && s2 && save && dtype == MVLT_BF16, "swin_block_fwd: a row plan needs s2, save and bf16");
+        for (const Tensor& t : plan) TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kInt && t.is_contiguous(), "swin_block_fwd: plan tensors are int32");
+        TORCH_CHECK(plan[0].numel() == rows && plan[1].numel() == rows && plan[2].numel() == 1, "swin_block_fwd: plan sizes");
+        perm = plan[0].data_ptr<int32_t>(); inv = plan[1].data_ptr<int32_t>(); count = plan[2].data_ptr<int32_t>();
+    }
+    ln_fwd(x1, (int)rows, C, f[5], f[6], (float)eps, xn2, m2, r2, inv, st);          // (all rows: xn2 is finite everywhere)
     Tensor h = empty2(rows, 4 * C, x), act = empty2(rows, 4 * C, x);
-    { Epi e; e.bias = P<float>(f[7]); e.gelu = true; e.pre = dp(h); e.pf = P(w[3]); e.pf_bytes = (int64_t)4 * C * C * esz; linear(xn2, w[2], 4 * C, act, e, st); }
+    { Epi e; e.m_dev = count; e.bias = P<float>(f[7]); e.gelu = true; e.pre = dp(h); e.pf = P(w[3]); e.pf_bytes = (int64_t)4 * C * C * esz; linear(xn2, w[2], 4 * C, act, e, st); }
     Tensor x2 = empty2(rows, C, x);
     { Epi e; e.bias = P<float>(f[8]); e.residual = dp(x1); e.ldr = C; if (s2) { e.rowscale = P<float>(s2); e.rps = Lt; }
+      if (compact) { e.m_dev = count; e.rowmap = perm; e.tail = true; }
       if (nb) { e.pf = P(w[4]); e.pf_bytes = w[5]; } linear(act, w[3], C, x2, e, st); }
     if (!save) return {x2};
+    if (compact) return {x2, x, stat1, xn1w, qkv, ao, lse, x1, stat2, xn2, h, act, plan[0], plan[1], plan[2]};
     return {x2, x, stat1, xn1w, qkv, ao, lse, x1, stat2, xn2, h, act};
 }
 
@@ -461,9 +483,14 @@ std::vector<Tensor> swin_block_fwd(const Tensor& x, const Ptrs& w, const Ptrs& f
 // s2_next: DropPath scales of the MLP branch of the block that consumes dx0 (the previous block of the stage), or 0: the
 // last LayerNorm backward then also writes dx0 * s2_next, which that block takes as `dy2_pre` instead of launching a
 // row-scale pass of its own.  Returns {dx0} or {dx0, dx0 * s2_next}.
+// A forward with a row plan appended sv[11 .. 13] = perm, inv, count: the Mlp half then runs in the plan's compact order.  dy2 is
+// dx2 * s2 gathered through perm (zeros behind the count), both dgrads and both Mlp weight gradients stop at `count` rows, the
+// fc1 dgrad fills the rows behind it with zeros (MVLT_EPI_TAIL) and norm2's backward reads dxn2 through inv.  dy2_pre, when
+// given, is already in that order: inv_next (int32 device pointer or 0) is the consuming block's `inv`, through which the last
+// LayerNorm backward scatters dx0 * s2_next.
 std::vector<Tensor> swin_block_bwd(const Tensor& dx2, const std::vector<Tensor>& sv, const Ptrs& w, const Ptrs& f, const Ptrs& g, const Ptrs& geo,
                                    const Ptrs& maps, double scale, int64_t s1, int64_t s2, int64_t s2_next, const c10::optional<Tensor>& dy2_pre,
-                                   int64_t stream_, int64_t side_) {
+                                   int64_t stream_, int64_t side_, int64_t inv_next) {
     check_device(dx2);
     Streams ss{P(stream_), P(side_)};
     void* st = ss.main;
@@ -475,23 +502,29 @@ std::vector<Tensor> swin_block_bwd(const Tensor& dx2, const std::vector<Tensor>&
     const int dtype = dtype_of(x);
     const int32_t* w2n = P<const int32_t>(maps[0]); const int32_t* n2w = P<const int32_t>(maps[1]);
     (void)w2n;
+    const bool compact = sv.size() >= 14;
+    const int32_t *perm = nullptr, *inv = nullptr, *count = nullptr;
+    if (compact) {
+        TORCH_CHECK(s2 && sv[11].numel() == rows && sv[12].numel() == rows && sv[13].numel() == 1, "swin_block_bwd: row plan");
+        perm = sv[11].data_ptr<int32_t>(); inv = sv[12].data_ptr<int32_t>(); count = sv[13].data_ptr<int32_t>();
+    }
     Tensor dy2 = dx2;
     if (s2 && dy2_pre.has_value()) {
         dy2 = *dy2_pre;
         TORCH_CHECK(dy2.sizes() == dx2.sizes() && dy2.scalar_type() == dx2.scalar_type() && dy2.is_contiguous(), "dy2_pre");
     } else if (s2) {
         dy2 = empty2(rows, C, x);
-        ck(mvlt_rows_transform(dtype, dp(dx2), dp(dy2), (int)rows, C, nullptr, P<float>(s2), Lt, 0.f, 0, 0, st), "mvlt_rows_transform");
+        ck(mvlt_rows_transform(dtype, dp(dx2), dp(dy2), (int)rows, C, perm, P<float>(s2), Lt, 0.f, 0, 0, st), "mvlt_rows_transform");
     }
     Tensor dh = empty2(rows, 4 * C, x);
     const int64_t esz = x.element_size();
     const bool nb = w.size() >= 8;
-    { Epi e; e.aux = dp(h); e.pf = P(w[2]); e.pf_bytes = (int64_t)4 * C * C * esz; dgrad(dy2, w[3], 4 * C, dh, e, st); }
+    { Epi e; e.m_dev = count; e.aux = dp(h); e.pf = P(w[2]); e.pf_bytes = (int64_t)4 * C * C * esz; dgrad(dy2, w[3], 4 * C, dh, e, st); }
     Tensor dxn2 = empty2(rows, C, x);
-    { Epi e; e.pf = P(w[1]); e.pf_bytes = (int64_t)C * C * esz; dgrad(dh, w[2], C, dxn2, e, st); }
+    { Epi e; e.m_dev = count; e.tail = compact; e.pf = P(w[1]); e.pf_bytes = (int64_t)C * C * esz; dgrad(dh, w[2], C, dxn2, e, st); }
     Tensor dx1 = empty2(rows, C, x), dyw = empty2(rows, C, x);
     { LnBranch br; br.dz = dp(dyw); br.rowmap = n2w; if (s1) { br.rowscale = P<float>(s1); br.rps = Lt; }
-      ln_bwd(dxn2, nullptr, x1, fp(stat2), fp(stat2) + rows, (int)rows, C, f[5], g[7], g[8], dp(dx2), dx1, br, st); }
+      ln_bwd(dxn2, inv, x1, fp(stat2), fp(stat2) + rows, (int)rows, C, f[5], g[7], g[8], dp(dx2), dx1, br, st); }
     // the output projection's dgrad rides inside the attention backward where the kernel takes it (MvltAttn.dout_weight: bf16,
     // 3 / 6 / 12 heads of 32; MVLT_SWIN_BWD_PROJ=0: the separate product)
     static const bool proj_in_attn = [] { const char* e = getenv("MVLT_SWIN_BWD_PROJ"); return !e || e[0] != '0'; }();
@@ -530,7 +563,9 @@ std::vector<Tensor> swin_block_bwd(const Tensor& dx2, const std::vector<Tensor>&
       if (fuse_proj) { p.dout_weight = P(w[1]); p.prefetch = P(w[0]); p.prefetch_bytes = (int64_t)3 * C * C * esz; }
       attn_bwd_fork(p, ss); }
     for (const Tensor* t : std::initializer_list<const Tensor*>{&dy2, &act, &dh, &xn2, &dyw, &ao, &dqkv, &xn1w}) g_side_keepalive.push_back(*t);
-    wgrad_group({{&dy2, &act, g[11], g[12]}, {&dh, &xn2, g[9], g[10]}, {&dyw, &ao, g[4], g[5]}, {&dqkv, &xn1w, g[2], g[3]}},
+    if (compact) g_side_keepalive.push_back(sv[13]);
+    // (compact: dy2 / act / dh / xn2 share the plan's row order, so the two Mlp products are the dense ones minus exact zeros)
+    wgrad_group({{&dy2, &act, g[11], g[12], count}, {&dh, &xn2, g[9], g[10], count}, {&dyw, &ao, g[4], g[5]}, {&dqkv, &xn1w, g[2], g[3]}},
                 ss.side, g_ws_side);
     if (!nparts) {
         dxn1w = empty2(rows, C, x);
@@ -538,7 +573,7 @@ std::vector<Tensor> swin_block_bwd(const Tensor& dx2, const std::vector<Tensor>&
     }
     Tensor dx0 = empty2(rows, C, x), dy2n;
     { LnBranch br;
-      if (s2_next) { dy2n = empty2(rows, C, x); br.dz = dp(dy2n); br.rowscale = P<float>(s2_next); br.rps = Lt; }
+      if (s2_next) { dy2n = empty2(rows, C, x); br.dz = dp(dy2n); br.rowscale = P<float>(s2_next); br.rps = Lt; br.rowmap = P<const int32_t>(inv_next); }
       ln_bwd(dxn1w, n2w, x, fp(stat1), fp(stat1) + rows, (int)rows, C, f[0], g[0], g[1], dp(dx1), dx0, br, st, nullptr, nparts); }
     if (s2_next) return {dx0, dy2n};
     return {dx0};

@@ -293,6 +293,35 @@ __global__ void droppath_rows_kernel(float* scale, const float* probs, int rows,
     scale[i] = (p <= 0.f || rng_keep(seed, tag + (uint32_t)r, (uint32_t)b, thresh)) ? 1.0f / (1.0f - p) : 0.f;
 }
 
+// mvlt_droppath_plan: one workgroup per block.  Thread 0 places the B samples (kept ones first, both groups in sample order: B is a
+// batch size, the scan is a few dozen steps); all threads then write the two row maps.  A block whose rows do not fit `ld` is
+// left alone (lt comes from the device: the bound cannot be checked on the host).
+constexpr int DROPPATH_PLAN_MAX_B = 4096;
+__global__ __launch_bounds__(256) void droppath_plan_kernel(const float* scale, int row0, int row_step, const int* lt, int B, long ld,
+                                                            int* perm, int* inv, int* count) {
+    __shared__ int pos[DROPPATH_PLAN_MAX_B];
+    const int blk = blockIdx.x;
+    const int L = lt[blk];
+    if (L <= 0 || (long)B * L > ld) return;
+    const float* s = scale + ((long)row0 + (long)blk * row_step) * B;
+    if (threadIdx.x == 0) {
+        int nk = 0;
+        for (int b = 0; b < B; ++b) if (s[b] != 0.f) pos[b] = nk++;
+        int nd = nk;
+        for (int b = 0; b < B; ++b) if (!(s[b] != 0.f)) pos[b] = nd++;
+        count[blk] = nk * L;
+    }
+    __syncthreads();
+    int* pm = perm + (long)blk * ld;
+    int* iv = inv + (long)blk * ld;
+    const int rows = B * L;
+    for (int r = threadIdx.x; r < rows; r += 256) {
+        const int b = r / L, t = r - b * L;
+        const int j = pos[b] * L + t;
+        pm[j] = r; iv[r] = j;
+    }
+}
+
 // ------------------------------------------------------------------ column sums
 constexpr int COLSUM_ROWS = 128;   // partial rows
 template <typename T>
@@ -1108,6 +1137,13 @@ extern "C" int mvlt_droppath_scale(float* scale, int B, float p, uint64_t seed, 
 extern "C" int mvlt_droppath_scales(float* scale, const float* probs, int rows, int B, uint64_t seed, uint32_t tag, void* stream) {
     MVLT_CHECK(scale && probs && rows > 0 && B > 0 && (long)rows * B < (1L << 30), MVLT_ERR_ARG);
     hipLaunchKernelGGL(droppath_rows_kernel, dim3(ceil_div(rows * B, 256)), dim3(256), 0, STREAM(stream), scale, probs, rows, B, seed, tag);
+    MVLT_LAUNCH_CHECK();
+    return MVLT_OK;
+}
+extern "C" int mvlt_droppath_plan(const float* scale, int row0, int row_step, const int32_t* lt, int nblk, int B, int64_t ld,
+                                  int32_t* perm, int32_t* inv, int32_t* count, void* stream) {
+    MVLT_CHECK(scale && lt && perm && inv && count && nblk > 0 && B > 0 && B <= DROPPATH_PLAN_MAX_B && ld > 0 && row0 >= 0 && row_step >= 0, MVLT_ERR_ARG);
+    hipLaunchKernelGGL(droppath_plan_kernel, dim3(nblk), dim3(256), 0, STREAM(stream), scale, row0, row_step, lt, B, (long)ld, perm, inv, count);
     MVLT_LAUNCH_CHECK();
     return MVLT_OK;
 }

@@ -330,7 +330,7 @@ int rs_launch(const RsArgs& a, hipStream_t s, int bit, int* route) {
 extern "C" __attribute__((visibility("hidden"))) int mvlt_rowstream_try(const void* dev_block, int b_kmajor, void* stream, int* route) {
     const GemmDev& d = *reinterpret_cast<const GemmDev*>(dev_block);
     constexpr int ALLOWED = MVLT_EPI_BIAS | MVLT_EPI_GELU | MVLT_EPI_SAVE_PRE | MVLT_EPI_ROWSCALE | MVLT_EPI_MUL_GELU_GRAD | MVLT_EPI_RESIDUAL;
-    if ((d.epi & ~ALLOWED) || d.m_dev || d.split_k > 1 || d.a_colsum || d.a_kmajor) return 0;
+    if ((d.epi & ~ALLOWED) || d.m_dev || d.split_k > 1 || d.a_colsum || d.a_kmajor) return 0;          // (MVLT_EPI_TAIL: not in ALLOWED)
     if (d.lda != d.K || d.ldc != d.N || !d.a_vec || !d.b_vec || !d.epi_vec || d.M < 16384) return 0;
     if ((d.epi & MVLT_EPI_BIAS) && !aligned16(d.bias)) return 0;
     if ((d.epi & MVLT_EPI_MUL_GELU_GRAD) && (d.epi & MVLT_EPI_RESIDUAL)) return 0;

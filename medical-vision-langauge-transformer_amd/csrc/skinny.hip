@@ -1035,6 +1035,7 @@ extern "C" __attribute__((visibility("hidden"))) int mvlt_skinny_try(const MvltG
     const int rc = by_dtype(p->dtype, [&](auto t) -> int {
         using T = decltype(t);
         if (!skinny_ok<T>(p)) return 0;
+        if (p->epilogue & MVLT_EPI_TAIL) return 0;          // rows beyond *m_dev leave this kernel: the tile kernels honour the bit
         if (route) { *route = gemm_route_code(MVLT_GEMM_ROUTE_SKINNY, 1); return 1; }
         hipLaunchKernelGGL((gemm_skinny_kernel<T, false>), dim3(ceil_div(p->N, 16)), dim3(64 * SKINNY_WAVES), 0, s, d, ArgmaxOut{nullptr, nullptr});
         return hipGetLastError() == hipSuccess ? 1 : -1;

@@ -211,7 +211,7 @@ def _ld(t):
 
 def gemm(A, B, *, a_kmajor=False, b_kmajor=False, out=None, out_f32=False, bias=None, gelu=False,
          save_pre=None, dropout=None, rowscale=None, residual=None, rowmap=None, mul_gelu_grad=None,
-         accumulate=False, split_k=0, ldc=None, a_colsum=None, m_dev=None, prefetch=None):
+         accumulate=False, split_k=0, ldc=None, a_colsum=None, m_dev=None, prefetch=None, tail=False):
     """C = epilogue(A @ B); see MvltGemm.  A: [M,K] (or [K,M] if a_kmajor);
     B: [N,K] torch-Linear layout (or [K,N] if b_kmajor).
     (Written for a short host path: ~330 calls per training step; pointers go into the struct as plain ints.)"""
@@ -278,6 +278,10 @@ def gemm(A, B, *, a_kmajor=False, b_kmajor=False, out=None, out_f32=False, bias=
         epi |= L.EPI_OUT_F32
     if accumulate:
         epi |= L.EPI_ACCUM
+    if tail:                       # MVLT_EPI_TAIL: rows at or beyond *m_dev run the epilogue on a zero accumulator (k-slices refuse it)
+        assert m_dev is not None and not a_kmajor
+        epi |= L.EPI_TAIL
+        split_k = split_k or 1
     p.epilogue = epi
     p.split_k = split_k
     if m_dev is not None:          # valid storage rows of A on the device (ragged batch planned on the GPU)
@@ -1433,6 +1437,21 @@ def droppath_scales(probs, B, seed, tag=0):
     s = torch.empty((probs.numel(), B), dtype=torch.float32, device=probs.device)
     L.check(L.lib().mvlt_droppath_scales(_p(s), _p(probs), probs.numel(), B, int(seed), int(tag), _stream()), "mvlt_droppath_scales")
     return s
+
+
+def droppath_plan(scales, row0, row_step, lt, B, ld):
+    """Row plans (mvlt_droppath_plan) of the len(lt) blocks whose DropPath scales are rows row0, row0 + row_step, ... of `scales`
+    ([*, B] f32); lt: int32 [nblk] on the device, tokens per sample (0: no plan).  -> perm, inv int32 [nblk, ld], count int32
+    [nblk].  One launch, nothing read back; rows of perm / inv beyond B * lt[i] and the rows of skipped blocks stay unwritten."""
+    _need_cuda(scales)
+    assert scales.dtype == torch.float32 and scales.is_contiguous() and lt.dtype == torch.int32 and lt.is_contiguous()
+    n = lt.numel()
+    assert scales.numel() >= (row0 + (n - 1) * row_step + 1) * B
+    buf = torch.empty(n * (2 * ld + 1), dtype=torch.int32, device=scales.device)
+    perm, inv, count = buf[:n * ld].view(n, ld), buf[n * ld:2 * n * ld].view(n, ld), buf[2 * n * ld:]
+    L.check(L.lib().mvlt_droppath_plan(_p(scales), int(row0), int(row_step), _p(lt), n, B, ld, _p(perm), _p(inv), _p(count), _stream()),
+            "mvlt_droppath_plan")
+    return perm, inv, count
 
 
 # ----------------------------------------------------------------------------- loss / optimizer / decode

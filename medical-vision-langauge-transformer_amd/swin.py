@@ -110,6 +110,9 @@ _FUSED_WMSA = os.environ.get("MVLT_FUSED_WMSA", "auto")     # "0" never, "1" whe
 _SWIN_BWD_ONE = int(os.environ.get("MVLT_SWIN_BWD_ONE", "384"))        # smallest width whose blocks take the one-launch backward (0: none; host.cpp reads it too)
 _SWIN_BWD_ONE = (1 << 30) if _SWIN_BWD_ONE <= 0 else (96 if _SWIN_BWD_ONE == 1 else _SWIN_BWD_ONE)
 _SWIN_BWD_PROJ = os.environ.get("MVLT_SWIN_BWD_PROJ", "1") != "0"     # proj dgrad inside the attention backward (A/B switch; host.cpp reads it too)
+# Mlp branch of a stage-2 / 3 block only on the rows of the samples DropPath keeps (native host path, bf16, training): "0" = dense
+_DROP_COMPACT = os.environ.get("MVLT_SWIN_DROP_COMPACT", "1") != "0"
+_DROP_COMPACT_MIN_C = 384             # stages 0 / 1 (p <= 0.05, row-streaming products that refuse a device row count) stay dense
 _WMSA2 = os.environ.get("MVLT_WMSA2", "1") != "0"           # second design at stage 2 (A/B measurements and parity tests turn it off)
 
 
@@ -260,6 +263,8 @@ class SwinTransformer(nn.Module):
                 self.__dict__["_dp_probs"] = probs          # cached: a per-step H2D copy would stall the host
             if img.is_cuda:      # one launch (counter RNG, like the dropout masks) instead of rand / compare / cast / sub / div
                 dp = ops.droppath_scales(probs, B, next_seed(), 0x44500000)
+                if save and self._drop_compact(self.num_features, cd):
+                    self._dp_plan_all(dp, B)          # one more launch: the row plans of every block that skips its dropped samples
             else:
                 keep = (torch.rand(2 * nblk, B, device=img.device) >= probs[:, None]).float()
                 dp = (keep / (1.0 - probs[:, None])).contiguous()
@@ -291,6 +296,35 @@ class SwinTransformer(nn.Module):
             saved["arena"] = ar
         return y.view(B, -1, self.num_features), saved
 
+    # ------------------------------------------------------------------ DropPath row plans (csrc/host.cpp swin_block_fwd / _bwd)
+    @staticmethod
+    def _drop_compact(C, dtype):
+        return _DROP_COMPACT and ops.NATIVE and C >= _DROP_COMPACT_MIN_C and dtype == torch.bfloat16
+
+    def _dp_plan_all(self, dp, B):
+        lt = self.__dict__.get("_dp_lt")
+        if lt is None or lt[0].device != dp.device:
+            vals = [l.input_resolution[0] * l.input_resolution[1] if (b.dim >= _DROP_COMPACT_MIN_C and b.drop_path_prob > 0) else 0
+                    for l, b in self._blocks()]
+            lt = (torch.tensor(vals, dtype=torch.int32, device=dp.device), max(vals))
+            self.__dict__["_dp_lt"] = lt             # cached like _dp_probs: a per-step H2D copy would stall the host
+        if lt[1] > 0:
+            self.__dict__["_dp_plan"] = (dp,) + ops.droppath_plan(dp, 1, 2, lt[0], B, B * lt[1])
+
+    def _dp_plan_of(self, s2, B, Lt, C, dtype):
+        """[perm, inv, count] of the block whose Mlp-branch scales are s2, or None when the block runs dense."""
+        if s2 is None or not self._drop_compact(C, dtype):
+            return None
+        rows = B * Lt
+        pl = self.__dict__.get("_dp_plan")
+        if pl is not None and s2._base is pl[0]:          # a row of the forward pass's scales: its plan is already there
+            i = (s2.storage_offset() // B - 1) // 2
+            return [pl[1][i, :rows], pl[2][i, :rows], pl[3][i:i + 1]]
+        # scales from elsewhere (a caller of the block functions): a plan of their own -- a pure function of s2
+        lt = torch.full((1,), Lt, dtype=torch.int32, device=s2.device)
+        perm, inv, count = ops.droppath_plan(s2.contiguous(), 0, 1, lt, B, rows)
+        return [perm[0], inv[0], count]
+
     def _block_fwd(self, ar, blk, x, B, H, W, s1, s2, save):
         C, nH, ws = blk.dim, blk.num_heads, blk.window_size
         Lt = H * W
@@ -303,9 +337,10 @@ class SwinTransformer(nn.Module):
             mode = _wmsa_mode(x.dtype, B, H, C, nH)
             geo = [B, H, C, nH, blk.shift_size, mode,
                    ops.wmsa2_sync_ws(x.device, L.lib().mvlt_swin_wmsa2_sync_words(B, H)).data_ptr() if mode == 2 else 0]
+            plan = self._dp_plan_of(s2, B, Lt, C, x.dtype) if save else None
             out = ops.host().swin_block_fwd(x, w, f, geo, [w2n.data_ptr(), n2w.data_ptr()], at.scale, blk.norm1.eps,
                                             0 if s1 is None else s1.data_ptr(), 0 if s2 is None else s2.data_ptr(),
-                                            save, ops.stream_int())
+                                            save, ops.stream_int(), plan or [])
             return out[0], ((blk, out[1:], s1, s2, H, W) if save else None)
         mode = _wmsa_mode(x.dtype, B, H, C, nH)
         if mode:
@@ -404,10 +439,13 @@ class SwinTransformer(nn.Module):
         w2n, n2w = batched_window_maps(B, H, W, blk.window_size, blk.shift_size, dx2.device)
         w, f, gr = self._block_desc(ar, blk)
         at, mlp = blk.attn, blk.mlp
+        # the block that consumes dx0 takes dx0 * s2_next in ITS compact row order when it skipped its dropped samples
+        plan_next = self._dp_plan_of(s2_next, B, H * W, blk.dim, dx2.dtype)
         out = ops.host().swin_block_bwd(dx2, saved, w, f, gr, [B, H, blk.dim, blk.num_heads, blk.shift_size, 0],
                                         [w2n.data_ptr(), n2w.data_ptr()], at.scale, 0 if s1 is None else s1.data_ptr(),
                                         0 if s2 is None else s2.data_ptr(), 0 if s2_next is None else s2_next.data_ptr(),
-                                        dy2_pre if s2 is not None else None, ops.stream_int(), ops.side_int(dx2.device))
+                                        dy2_pre if s2 is not None else None, ops.stream_int(), ops.side_int(dx2.device),
+                                        0 if plan_next is None else plan_next[1].data_ptr())
         dx0 = out[0]
         ar.mark(mlp.fc1.weight, mlp.fc1.bias, mlp.fc2.weight, mlp.fc2.bias, blk.norm1.weight, blk.norm1.bias,
                 blk.norm2.weight, blk.norm2.bias, at.qkv.weight, at.qkv.bias, at.proj.weight, at.proj.bias,

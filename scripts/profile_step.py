@@ -13,6 +13,18 @@ M.manual_seed(1)
 step = PretrainStep(model)
 batch = synthetic_batch(B, 80, "cuda", 1234, with_lengths=os.environ.get("PACK", "1") == "1")
 import random; random.seed(5678)
+if os.environ.get("KEPT"):
+    # mean fraction of the samples whose Mlp branch DropPath keeps in the Swin stage-2 / 3 blocks (C >= 384), over all steps run
+    _swin = [m for m in model.modules() if type(m).__name__ == "SwinTransformer"][0]
+    _rows = [2 * i + 1 for i, d in enumerate(b.dim for l in _swin.layers for b in l.blocks) if d >= 384]
+    _kept, _step = [], step
+    def step(b):
+        out = _step(b)
+        _kept.append(_swin.last_droppath[_rows].ne(0).float().mean())
+        return out
+    step.model, step.opt = _step.model, _step.opt
+    import atexit
+    atexit.register(lambda: print(f"mean kept fraction of the stage-2/3 Mlp samples over {len(_kept)} steps: {float(torch.stack(_kept).mean()):.4f}", flush=True))
 for i in range(warm):
     l = step(batch)
 torch.cuda.synchronize()
