@@ -164,7 +164,8 @@ __global__ __launch_bounds__(256) void embed_bwd_tokens_kernel(const EmbDev p) {
         const f32x4 g = load4f(dout + row * p.H + c);
         const int wid = emb_word_id(p, b, posi);
         if (wid < 0) { if (dimg) store4f(dimg + ((long)b * p.n_img + (posi - 1)) * p.H + c, g); }
-        else if (p.dword && posi != 0 && posi != p.n_img + 1) {
+        // [CLS] / [SEP] exist only behind an image prefix (the position kernel adds their rows); text only: every position is text
+        else if (p.dword && (p.n_img < 0 || (posi != 0 && posi != p.n_img + 1))) {
             float* d = p.dword + (long)wid * p.H + c;
 #pragma unroll
             for (int e = 0; e < 4; ++e) atomicAdd(d + e, g[e]);
