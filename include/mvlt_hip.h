@@ -745,6 +745,25 @@ int mvlt_grad_norm_finish(const double* partial, int nparts, float grad_scale, f
 int mvlt_adamw_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16,
                        int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
                        int step, float grad_scale, const float* coef_dev, const int32_t* skip_dev, void* stream);
+/* The sweep with parameter groups resolved inside the launch (plain arguments, no struct): a contiguous range stays ONE launch
+ * however many groups it crosses.
+ *   block_group[b]   (uint8)  group of elements [64 b, 64 b + 64) of THIS range: it points at the byte of the range's first block
+ *                             and spans n / 64 bytes.  Every id must be < ngroups (the caller guarantees it; an id in
+ *                             [ngroups, 256) reads an unset table slot, never out of bounds).
+ *   group_lr_scale[g], group_weight_decay[g]   (f32 [ngroups], device)   group g runs with lr_g = lr * group_lr_scale[g] (one f32
+ *                             product) and its own weight decay; otherwise the element arithmetic is mvlt_adamw's own: a table of
+ *                             (1, wd) gives mvlt_adamw's results bit for bit.
+ *   lr               stays an argument: a schedule moves it every step, the tables are static.
+ *   coef_dev / skip_dev       both NULL: plain.  Both set: mvlt_adamw_guarded's semantics (gradient scale grad_scale * *coef_dev,
+ *                             nothing written when *skip_dev != 0).
+ * MVLT_ERR_ARG before any launch: a NULL required pointer (shadow_bf16 alone may be NULL), n < 64 or n % 64 != 0, ngroups outside
+ * 1..256, step < 1, param / grad / exp_avg / exp_avg_sq not 16-byte aligned, exactly one of coef_dev / skip_dev set.
+ * mvlt_adamw_groups_block(): the block size of the map (64 elements); a binding checks it against its arena alignment. */
+int mvlt_adamw_groups_block(void);
+int mvlt_adamw_groups(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16, int64_t n,
+                      const uint8_t* block_group, const float* group_lr_scale, const float* group_weight_decay, int ngroups,
+                      float lr, float beta1, float beta2, float eps, int step, float grad_scale,
+                      const float* coef_dev, const int32_t* skip_dev, void* stream);
 
 /* ------------------------------------------------------------------ decode (greedy, KV cache)
  * 2-token cached step attention (model.py:82-108): q rows = n_new new tokens,

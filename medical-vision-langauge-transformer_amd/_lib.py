@@ -265,6 +265,8 @@ SYMBOLS = {
     "mvlt_softmax_rows": (i32, [i32, vp, i64, i32, i32, vp, vp]),
     "mvlt_adamw": (i32, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp]),
     "mvlt_adamw_guarded": (i32, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp, vp, vp]),
+    "mvlt_adamw_groups_block": (i32, []),
+    "mvlt_adamw_groups": (i32, [vp, vp, vp, vp, vp, i64, vp, vp, vp, i32, f32, f32, f32, f32, i32, f32, vp, vp, vp]),
     "mvlt_grad_sumsq_parts": (i32, []),
     "mvlt_grad_sumsq": (i32, [vp, i64, vp, i32, vp]),
     "mvlt_grad_norm_finish": (i32, [vp, i32, f32, f32, i32, vp, vp, vp]),

@@ -474,6 +474,59 @@ __global__ __launch_bounds__(256) void adamw_guarded_kernel(float* p, const floa
     if (*skip != 0) return;
     adamw_sweep(p, g, m, v, sh, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale * *coef);
 }
+// The sweep with per-group (lr, weight decay): parameter groups are resolved INSIDE the launch, so a run of the arena is still one
+// launch however many groups it crosses (weights and biases alternate along the arena: one launch per same-group piece would be
+// several hundred launches of a few KB).  block_group[b] names the group of elements [64 b, 64 b + 64) -- every parameter starts
+// on a 64-element boundary, so a lane's f32x4 never straddles two groups -- and the two factors of a group that the element
+// arithmetic uses, 1 - lr_g wd_g and lr_g / bc1 with lr_g = lr * lr_scale[g] (one f32 product), are staged in LDS once per
+// workgroup: a lane's group differs within a wave (its 256 elements span four blocks), so they cannot live in scalar registers.
+// The byte of the map is an ordinary cached load issued beside the four streams; the LDS read behind it is the only dependent
+// access.  A SECOND body, not a generalised adamw_sweep: the two kernels above keep their code.  A table of (1, wd) must give
+// mvlt_adamw's bits, so the element arithmetic is spelled out in the form the compiler gives adamw_sweep (-ffp-contract=fast, read
+// off its ISA) with contraction switched off around it, instead of hoping that it contracts a second body alike:
+//   m' = fma(1 - b1, gr, b1 m)   v' = fma(b2, v, gr ((1 - b2) gr))   p' = fma(1 - lr wd, p, -((lr / bc1) m') / (sqrt(v') / bc2s + eps))
+// with 1 - lr wd = fma(-lr, wd, 1).  tests/test_param_groups_gpu.py holds the two bodies together bit for bit.
+// n is a multiple of 64: no scalar tail.  coef / skip both NULL: plain; both set: the guarded semantics above.
+#define ADAMW_GROUP_BLOCK 64
+#define ADAMW_MAX_GROUPS 256
+__global__ __launch_bounds__(256) void adamw_groups_kernel(float* p, const float* g, float* m, float* v, bf16_t* sh, long n,
+                                                          const uint8_t* block_group, const float* lr_scale, const float* wd_tab,
+                                                          int ngroups, float lr, float b1, float b2, float eps,
+                                                          float bc1, float bc2_sqrt, float gscale,
+                                                          const float* coef, const int32_t* skip) {
+#pragma clang fp contract(off)
+    __shared__ float s_decay[ADAMW_MAX_GROUPS], s_step[ADAMW_MAX_GROUPS];
+    if (skip && *skip != 0) return;                    // (uniform over the grid: nobody reaches the barrier)
+    if (coef) gscale = gscale * *coef;
+    if ((int)threadIdx.x < ngroups) {
+        const float lr_g = lr * lr_scale[threadIdx.x];
+        s_decay[threadIdx.x] = __builtin_fmaf(-lr_g, wd_tab[threadIdx.x], 1.0f);
+        s_step[threadIdx.x] = lr_g / bc1;
+    }
+    __syncthreads();
+    const float omb1 = 1.0f - b1, omb2 = 1.0f - b2;
+    const long nv = n / 4;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nv; i += (long)gridDim.x * 256) {
+        const int grp = block_group[i / (ADAMW_GROUP_BLOCK / 4)];
+        f32x4 pp = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p + 4 * i));
+        f32x4 gg = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g + 4 * i));
+        f32x4 mm = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(m + 4 * i));
+        f32x4 vv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(v + 4 * i));
+        const float decay = s_decay[grp], step = s_step[grp];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float gr = gg[e] * gscale;
+            mm[e] = __builtin_fmaf(omb1, gr, b1 * mm[e]);
+            vv[e] = __builtin_fmaf(b2, vv[e], gr * (omb2 * gr));
+            const float q = (step * mm[e]) / (sqrtf(vv[e]) / bc2_sqrt + eps);
+            pp[e] = __builtin_fmaf(decay, pp[e], -q);
+        }
+        __builtin_nontemporal_store(pp, reinterpret_cast<f32x4*>(p + 4 * i));
+        __builtin_nontemporal_store(mm, reinterpret_cast<f32x4*>(m + 4 * i));
+        __builtin_nontemporal_store(vv, reinterpret_cast<f32x4*>(v + 4 * i));
+        if (sh) store4f(sh + 4 * i, pp);
+    }
+}
 
 // ------------------------------------------------------------------ gradient norm (clipping, non-finite step skip)
 // Sum of squares of one f32 range in f64: every element is widened BEFORE it is squared (the product of two f32 values is exact in
@@ -1229,6 +1282,24 @@ extern "C" int mvlt_adamw_guarded(float* param, const float* grad, float* exp_av
     hipLaunchKernelGGL(adamw_guarded_kernel, dim3(grid_for(n / 4 + 1, 256, adamw_blocks())), dim3(256), 0, STREAM(stream), param,
                        grad, exp_avg, exp_avg_sq, (bf16_t*)shadow_bf16, (long)n, lr, beta1, beta2, eps, weight_decay, (float)bc1,
                        (float)sqrt(bc2), grad_scale, coef_dev, skip_dev);
+    MVLT_LAUNCH_CHECK();
+    return MVLT_OK;
+}
+
+extern "C" int mvlt_adamw_groups_block(void) { return ADAMW_GROUP_BLOCK; }
+extern "C" int mvlt_adamw_groups(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, void* shadow_bf16, int64_t n,
+                                 const uint8_t* block_group, const float* group_lr_scale, const float* group_weight_decay,
+                                 int ngroups, float lr, float beta1, float beta2, float eps, int step, float grad_scale,
+                                 const float* coef_dev, const int32_t* skip_dev, void* stream) {
+    MVLT_CHECK(param && grad && exp_avg && exp_avg_sq && block_group && group_lr_scale && group_weight_decay, MVLT_ERR_ARG);
+    MVLT_CHECK(n >= ADAMW_GROUP_BLOCK && n % ADAMW_GROUP_BLOCK == 0 && step >= 1, MVLT_ERR_ARG);
+    MVLT_CHECK(ngroups >= 1 && ngroups <= ADAMW_MAX_GROUPS && (coef_dev == nullptr) == (skip_dev == nullptr), MVLT_ERR_ARG);
+    MVLT_CHECK(aligned16(param) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq), MVLT_ERR_ARG);
+    MVLT_CHECK(!shadow_bf16 || ((uintptr_t)shadow_bf16 & 7) == 0, MVLT_ERR_ARG);
+    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+    hipLaunchKernelGGL(adamw_groups_kernel, dim3(grid_for(n / 4 + 1, 256, adamw_blocks())), dim3(256), 0, STREAM(stream), param, grad,
+                       exp_avg, exp_avg_sq, (bf16_t*)shadow_bf16, (long)n, block_group, group_lr_scale, group_weight_decay, ngroups,
+                       lr, beta1, beta2, eps, (float)bc1, (float)sqrt(bc2), grad_scale, coef_dev, skip_dev);
     MVLT_LAUNCH_CHECK();
     return MVLT_OK;
 }

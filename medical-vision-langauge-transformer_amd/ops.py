@@ -1510,6 +1510,28 @@ def adamw_guarded(param, grad, exp_avg, exp_avg_sq, shadow, lr, beta1, beta2, ep
                                        float(grad_scale), _p(coef), _p(skip), _stream()), "mvlt_adamw_guarded")
 
 
+def adamw_groups_block():
+    return int(L.lib().mvlt_adamw_groups_block())
+
+
+def adamw_groups(param, grad, exp_avg, exp_avg_sq, shadow, block_group, lr_scale, weight_decay, lr, beta1, beta2, eps, step,
+                 grad_scale=1.0, coef=None, skip=None):
+    """adamw with the parameter groups resolved inside the launch: ``block_group`` (uint8, one per 64 elements of ``param``) names
+    the group of each block, group g runs with lr * lr_scale[g] and weight_decay[g] (f32 tables on the device).  ``coef`` / ``skip``
+    both None: plain; both given: adamw_guarded's semantics."""
+    _need_cuda(param, block_group, lr_scale, weight_decay)
+    n = param.numel()
+    assert block_group.dtype == torch.uint8 and block_group.is_contiguous() and block_group.numel() * 64 == n, (block_group.shape, n)
+    assert lr_scale.dtype == torch.float32 and weight_decay.dtype == torch.float32 and lr_scale.numel() == weight_decay.numel()
+    assert lr_scale.is_contiguous() and weight_decay.is_contiguous()
+    if coef is not None or skip is not None:
+        _need_cuda(coef, skip)
+        assert coef.dtype == torch.float32 and skip.dtype == torch.int32
+    L.check(L.lib().mvlt_adamw_groups(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), _p(shadow), n, _p(block_group),
+                                      _p(lr_scale), _p(weight_decay), lr_scale.numel(), float(lr), float(beta1), float(beta2),
+                                      float(eps), int(step), float(grad_scale), _p(coef), _p(skip), _stream()), "mvlt_adamw_groups")
+
+
 def grad_sumsq_parts():
     return int(L.lib().mvlt_grad_sumsq_parts())
 

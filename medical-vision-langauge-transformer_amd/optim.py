@@ -21,6 +21,12 @@ taken on the device (``mvlt_grad_sumsq`` over the runs of the sweep, ``mvlt_grad
 ``mvlt_adamw_guarded``, which reads the clip coefficient and the skip flag from device memory: global-norm clipping
 as ``torch.nn.utils.clip_grad_norm_`` defines it, and a step whose gradients hold a NaN or an Inf is not applied --
 no host synchronisation in either case.  With both options off the launches are the ones described above.
+
+``param_groups`` (opt-in): per-group learning-rate scale and weight decay -- no weight decay on biases / LayerNorm weights / Swin's
+relative-position tables (``no_decay_rules()``), a smaller learning rate for a pretrained backbone (``param_groups_by_name``).  Weights
+and biases alternate along the arena, so the groups are resolved INSIDE the sweep (``mvlt_adamw_groups``: one byte per ALIGN-element
+block names its group, two f32 tables hold the constants): the step stays 4-6 launches on every route above.  ``LRSchedule`` moves
+``opt.lr`` on the host between steps (warm-up, then linear / cosine / constant).  Without ``param_groups`` nothing changes.
 """
 import math
 
@@ -31,6 +37,143 @@ from .arena import ALIGN, Arena
 from .runtime import compute_dtype_of
 
 
+MAX_GROUPS = 256          # a uint8 per arena block names its group (mvlt_adamw_groups)
+
+
+def _named(model):
+    """(name, parameter) as the arena names them: state-dict names, a shared parameter once."""
+    return list(model.named_parameters())
+
+
+def _hyper_value(what, v, where):
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+        raise ValueError(f"{what} must be a finite number >= 0, got {v!r} ({where})")
+    return float(v)
+
+
+def _resolve_groups(model, groups):
+    """param_groups as the user wrote them -> [dict(names=(...), lr_scale=float, weight_decay=float or None)], every complaint
+    raised here: construction needs no arena and no GPU."""
+    named = _named(model)
+    name_of = {id(p): n for n, p in named}
+    known = set(name_of.values())
+    owner, out = {}, []
+    for k, g in enumerate(groups):
+        if not isinstance(g, dict):
+            raise ValueError(f"param_groups[{k}] must be a dict, got {type(g).__name__}")
+        extra = set(g) - {"params", "names", "lr_scale", "weight_decay"}
+        if extra:
+            raise ValueError(f"param_groups[{k}]: unknown keys {sorted(extra)} (params, names, lr_scale, weight_decay)")
+        names = []
+        for p in g.get("params") or ():
+            if id(p) not in name_of:
+                raise ValueError(f"param_groups[{k}]: a tensor of shape {tuple(getattr(p, 'shape', ()))} is not a parameter of the model")
+            names.append(name_of[id(p)])
+        for n in g.get("names") or ():
+            if n not in known:
+                raise KeyError(f"param_groups[{k}]: unknown parameter name {n!r}")
+            names.append(n)
+        for n in names:
+            if n in owner:
+                raise ValueError(f"parameter {n!r} is in param_groups[{owner[n]}] and in param_groups[{k}]"
+                                 if owner[n] != k else f"parameter {n!r} is listed twice in param_groups[{k}]")
+            owner[n] = k
+        wd = g.get("weight_decay")
+        out.append(dict(names=tuple(names), lr_scale=_hyper_value("lr_scale", g.get("lr_scale", 1.0), f"param_groups[{k}]"),
+                        weight_decay=None if wd is None else _hyper_value("weight_decay", wd, f"param_groups[{k}]")))
+    return out
+
+
+def _no_decay(name, p):
+    return p.dim() <= 1 or name.endswith(".bias") or "relative_position_bias_table" in name or "absolute_pos_embed" in name
+
+
+def no_decay_rules():
+    """Rules for param_groups_by_name: weight decay 0 for biases, LayerNorm weights (every parameter with dim() <= 1) and Swin's
+    relative_position_bias_table / absolute_pos_embed -- HF's ``no_decay`` list and Swin's no_weight_decay().  Everything else,
+    embedding tables included, keeps the optimizer's weight decay, as HF does for BERT."""
+    return [(_no_decay, dict(weight_decay=0.0))]
+
+
+def param_groups_by_name(model, rules):
+    """param_groups for FusedAdamW from ``rules`` = [(regex, dict(lr_scale=..., weight_decay=...))].  The regex is searched in the
+    state-dict name (re.search; a callable (name, parameter) -> bool is taken as is: no_decay_rules() tests dim()).  The FIRST
+    matching rule that sets a value wins, per value -- so rule lists compose: [(r"^conv[.]", dict(lr_scale=0.1))] +
+    no_decay_rules() gives a backbone bias lr_scale 0.1 AND weight decay 0, four groups in all.  Parameters that resolve to the same
+    (lr_scale, weight_decay) share a group; parameters no rule touches are left out (FusedAdamW keeps them at its own values)."""
+    import re
+    tests = []
+    for k, (pat, sets) in enumerate(rules):
+        extra = set(sets) - {"lr_scale", "weight_decay"}
+        if extra:
+            raise ValueError(f"rule {k}: unknown keys {sorted(extra)} (lr_scale, weight_decay)")
+        for key, v in sets.items():
+            _hyper_value(key, v, f"rule {k}")
+        tests.append((pat if callable(pat) else (lambda n, p, rx=re.compile(pat): rx.search(n) is not None), sets))
+    groups = {}
+    for name, p in _named(model):
+        got = {}
+        for test, sets in tests:
+            if test(name, p):
+                for key, v in sets.items():
+                    got.setdefault(key, float(v))
+        if got:
+            groups.setdefault((got.get("lr_scale"), got.get("weight_decay")), []).append(name)
+    return [dict(names=names, **{k: v for k, v in (("lr_scale", ls), ("weight_decay", wd)) if v is not None})
+            for (ls, wd), names in groups.items()]
+
+
+class LRSchedule:
+    """Warm-up and decay of FusedAdamW's learning rate (torch.optim.lr_scheduler refuses anything that is not a torch Optimizer).
+    ``step()`` -- once after every opt.step() -- advances t and sets opt.lr = base_lr * factor(t) on the host, in fp64; the value is a
+    scalar argument of the next step's launches (a deferred optimizer tail keeps the lr of the step it belongs to), so nothing is
+    synchronised.  Per-group lr_scale factors multiply it on the device.  factor(t):
+        t < warmup_steps             t / warmup_steps                       (the first step runs at factor(0), as torch's LambdaLR)
+        "constant"                   1
+        "linear"                     max(min_ratio, (total_steps - t) / (total_steps - warmup_steps))
+        "cosine"                     min_ratio + (1 - min_ratio) * 0.5 * (1 + cos(pi * (t - warmup_steps) / (total_steps - warmup_steps)))
+        t >= total_steps             min_ratio, whatever the kind (the schedule is over; "constant" drops from 1 to it)
+    The schedule counts CALLS: it also advances on a step that skip_nonfinite refused (whether the device refused it is not known
+    on the host when step() returns), exactly as a torch scheduler beside a GradScaler-skipped step."""
+    KINDS = ("linear", "cosine", "constant")
+
+    def __init__(self, opt, warmup_steps, total_steps, kind="linear", min_ratio=0.0):
+        if kind not in self.KINDS:
+            raise ValueError(f"kind must be one of {self.KINDS}, got {kind!r}")
+        if int(warmup_steps) != warmup_steps or int(total_steps) != total_steps or not 0 <= warmup_steps < total_steps:
+            raise ValueError(f"need integers 0 <= warmup_steps < total_steps, got {warmup_steps!r}, {total_steps!r}")
+        if not (isinstance(min_ratio, (int, float)) and 0.0 <= min_ratio <= 1.0):
+            raise ValueError(f"min_ratio must be in [0, 1], got {min_ratio!r}")
+        self.opt, self.warmup_steps, self.total_steps = opt, int(warmup_steps), int(total_steps)
+        self.kind, self.min_ratio = kind, float(min_ratio)
+        self.base_lr, self.t = float(opt.lr), 0
+        opt.lr = self.base_lr * self.factor(0)
+
+    def factor(self, t: int) -> float:
+        w, n = self.warmup_steps, self.total_steps
+        if t < w:
+            return t / w
+        if t >= n:
+            return self.min_ratio
+        if self.kind == "constant":
+            return 1.0
+        if self.kind == "linear":
+            return max(self.min_ratio, (n - t) / (n - w))
+        return self.min_ratio + (1.0 - self.min_ratio) * 0.5 * (1.0 + math.cos(math.pi * (t - w) / (n - w)))
+
+    def step(self) -> float:
+        self.t += 1
+        self.opt.lr = self.base_lr * self.factor(self.t)
+        return self.opt.lr
+
+    def state_dict(self):
+        return dict(t=self.t, base_lr=self.base_lr)
+
+    def load_state_dict(self, sd) -> None:
+        self.t, self.base_lr = int(sd["t"]), float(sd["base_lr"])
+        self.opt.lr = self.base_lr * self.factor(self.t)
+
+
 class _OptTail:
     """The part of one optimizer step that FusedAdamW(defer_tail=True) has NOT launched yet: the runs of the arena above
     ``split`` (BertLayers 1.. and the heads), in chunks.  The next forward pass launches them on the optimizer stream
@@ -39,18 +182,16 @@ class _OptTail:
     stream order (``flush``: Arena.refresh_shadow, the next step(), state_dict, PretrainStep.flush)."""
 
     def __init__(self, opt, ar, chunks):
+        self.opt = opt
         self.ar = ar
         self.chunks = chunks            # [dict(lo=, runs=[(lo, hi, step)], event=None, waited=False)] in arena order
         self.launched = False
         # the hyper-parameters of the step this tail belongs to (an LR schedule may move opt.lr before the tail runs)
-        self.hyper = (opt.lr, opt.betas[0], opt.betas[1], opt.eps, opt.weight_decay, opt.grad_scale)
+        self.hyper = opt._hyper()
 
     def _run(self, ch):
-        lr, b1, b2, eps, wd, gs = self.hyper
-        ar = self.ar
         for lo, hi, st in ch["runs"]:
-            ops.adamw(ar.flat[lo:hi], ar.grad[lo:hi], ar.exp_avg[lo:hi], ar.exp_avg_sq[lo:hi],
-                      ar.shadow[lo:hi] if ar.shadow is not None else None, lr, b1, b2, eps, wd, st + 1, gs)
+            self.opt._launch(self.ar, lo, hi, st + 1, self.hyper)
 
     def launch(self):
         """Queue every chunk on the optimizer stream behind what the current stream has queued so far."""
@@ -94,8 +235,13 @@ class _OptTail:
 
 class FusedAdamW:
     def __init__(self, model, lr=4e-5, betas=(0.9, 0.999), eps=1e-6, weight_decay=1e-4, grad_scale=1.0, defer_tail=False,
-                 max_grad_norm=None, skip_nonfinite=False):
+                 max_grad_norm=None, skip_nonfinite=False, param_groups=None):
         self.model = model
+        # param_groups (opt-in): [dict(params=[Parameter, ...] and / or names=[state-dict name, ...], lr_scale=1.0, weight_decay=<the
+        # optimizer's>)]; parameters that no dict lists keep the optimizer's lr and weight decay.  The groups are resolved INSIDE the
+        # sweep (mvlt_adamw_groups: a byte per ALIGN-element block of the arena names its group), so the step stays 4-6 launches on
+        # every route -- plain, guarded, overlap_with_backward(), defer_tail.  None: the launches are exactly the ungrouped ones.
+        self._groups, self._tables = None, None
         # defer_tail (opt-in, mvlt_amd.train.PretrainStep(defer_optimizer_tail=True)): step() updates the parameters the next
         # forward pass reads FIRST (Swin tower, embeddings, BertLayer 0) and leaves the rest -- BertLayers 1.., pooler, heads:
         # 102 M of the 182 M updated parameters, 3.1 GB of the sweep's 5.5 GB -- to the next forward pass, which runs them on the
@@ -122,6 +268,7 @@ class FusedAdamW:
         self._skipped = 0
         self.max_grad_norm = max_grad_norm
         self.skip_nonfinite = skip_nonfinite
+        self._set_groups(param_groups)
 
     @property
     def max_grad_norm(self):
@@ -210,6 +357,7 @@ class FusedAdamW:
                 old.exp_avg = old.exp_avg_sq = None
             self._arena = ar
             self.__dict__["_plans"] = {}          # cached (lo, hi) sweep ranges are offsets into the OLD arena layout
+            self._tables = self._build_group_tables(ar) if (self._groups is not None and ar.flat.is_cuda) else None
             if self._overlap is not None:
                 self._hook(ar)
         return ar
@@ -228,6 +376,9 @@ class FusedAdamW:
         self.flush()
         out = {"hyper": dict(lr=self.lr, betas=tuple(self.betas), eps=self.eps, weight_decay=self.weight_decay),
                "state": {}}
+        if self._groups is not None:             # by parameter name; weight_decay None = the optimizer's
+            out["hyper"]["param_groups"] = [dict(names=list(g["names"]), lr_scale=g["lr_scale"], weight_decay=g["weight_decay"])
+                                            for g in self._groups]
         for name, p in zip(ar.names, ar.params):
             o, n = ar.offset[id(p)], p.numel()
             if ar.steps[id(p)] > 0:
@@ -244,6 +395,8 @@ class FusedAdamW:
         self.betas = tuple(hp.get("betas", self.betas))
         self.eps = hp.get("eps", self.eps)
         self.weight_decay = hp.get("weight_decay", self.weight_decay)
+        if "param_groups" in hp:                 # (a checkpoint without the key leaves the groups of this optimizer as they are)
+            self._set_groups(hp["param_groups"])
         byname = dict(zip(ar.names, ar.params))
         unknown = [k for k in sd["state"] if k not in byname]
         if unknown:
@@ -258,10 +411,74 @@ class FusedAdamW:
             ar.exp_avg_sq[o:o + n].copy_(st["exp_avg_sq"].reshape(-1))
             ar.steps[id(p)] = int(st["step"])
 
+    # ------------------------------------------------------------------ parameter groups
+    @property
+    def param_groups(self):
+        """Read-only view for logging: [dict(lr=opt.lr * lr_scale, lr_scale=, weight_decay=, names=[...])], the parameters that no
+        group lists first (when there are any).  Without param_groups: one entry that holds every parameter."""
+        listed = set(n for g in self._groups or () for n in g["names"])
+        rest = [n for n, _ in _named(self.model) if n not in listed]
+        out = [dict(lr=self.lr, lr_scale=1.0, weight_decay=self.weight_decay, names=rest)] if rest else []
+        for g in self._groups or ():
+            wd = self.weight_decay if g["weight_decay"] is None else g["weight_decay"]
+            out.append(dict(lr=self.lr * g["lr_scale"], lr_scale=g["lr_scale"], weight_decay=wd, names=list(g["names"])))
+        return out
+
+    def _set_groups(self, groups) -> None:
+        self._groups = _resolve_groups(self.model, groups) if groups is not None else None
+        self._tables = None
+        if len(self.param_groups) > MAX_GROUPS:
+            self._groups = None
+            raise ValueError(f"{len(groups)} param_groups (+ the parameters none of them lists): at most {MAX_GROUPS} groups")
+
+    def _build_group_tables(self, ar: Arena):
+        """dict(map=uint8 [ar.total / ALIGN], lr_scale=f32 [g], weight_decay=f32 [g]) on the arena's device: the group of every
+        ALIGN-element block of the arena -- a parameter's padding carries the parameter's group -- and the two constants of every
+        group.  Group 0 is the parameters no group lists (optimizer's lr and weight decay) when there are any."""
+        if ops.adamw_groups_block() != ALIGN:
+            raise RuntimeError(f"mvlt_adamw_groups maps blocks of {ops.adamw_groups_block()} elements, the arena aligns to {ALIGN}")
+        view = self.param_groups
+        gid = {n: k for k, g in enumerate(view) for n in g["names"]}
+        bmap = torch.zeros(ar.total // ALIGN, dtype=torch.uint8)
+        for name, p in zip(ar.names, ar.params):
+            o = ar.offset[id(p)]
+            bmap[o // ALIGN:(o + p.numel() + ALIGN - 1) // ALIGN] = gid[name]
+        dev = ar.flat.device
+        return dict(map=bmap.to(dev), lr_scale=torch.tensor([g["lr_scale"] for g in view], dtype=torch.float32).to(dev),
+                    weight_decay=torch.tensor([g["weight_decay"] for g in view], dtype=torch.float32).to(dev),
+                    key=(ar, self.weight_decay))
+
+    def _group_tables(self, ar: Arena):
+        t = self._tables
+        if t is None or t["key"][0] is not ar or t["key"][1] != self.weight_decay:
+            t = self._tables = self._build_group_tables(ar)          # (first use, a rebuilt arena, opt.weight_decay assigned)
+        return t
+
+    # ------------------------------------------------------------------ the one place that launches the sweep
+    def _hyper(self, extra_scale: float = 1.0):
+        """(lr, beta1, beta2, eps, weight_decay, grad_scale) of the step that is being launched NOW: a deferred tail keeps its own copy,
+        because an LR schedule moves ``lr`` before the tail runs."""
+        return (self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.grad_scale * extra_scale)
+
+    def _launch(self, ar: Arena, lo: int, hi: int, step: int, hyper, guard=None) -> None:
+        """One sweep launch over arena elements [lo, hi): plain or grouped (param_groups), plain or guarded (``guard`` = (coef, skip)
+        on the device).  Without param_groups these are exactly the mvlt_adamw / mvlt_adamw_guarded launches of before."""
+        lr, b1, b2, eps, wd, gs = hyper
+        sh = ar.shadow[lo:hi] if ar.shadow is not None else None
+        if self._groups is not None:
+            t = self._group_tables(ar)
+            coef, skip = guard if guard is not None else (None, None)
+            ops.adamw_groups(ar.flat[lo:hi], ar.grad[lo:hi], ar.exp_avg[lo:hi], ar.exp_avg_sq[lo:hi], sh,
+                             t["map"][lo // ALIGN:hi // ALIGN], t["lr_scale"], t["weight_decay"], lr, b1, b2, eps, step, gs, coef, skip)
+        elif guard is not None:
+            ops.adamw_guarded(ar.flat[lo:hi], ar.grad[lo:hi], ar.exp_avg[lo:hi], ar.exp_avg_sq[lo:hi], sh,
+                              lr, b1, b2, eps, wd, step, gs, guard[0], guard[1])
+        else:
+            ops.adamw(ar.flat[lo:hi], ar.grad[lo:hi], ar.exp_avg[lo:hi], ar.exp_avg_sq[lo:hi], sh, lr, b1, b2, eps, wd, step, gs)
+
     # ------------------------------------------------------------------ update of a set of element ranges
     def _apply(self, ar: Arena, params, extra_scale: float = 1.0) -> None:
         """AdamW over ``params`` (arena order): one launch per contiguous run with equal step count."""
-        b1, b2 = self.betas
         run = None
         runs = []
         for p in params:
@@ -274,10 +491,9 @@ class FusedAdamW:
             else:
                 run = [o, e, st]
                 runs.append(run)
+        hyper = self._hyper(extra_scale)
         for lo, hi, st in runs:
-            ops.adamw(ar.flat[lo:hi], ar.grad[lo:hi], ar.exp_avg[lo:hi], ar.exp_avg_sq[lo:hi],
-                      ar.shadow[lo:hi] if ar.shadow is not None else None,
-                      self.lr, b1, b2, self.eps, self.weight_decay, st + 1, self.grad_scale * extra_scale)
+            self._launch(ar, lo, hi, st + 1, hyper)
 
     def _plan_runs(self, ar: Arena, params):
         """[(lo, hi, ids of the parameters of the run)]: maximal contiguous arena ranges of ``params`` that
@@ -392,18 +608,15 @@ class FusedAdamW:
         never written.  Every rank of a data-parallel run reads the same reduced bytes, so all ranks clip and skip alike."""
         ws = self._guard_buffers(ar)
         steps = ar.steps
-        b1, b2 = self.betas
         for k, (lo, hi, _) in enumerate(plan):
             ops.grad_sumsq(ar.grad[lo:hi], ws["partial"], accumulate=k > 0)
         ops.grad_norm_finish(ws["partial"], self.grad_scale, self.max_grad_norm or 0.0, self.skip_nonfinite, ws["out"], ws["flags"])
-        coef, skip = ws["out"][1:], ws["flags"][:1]
+        guard, hyper = (ws["out"][1:], ws["flags"][:1]), self._hyper()
         for lo, hi, ids in plan:
-            ops.adamw_guarded(ar.flat[lo:hi], ar.grad[lo:hi], ar.exp_avg[lo:hi], ar.exp_avg_sq[lo:hi],
-                              ar.shadow[lo:hi] if ar.shadow is not None else None,
-                              self.lr, b1, b2, self.eps, self.weight_decay, steps[ids[0]] + 1, self.grad_scale, coef, skip)
+            self._launch(ar, lo, hi, steps[ids[0]] + 1, hyper, guard)
         if self.skip_nonfinite:
             # (the pinned word is free: _state() has waited for the previous step's copy)
-            ws["host"].copy_(skip, non_blocking=True)
+            ws["host"].copy_(guard[1], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream())
             self._guard_pending = (ar, ev, tuple(id(p) for p in ar._marked))
@@ -429,7 +642,7 @@ class FusedAdamW:
                 plan = self._plan_runs(ar, [p for p in ar.params if ar.has_grad[id(p)]])
                 if key is not None:
                     self._plans[key] = plan
-            b1, b2 = self.betas
+            hyper = self._hyper()
             if self._guarded and plan:
                 self._guarded_sweep(ar, plan)
                 plan = ()
@@ -442,9 +655,7 @@ class FusedAdamW:
                     tail.append((cut, hi, st))
                     hi = cut
                 if hi > lo:
-                    ops.adamw(ar.flat[lo:hi], ar.grad[lo:hi], ar.exp_avg[lo:hi], ar.exp_avg_sq[lo:hi],
-                              ar.shadow[lo:hi] if ar.shadow is not None else None,
-                              self.lr, b1, b2, self.eps, self.weight_decay, st + 1, self.grad_scale)
+                    self._launch(ar, lo, hi, st + 1, hyper)
             if tail:
                 edges = bounds + [ar.total]
                 chunks = []

@@ -5,7 +5,7 @@ import random
 import torch
 
 from . import ops
-from .optim import FusedAdamW
+from .optim import FusedAdamW, LRSchedule
 
 
 def synthetic_batch(B, T, device, seed, vocab=30522, itm=True, with_lengths=False, lengths=None):
@@ -40,8 +40,12 @@ class PretrainStep:
     ``reducer`` (mvlt_amd.ddp.GradReducer) makes it data parallel."""
 
     def __init__(self, model, lr=None, reducer=None, world_size=1, overlap_optimizer=False, defer_optimizer_tail=False,
-                 max_grad_norm=None, skip_nonfinite=False):
-        """max_grad_norm / skip_nonfinite (opt-in, optim.FusedAdamW): clip the global L2 norm of the (rank-averaged) gradients; do
+                 max_grad_norm=None, skip_nonfinite=False, param_groups=None, lr_schedule=None):
+        """param_groups (opt-in, optim.FusedAdamW): per-group lr_scale / weight_decay, e.g. optim.param_groups_by_name(model,
+        [(r"^conv[.]", dict(lr_scale=0.1))] + optim.no_decay_rules()); works with every option below.
+        lr_schedule (opt-in): kwargs of optim.LRSchedule (dict(warmup_steps=, total_steps=, kind=, min_ratio=)) or a callable
+        opt -> LRSchedule; it is stepped after every opt.step() (``self.schedule``; save its state_dict() beside the optimizer's).
+        max_grad_norm / skip_nonfinite (opt-in, optim.FusedAdamW): clip the global L2 norm of the (rank-averaged) gradients; do
         not apply a step whose gradients hold a NaN or an Inf.  Both are decided on the device, and under a ``reducer`` every rank
         decides alike.  Neither combines with overlap_optimizer or defer_optimizer_tail (ValueError).
         defer_optimizer_tail (opt-in): the AdamW sweep over BertLayers 1.., pooler and heads is left to the NEXT call, which
@@ -55,7 +59,10 @@ class PretrainStep:
         gs = 1.0 if (reducer is None or getattr(reducer, "average", False)) else 1.0 / world_size
         self.opt = FusedAdamW(model, lr=lr if lr is not None else model.config.lr, betas=(0.9, 0.999), eps=1e-6,
                               weight_decay=1e-4, grad_scale=gs, defer_tail=defer_optimizer_tail and not overlap_optimizer,
-                              max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+                              max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, param_groups=param_groups)
+        self.schedule = None
+        if lr_schedule is not None:
+            self.schedule = lr_schedule(self.opt) if callable(lr_schedule) else LRSchedule(self.opt, **lr_schedule)
         self.reducer = reducer
         if overlap_optimizer:
             # opt-in: AdamW of finished arena slices is queued beside the rest of the backward pass.  On one
@@ -68,6 +75,8 @@ class PretrainStep:
         loss = self.model(*batch[:4], text_lengths=batch[4]) if len(batch) > 4 else self.model(*batch)
         loss.backward()
         self.opt.step()
+        if self.schedule is not None:
+            self.schedule.step()          # (host only: the lr of the NEXT step; a deferred tail keeps this step's)
         # in-launch hand-offs (mvlt_swin_wmsa2_fwd) that timed out poison the loss with NaN AND raise here, one step late:
         # the error counts travel to pinned host memory behind the step's kernels, no device sync (ops.wmsa2_check).
         # By then the NaN gradients of that step have been applied -- reload the last checkpoint -- unless the optimizer runs with
