@@ -36,7 +36,7 @@ enum { MVLT_OK = 0, MVLT_ERR_ARG = -1, MVLT_ERR_LAUNCH = -2, MVLT_ERR_UNSUPPORTE
  * signature; a binding compiles / hard-codes the value it was written against and compares it with what the
  * loaded library returns.  mvlt_sizeof(MVLT_STRUCT_*) lets a binding that mirrors the structs by hand (ctypes,
  * cgo, JNI) prove that its mirror has the size the library was compiled with (0 for an unknown id). */
-#define MVLT_ABI_VERSION 16
+#define MVLT_ABI_VERSION 17
 int mvlt_version(void);            /* MVLT_ABI_VERSION of the loaded library */
 const char* mvlt_arch(void);       /* "gfx950" */
 enum { MVLT_STRUCT_GEMM = 0, MVLT_STRUCT_LAYERNORM = 1, MVLT_STRUCT_LAYERNORM_BWD = 2, MVLT_STRUCT_LN_REDUCE_ITEM = 3,
@@ -518,6 +518,10 @@ enum MvltAttnRoute {
     MVLT_ATTN_ROUTE_BERT_BWD_KT9 = 16
 };
 int mvlt_attn_route(const MvltAttn* p, int bwd);
+/* 1 exactly when mvlt_attn_bwd of a MVLT_ATTN_SWIN call (L 49, no dropout) with dout_weight set would take
+ * MVLT_ATTN_ROUTE_SWIN_BWD_KS3 / 6 / 12, answered by that same route function: callers ask before they choose between
+ * dout_weight and a separate projection dgrad. */
+int mvlt_swin_bwd_proj_supported(int dtype, int nseq, int nH, int hd, int shift);
 
 /* ------------------------------------------------------------------ fused Swin (S)W-MSA (SURVEY.md 8b `swin_wmsa`)
  * The attention half of SwinTransformerBlock.forward in ONE launch (visual_feature_extractor.py:356-384 around
@@ -529,12 +533,7 @@ int mvlt_attn_route(const MvltAttn* p, int bwd);
  * HBM round trip.  Training: the optional pointers receive what the backward pass needs, as write-only outputs:
  *   xn_win   [B*res*res, C]  norm1(x), window order (A operand of the qkv weight gradient)
  *   attn_out [B*res*res, C]  attention output, window order (A operand of the proj weight gradient)
- *   lse      f32 [B*nW, nH, 49], mean / rstd f32 [B*res*res] (token order)
- * backward (mvlt_swin_wmsa_bwd): dy_win = gradient of the proj output in WINDOW order (rowscale already applied);
- *   output-projection dgrad, attention backward and qkv dgrad in one launch: reads q,k,v from qkv_win and lse (saved
- *   by the forward pass) and the transposed weight copies wproj_t / wqkv_t, writes dqkv [B*res*res, 3C] (window
- *   order, for the qkv weight gradient) and dxn_win [B*res*res, C] = dqkv Wqkv (window order; LayerNorm backward
- *   consumes it through its dy_rowmap); dbias_table f32 [169, nH] is ACCUMULATED (zero it first). */
+ *   lse      f32 [B*nW, nH, 49], mean / rstd f32 [B*res*res] (token order) */
 typedef struct MvltSwinWmsa {
     int dtype, B, res, C, nH, shift;
     const void* x; void* y; const int32_t* w2n;
@@ -543,15 +542,12 @@ typedef struct MvltSwinWmsa {
     const float* bias_table; float scale;
     const float* rowscale;             /* optional DropPath keep/(1-p), f32 [B] */
     void* xn_win; void* attn_out; float* lse; float* mean; float* rstd;
-    /* backward only */
-    const void* dy_win; void* dqkv; void* dxn_win; float* dbias_table;
+    /* backward only (mvlt_swin_wmsa2_bwd, see there) */
+    const void* dy_win; void* dqkv; void* dxn_win;
     /* optional, training: q,k,v in the [B*res*res, 3C] window-order layout MvltAttn uses (forward: write-only
      * output, so the unfused mvlt_attn_bwd can run on a fused forward; backward: read instead of recomputed) */
     void* qkv_win;
-    /* backward only: TRANSPOSED compute-dtype copies of the projection weights, wproj_t [C_in, C_out] = proj.weight^T and
-     * wqkv_t [C, 3C] = qkv.weight^T (mvlt_transpose_batch makes them): the dgrad products then read k-contiguous rows */
-    const void* wproj_t; const void* wqkv_t;
-    /* forward only: 1 = one workgroup per (window, head group) and NO output projection: attn_out [B*res*res, C]
+    /* mvlt_swin_wmsa_fwd only: 1 = one workgroup per (window, head group) and NO output projection: attn_out [B*res*res, C]
      * (window order, required) is the result, y / wproj / bproj / rowscale are unused; follow with mvlt_gemm
      * (bias, DropPath row scale, window-reverse row map, residual).  For launches with too few windows to fill the chip. */
     int head_split;
@@ -560,8 +556,6 @@ typedef struct MvltSwinWmsa {
 } MvltSwinWmsa;
 int mvlt_swin_wmsa_supported(int dtype, int C, int nH);   /* 1 when the fused kernels cover this width */
 int mvlt_swin_wmsa_fwd(const MvltSwinWmsa* p, void* stream);
-int mvlt_swin_wmsa_bwd(const MvltSwinWmsa* p, void* stream);
-int mvlt_swin_wmsa_bwd_supported(int dtype, int C, int nH);
 
 /* Second design of the fused forward (csrc/wmsa2.hip, bf16): a workgroup owns TWO windows (98 rows share every weight
  * fragment) and a GROUP of heads; the head groups of a window pair run in different workgroups and meet through
@@ -595,7 +589,7 @@ int mvlt_swin_wmsa2_bwd_parts(int dtype, int B, int res, int C, int nH);    /* n
  * three heads into MvltSwinWmsa.dbias_ws, f32 [mvlt_swin_wmsa2_bwd_workgroups()][3 * 169] (plain stores: nothing to zero, no
  * atomics), and mvlt_swin_wmsa2_bwd_dbias ADDS the workgroups of up to any number of launches into their tables
  * (dbias_table f32 [169, nH]) in a fixed order -- one small launch for all Swin blocks of a step; items is a HOST array.
- * (MvltSwinWmsa.dbias_table itself is not touched by mvlt_swin_wmsa2_bwd; dbias_ws may be NULL: no bias gradient.) */
+ * (dbias_ws may be NULL: no bias gradient.) */
 typedef struct MvltSwinDbiasItem { const float* ws; int nwg; int nH; float* dbias_table; } MvltSwinDbiasItem;
 int mvlt_swin_wmsa2_bwd_workgroups(int dtype, int B, int res, int C, int nH);
 int mvlt_swin_wmsa2_bwd_dbias(const MvltSwinDbiasItem* items, int n, void* stream);

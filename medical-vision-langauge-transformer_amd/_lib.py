@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(_HERE, "libmvlt_hip.so")
 
 F32, BF16 = 0, 1
 OK = 0
-ABI_VERSION = 16         # == MVLT_ABI_VERSION of the include/mvlt_hip.h these mirrors were written against
+ABI_VERSION = 17         # == MVLT_ABI_VERSION of the include/mvlt_hip.h these mirrors were written against
 ERRORS = {-1: "MVLT_ERR_ARG", -2: "MVLT_ERR_LAUNCH", -3: "MVLT_ERR_UNSUPPORTED"}
 
 EPI_BIAS, EPI_GELU, EPI_SAVE_PRE, EPI_DROPOUT = 1, 2, 4, 8
@@ -94,8 +94,7 @@ class MvltSwinWmsa(C.Structure):
                 ("wqkv", vp), ("bqkv", vp), ("wproj", vp), ("bproj", vp),
                 ("bias_table", vp), ("scale", f32), ("rowscale", vp),
                 ("xn_win", vp), ("attn_out", vp), ("lse", vp), ("mean", vp), ("rstd", vp),
-                ("dy_win", vp), ("dqkv", vp), ("dxn_win", vp), ("dbias_table", vp), ("qkv_win", vp),
-                ("wproj_t", vp), ("wqkv_t", vp), ("head_split", i32), ("dbias_ws", vp)]
+                ("dy_win", vp), ("dqkv", vp), ("dxn_win", vp), ("qkv_win", vp), ("head_split", i32), ("dbias_ws", vp)]
 
 
 class MvltSwinDbiasItem(C.Structure):
@@ -226,10 +225,9 @@ SYMBOLS = {
     "mvlt_attn_bwd": (i32, [C.POINTER(MvltAttn), vp]),
     "mvlt_attn_bwd_ev": (i32, [C.POINTER(MvltAttn), vp, vp]),
     "mvlt_attn_route": (i32, [C.POINTER(MvltAttn), i32]),
+    "mvlt_swin_bwd_proj_supported": (i32, [i32, i32, i32, i32, i32]),
     "mvlt_swin_wmsa_supported": (i32, [i32, i32, i32]),
     "mvlt_swin_wmsa_fwd": (i32, [C.POINTER(MvltSwinWmsa), vp]),
-    "mvlt_swin_wmsa_bwd": (i32, [C.POINTER(MvltSwinWmsa), vp]),
-    "mvlt_swin_wmsa_bwd_supported": (i32, [i32, i32, i32]),
     "mvlt_swin_wmsa2_supported": (i32, [i32, i32, i32, i32, i32]),
     "mvlt_swin_wmsa2_sync_words": (i32, [i32, i32]),
     "mvlt_swin_wmsa2_fwd": (i32, [C.POINTER(MvltSwinWmsa), vp, vp]),

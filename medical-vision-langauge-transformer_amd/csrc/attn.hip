@@ -1652,6 +1652,17 @@ int route(const MvltAttn* p, bool bwd) {
 extern "C" int mvlt_attn_fwd(const MvltAttn* p, void* stream) { return run(p, false, stream); }
 extern "C" int mvlt_attn_bwd(const MvltAttn* p, void* stream) { return run(p, true, stream); }
 extern "C" int mvlt_attn_route(const MvltAttn* p, int bwd) { return route(p, bwd != 0); }
+extern "C" int mvlt_swin_bwd_proj_supported(int dtype, int nseq, int nH, int hd, int shift) {
+    // the Swin block's backward call with dout_weight set, asked of route(): the addresses only have to pass prepare()'s
+    // null and alignment checks, nothing dereferences them
+    alignas(16) static char ph[16];
+    MvltAttn p{};
+    p.dtype = dtype; p.mode = MVLT_ATTN_SWIN; p.nseq = nseq; p.L = 49; p.nH = nH; p.hd = hd;
+    p.qkv = ph; p.out = ph; p.dout = ph; p.dqkv = ph; p.dout_weight = ph;
+    p.lse = reinterpret_cast<float*>(ph); p.bias_table = p.lse; p.nW = 1; p.win_res = 7; p.shift = shift;
+    const int r = route(&p, true);
+    return r == MVLT_ATTN_ROUTE_SWIN_BWD_KS3 || r == MVLT_ATTN_ROUTE_SWIN_BWD_KS6 || r == MVLT_ATTN_ROUTE_SWIN_BWD_KS12;
+}
 extern "C" int mvlt_attn_bwd_ev(const MvltAttn* p, void* stream, void* event) {
     MVLT_CHECK(event, MVLT_ERR_ARG);
     t_stop_event = reinterpret_cast<hipEvent_t>(event);

@@ -405,7 +405,9 @@ Tensor bert_layer_bwd(const Tensor& dx, const std::vector<Tensor>& sv, const Ptr
 // ----------------------------------------------------------------------------------------------- Swin block
 // w: compute-dtype weights [wqkv, wproj, wfc1, wfc2]; f: f32 [n1g, n1b, bqkv, bproj, table, n2g, n2b, bfc1, bfc2];
 // g: f32 gradients [dn1g, dn1b, dwqkv, dbqkv, dwproj, dbproj, dtable, dn2g, dn2b, dwfc1, dbfc1, dwfc2, dbfc2]
-// geo: [B, H(res), C, nH, shift, fused (0 | 1 wmsa.hip | 2 wmsa2.hip), sync workspace of wmsa2]; maps: [w2n, n2w] int32 device pointers; s1/s2: DropPath scales f32 [B] or 0
+// geo: [B, H(res), C, nH, shift, mode, sync workspace of wmsa2 (forward)]; mode is what swin.py decided, forward: swin._wmsa_mode
+// (0 four launches | 1 wmsa.hip | 2 wmsa2.hip), backward: swin._bwd_mode (0 three launches | 1 projection dgrad inside the
+// attention backward | 2 mvlt_swin_wmsa2_bwd); maps: [w2n, n2w] int32 device pointers; s1/s2: DropPath scales f32 [B] or 0
 // plan: {} or {perm, inv, count} of mvlt_droppath_plan for s2 (int32 [rows], [rows], [1]): the Mlp branch then runs only on the
 // rows of the samples DropPath keeps.  norm2 writes xn2 in the plan's compact order (kept samples first), fc1 / fc2 stop at
 // `count` rows, fc2 scatters back through `perm` and lets the rows of the dropped samples through its epilogue on a zero
@@ -500,8 +502,7 @@ std::vector<Tensor> swin_block_bwd(const Tensor& dx2, const std::vector<Tensor>&
     const int64_t rows = x.size(0);
     const int Lt = res * res, nW = (res / 7) * (res / 7);
     const int dtype = dtype_of(x);
-    const int32_t* w2n = P<const int32_t>(maps[0]); const int32_t* n2w = P<const int32_t>(maps[1]);
-    (void)w2n;
+    const int32_t* n2w = P<const int32_t>(maps[1]);
     const bool compact = sv.size() >= 14;
     const int32_t *perm = nullptr, *inv = nullptr, *count = nullptr;
     if (compact) {
@@ -525,16 +526,13 @@ std::vector<Tensor> swin_block_bwd(const Tensor& dx2, const std::vector<Tensor>&
     Tensor dx1 = empty2(rows, C, x), dyw = empty2(rows, C, x);
     { LnBranch br; br.dz = dp(dyw); br.rowmap = n2w; if (s1) { br.rowscale = P<float>(s1); br.rps = Lt; }
       ln_bwd(dxn2, inv, x1, fp(stat2), fp(stat2) + rows, (int)rows, C, f[5], g[7], g[8], dp(dx2), dx1, br, st); }
-    // the output projection's dgrad rides inside the attention backward where the kernel takes it (MvltAttn.dout_weight: bf16,
-    // 3 / 6 / 12 heads of 32; MVLT_SWIN_BWD_PROJ=0: the separate product)
-    static const bool proj_in_attn = [] { const char* e = getenv("MVLT_SWIN_BWD_PROJ"); return !e || e[0] != '0'; }();
-    const bool fuse_proj = proj_in_attn && dtype == MVLT_BF16 && C == 32 * nH && (nH == 3 || nH == 6 || nH == 12) && (shift == 0 || shift == 3);
-    // one launch for projection dgrad + attention backward + qkv dgrad where the second design covers the shape
-    // (mvlt_swin_wmsa2_bwd: partial qkv-dgrad products per head group, summed by the LayerNorm backward below; MVLT_SWIN_BWD_ONE=0: off)
-    // MVLT_SWIN_BWD_ONE = smallest width that takes it (default 384: stage 2; 96 / 192: stages 0 / 1 too, measured slower there --
-    // a workgroup walks 4 / 2 units one after the other and every phase of a unit is latency-bound whatever the width)
-    static const int one_minc = [] { const char* e = getenv("MVLT_SWIN_BWD_ONE"); const int v = e ? atoi(e) : 384; return v <= 0 ? 1 << 30 : (v == 1 ? 96 : v); }();
-    const int nparts = (C >= one_minc && (shift == 0 || shift == 3)) ? mvlt_swin_wmsa2_bwd_parts(dtype, B, res, C, nH) : 0;
+    // geo[5] = swin._bwd_mode: 2 = one launch for projection dgrad + attention backward + qkv dgrad (mvlt_swin_wmsa2_bwd: partial
+    // qkv-dgrad products per head group, summed by the LayerNorm backward below), 1 = the projection's dgrad rides inside the
+    // attention backward (MvltAttn.dout_weight), 0 = the separate product
+    const int mode = (int)geo[5];
+    const int nparts = mode == 2 ? mvlt_swin_wmsa2_bwd_parts(dtype, B, res, C, nH) : 0;
+    TORCH_CHECK(mode >= 0 && mode <= 2 && (mode != 2 || nparts > 0), "swin_block_bwd: backward mode ", mode, " does not fit this block");
+    const bool fuse_proj = mode == 1;
     Tensor dao = dyw;
     if (!fuse_proj && !nparts) {
         dao = empty2(rows, C, x);

@@ -16,6 +16,7 @@ reverse and writes parameter gradients straight into the arena.
 """
 from __future__ import annotations
 
+import functools
 import math
 import os
 from typing import List, Optional
@@ -104,12 +105,10 @@ class PatchEmbed(nn.Module):
         self.norm = nn.LayerNorm(embed_dim)
 
 
-_FUSED_WMSA_BWD = False      # mvlt_swin_wmsa_bwd (one-launch backward of the first design) is parity-tested but 1.3-3.5x slower than the
-                             # three launches at B = 32: the tests switch it on through this attribute (Python host path)
 _FUSED_WMSA = os.environ.get("MVLT_FUSED_WMSA", "auto")     # "0" never, "1" wherever supported, "auto" where it wins
-_SWIN_BWD_ONE = int(os.environ.get("MVLT_SWIN_BWD_ONE", "384"))        # smallest width whose blocks take the one-launch backward (0: none; host.cpp reads it too)
+_SWIN_BWD_ONE = int(os.environ.get("MVLT_SWIN_BWD_ONE", "384"))        # smallest width whose blocks take the one-launch backward (0: none)
 _SWIN_BWD_ONE = (1 << 30) if _SWIN_BWD_ONE <= 0 else (96 if _SWIN_BWD_ONE == 1 else _SWIN_BWD_ONE)
-_SWIN_BWD_PROJ = os.environ.get("MVLT_SWIN_BWD_PROJ", "1") != "0"     # proj dgrad inside the attention backward (A/B switch; host.cpp reads it too)
+_SWIN_BWD_PROJ = os.environ.get("MVLT_SWIN_BWD_PROJ", "1") != "0"     # proj dgrad inside the attention backward (A/B switch)
 # Mlp branch of a stage-2 / 3 block only on the rows of the samples DropPath keeps (native host path, bf16, training): "0" = dense
 _DROP_COMPACT = os.environ.get("MVLT_SWIN_DROP_COMPACT", "1") != "0"
 _DROP_COMPACT_MIN_C = 384             # stages 0 / 1 (p <= 0.05, row-streaming products that refuse a device row count) stay dense
@@ -131,6 +130,23 @@ def _wmsa_mode(dtype, B, res, C, nH):
     if not ops.swin_wmsa_supported(dtype, C, nH):
         return 0
     return 1 if (_FUSED_WMSA == "1" or nwin >= 512 or (nwin >= 256 and C <= 256)) else 0
+
+
+def _bwd_mode(dtype, B, res, C, nH, shift):
+    """How the backward of a block's attention half runs, for both host paths (the native one takes it as geo[5]): 2 =
+    mvlt_swin_wmsa2_bwd (projection dgrad + attention backward + qkv dgrad in one launch), 1 = two launches (the projection
+    dgrad rides in the attention backward, MvltAttn.dout_weight), 0 = three.  Measured on MI355X at B = 32
+    (profiles/r6_swin_bwd_one_launch*, r6_swin_bwd_proj*): the one launch wins at stage 2 only, hence _SWIN_BWD_ONE = 384
+    (MVLT_SWIN_BWD_ONE=96: stages 0 / 1 too, 0: nowhere); MVLT_SWIN_BWD_PROJ=0 takes the projection dgrad out of the
+    attention backward (A/B measurements, parity tests).  What the kernels cover is asked of the library, never restated."""
+    return _bwd_mode_of(_SWIN_BWD_ONE, _SWIN_BWD_PROJ, dtype, B, res, C, nH, shift)
+
+
+@functools.lru_cache(maxsize=None)
+def _bwd_mode_of(one_minc, proj, dtype, B, res, C, nH, shift):          # (the switches are part of the key: tests change them)
+    if C >= one_minc and shift in (0, 3) and ops.swin_wmsa2_bwd_parts(dtype, B, res, C, nH) > 0:
+        return 2
+    return 1 if proj and ops.swin_bwd_proj_supported(dtype, B * (res // 7) ** 2, nH, C // nH, shift) else 0
 
 
 class _SwinFn(torch.autograd.Function):
@@ -441,7 +457,8 @@ class SwinTransformer(nn.Module):
         at, mlp = blk.attn, blk.mlp
         # the block that consumes dx0 takes dx0 * s2_next in ITS compact row order when it skipped its dropped samples
         plan_next = self._dp_plan_of(s2_next, B, H * W, blk.dim, dx2.dtype)
-        out = ops.host().swin_block_bwd(dx2, saved, w, f, gr, [B, H, blk.dim, blk.num_heads, blk.shift_size, 0],
+        mode = _bwd_mode(dx2.dtype, B, H, blk.dim, blk.num_heads, blk.shift_size)
+        out = ops.host().swin_block_bwd(dx2, saved, w, f, gr, [B, H, blk.dim, blk.num_heads, blk.shift_size, mode],
                                         [w2n.data_ptr(), n2w.data_ptr()], at.scale, 0 if s1 is None else s1.data_ptr(),
                                         0 if s2 is None else s2.data_ptr(), 0 if s2_next is None else s2_next.data_ptr(),
                                         dy2_pre if s2 is not None else None, ops.stream_int(), ops.side_int(dx2.device),
@@ -471,20 +488,14 @@ class SwinTransformer(nn.Module):
                                      branch=dict(rowmap=n2w, rowscale=(s1, Lt) if s1 is not None else None),
                                      defer=self.__dict__["_lnq"])
         dtab = g(at.relative_position_bias_table)          # zeroed for all blocks at once in _backward
-        if C >= _SWIN_BWD_ONE and blk.shift_size in (0, 3) and ops.swin_wmsa2_bwd_parts(dyw.dtype, B, H, C, nH):
+        mode = _bwd_mode(dyw.dtype, B, H, C, nH, blk.shift_size)
+        if mode == 2:
             # one launch, second design: dxn1w comes back as nH / 3 partial products that the LayerNorm backward below sums
             dqkv, dxn1w = ops.swin_wmsa2_bwd(dyw, qkv, lse, B, H, nH, blk.shift_size, ar.compute(at.proj.weight),
                                              ar.compute(at.qkv.weight), at.relative_position_bias_table.data, at.scale, dtab)
-        elif _FUSED_WMSA_BWD and ops.swin_wmsa_bwd_supported(dyw.dtype, C, nH):
-            # opt-in (MVLT_FUSED_WMSA_BWD=1, Python host path): proj dgrad + attention backward + qkv dgrad in one
-            # launch.  Correct, but slower than the three launches at B=32 (profiles/r2_wmsa_pmc.md), hence not default.
-            wpt = ar.compute(at.proj.weight).t().contiguous()
-            wqt = ar.compute(at.qkv.weight).t().contiguous()
-            dqkv, dxn1w = ops.swin_wmsa_bwd(dyw, qkv, lse, B, H, nH, blk.shift_size, wpt, wqt,
-                                            at.relative_position_bias_table.data, at.scale, dtab)
         else:
             wp = ar.compute(at.proj.weight)
-            if _SWIN_BWD_PROJ and ops.swin_bwd_proj_supported(dyw.dtype, nH, C // nH, blk.shift_size):
+            if mode == 1:
                 dao, wp = dyw, wp               # the projection's dgrad rides inside the attention backward (MvltAttn.dout_weight)
             else:
                 dao, wp = ops.gemm(dyw, wp, b_kmajor=True), None

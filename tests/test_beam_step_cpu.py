@@ -31,7 +31,7 @@ def test_abi_constants_agree_at_16():
     from mvlt_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "mvlt_hip.h")).read()
     macro = int(re.search(r"#define\s+MVLT_ABI_VERSION\s+(\d+)", hdr).group(1))
-    assert macro == _lib.ABI_VERSION == _lib.lib().mvlt_version() == 16
+    assert macro == _lib.ABI_VERSION == _lib.lib().mvlt_version() == 17
 
 
 def test_driver_on_a_hand_written_stream():

@@ -96,6 +96,58 @@ def test_cabi_version_and_struct_sizes_agree_everywhere():
     assert list(mod.struct_sizes()) == [ctypes.sizeof(s) for s in _lib.STRUCTS]
 
 
+def _swin_bwd_proj_route(L, _lib, dtype, nseq, nH, shift):
+    """mvlt_attn_route of the Swin attention backward with dout_weight set (placeholder addresses: the query only checks
+    that they are non-null and 16-byte aligned, nothing is launched or dereferenced)."""
+    p = _lib.MvltAttn()
+    p.dtype, p.mode, p.nseq, p.L, p.nH, p.hd = dtype, _lib.ATTN_SWIN, nseq, 49, nH, 32
+    p.qkv = p.out = p.lse = p.bias_table = p.dout = p.dqkv = p.dout_weight = 4096
+    p.nW, p.win_res, p.shift = 1, 7, shift
+    return _lib.ATTN_ROUTES[L.mvlt_attn_route(ctypes.byref(p), 1)]
+
+
+def test_swin_bwd_proj_supported_is_what_the_attention_dispatch_answers():
+    """mvlt_swin_bwd_proj_supported == "mvlt_attn_bwd with dout_weight takes swin_attn_bwd2_kernel<KS3 / 6 / 12>", over both
+    dtypes, every head count of Swin-S / Swin-B and shifts the kernel does and does not take, and on both sides of the
+    buffer-store range bound (nseq * nH * 9408 bytes of dqkv < 2^31: bf16, 12 heads, 19021 windows fit, 19022 do not)."""
+    from mvlt_amd import _lib
+    L = _lib.lib()
+    ks = {"SWIN_BWD_KS3", "SWIN_BWD_KS6", "SWIN_BWD_KS12"}
+    for dtype in (_lib.F32, _lib.BF16):
+        for nH in (3, 4, 6, 12, 24):
+            for shift in (0, 2, 3):
+                got = L.mvlt_swin_bwd_proj_supported(dtype, 128, nH, 32, shift)
+                assert got == int(_swin_bwd_proj_route(L, _lib, dtype, 128, nH, shift) in ks), (dtype, nH, shift)
+                assert got == int(dtype == _lib.BF16 and nH in (3, 6, 12) and shift in (0, 3)), (dtype, nH, shift)
+    for nseq, want in ((19021, 1), (19022, 0)):
+        assert L.mvlt_swin_bwd_proj_supported(_lib.BF16, nseq, 12, 32, 0) == want
+        assert _swin_bwd_proj_route(L, _lib, _lib.BF16, nseq, 12, 0) == ("SWIN_BWD_KS12" if want else "UNSUPPORTED")
+
+
+def test_swin_bwd_mode_is_a_pure_function_of_the_shape_and_the_two_switches(monkeypatch):
+    """swin._bwd_mode (2 = mvlt_swin_wmsa2_bwd, 1 = projection dgrad inside the attention backward, 0 = three launches) at the
+    four stage shapes of Swin-S, B = 32; a change of either switch is seen at once."""
+    from mvlt_amd import swin
+    BF16, F32 = torch.bfloat16, torch.float32
+    stages = [(56, 96, 3), (28, 192, 6), (14, 384, 12), (7, 768, 24)]
+    modes = lambda dt, shift: [swin._bwd_mode(dt, 32, res, C, nH, shift) for res, C, nH in stages]
+    monkeypatch.setattr(swin, "_SWIN_BWD_ONE", 384)
+    monkeypatch.setattr(swin, "_SWIN_BWD_PROJ", True)
+    for shift in (0, 3):
+        assert modes(BF16, shift) == [1, 1, 2, 0]
+        assert modes(F32, shift) == [0, 0, 0, 0]
+    assert modes(BF16, 2) == [0, 0, 0, 0]
+    assert swin._bwd_mode(BF16, 1, 7, 384, 12, 0) == 1            # one window: the one launch pairs windows, the projection still rides
+    monkeypatch.setattr(swin, "_SWIN_BWD_ONE", 96)
+    for shift in (0, 3):
+        assert modes(BF16, shift) == [2, 2, 2, 0]
+        assert modes(F32, shift) == [0, 0, 0, 0]
+    monkeypatch.setattr(swin, "_SWIN_BWD_ONE", 1 << 30)
+    monkeypatch.setattr(swin, "_SWIN_BWD_PROJ", False)
+    for shift in (0, 3):
+        assert modes(BF16, shift) == [0, 0, 0, 0]
+
+
 def _integration_example():
     md = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     block = md.split("<!-- cabi-example-begin")[1].split("<!-- cabi-example-end -->")[0]

@@ -109,7 +109,7 @@ def test_logit_rules_struct_bookkeeping():
     from mvlt_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "mvlt_hip.h")).read()
     assert re.search(r"MVLT_STRUCT_LOGIT_RULES = 20, MVLT_STRUCT_COUNT = 21", hdr)
-    assert int(re.search(r"#define\s+MVLT_ABI_VERSION\s+(\d+)", hdr).group(1)) == 16 == _lib.ABI_VERSION
+    assert int(re.search(r"#define\s+MVLT_ABI_VERSION\s+(\d+)", hdr).group(1)) == 17 == _lib.ABI_VERSION
     assert _lib.STRUCTS[20] is _lib.MvltLogitRules and len(_lib.STRUCTS) == 21
     assert _lib.lib().mvlt_sizeof(20) == ctypes.sizeof(_lib.MvltLogitRules) == 80
     fields = re.search(r"typedef struct MvltLogitRules \{(.*?)\} MvltLogitRules;", hdr, re.S).group(1)

@@ -207,16 +207,15 @@ def test_tiny_train_mode_matches_oracle_with_same_masks(M, specs):
     assert worst < 1e-2, worst
 
 
-def test_fused_wmsa_backward_in_the_model(M, specs, monkeypatch):
-    """mvlt_swin_wmsa_bwd inside the Swin backward pass (opt-in, Python host path) gives the gradients of the default
-    three-launch sequence: every parameter of the tiny model, f32."""
+def test_swin_backward_is_the_same_on_both_host_paths(M, specs, monkeypatch):
+    """The Swin-S widths (96 / 192 / 384 / 768) through the native and the Python host path: same loss, same gradient of
+    every parameter, f32."""
     from mvlt_amd import ops, swin
     image, ids, labels, itm = synth_batch(3, 24, seed=41, vocab=3000)
     monkeypatch.setattr(random, "random", lambda: 0.9)
     runs = []
-    for fused in (False, True):
-        monkeypatch.setattr(ops, "NATIVE", not fused)
-        monkeypatch.setattr(swin, "_FUSED_WMSA_BWD", fused)
+    for native in (True, False):
+        monkeypatch.setattr(ops, "NATIVE", native)
         monkeypatch.setattr(swin, "_FUSED_WMSA", "1")
         cfg = M.MVLBertPretrainConfig(hidden_size=768, num_hidden_layers=2, num_attention_heads=12, intermediate_size=1024,
                                       vocab_size=3000)
@@ -233,6 +232,59 @@ def test_fused_wmsa_backward_in_the_model(M, specs, monkeypatch):
     assert abs(l0 - l1) < 1e-6 * abs(l0)
     bad = [(k, rel_err(g1[k], g0[k])) for k in g0 if rel_err(g1[k], g0[k]) > 2e-4 and g0[k].abs().max() > 1e-9 and not k.endswith("key.bias")]
     assert g0.keys() == g1.keys() and not bad, bad[:10]
+
+
+def _swin_s_widths_run(M, cd):
+    """(loss, {name: f64 gradient}) of the model and batch of test_swin_backward_is_the_same_on_both_host_paths in `cd`."""
+    image, ids, labels, itm = synth_batch(3, 24, seed=41, vocab=3000)
+    cfg = M.MVLBertPretrainConfig(hidden_size=768, num_hidden_layers=2, num_attention_heads=12, intermediate_size=1024,
+                                  vocab_size=3000)
+    cfg.ITM_task = True
+    cfg.swin.update(embed_dim=96, num_heads=[3, 6, 12, 24], depths=[2, 2, 2, 2], drop_path_rate=0.2)
+    torch.manual_seed(17)
+    model = M.set_compute_dtype(M.MVLBertForPretraining(cfg).cuda().eval(), cd)
+    random.random = lambda: 0.9
+    try:
+        loss = model(image.cuda(), ids.cuda(), labels.cuda(), itm.cuda())
+    finally:
+        random.random = _ORIG_RANDOM_RANDOM
+    loss.backward()
+    torch.cuda.synchronize()
+    return loss.item(), {k: p.grad.double().clone() for k, p in model.named_parameters() if p.grad is not None}
+
+
+@pytest.fixture(scope="module")
+def swin_s_widths_f32(M):
+    return _swin_s_widths_run(M, F32)
+
+
+# (swin._SWIN_BWD_ONE, swin._SWIN_BWD_PROJ) -> swin._bwd_mode at stages 0 / 1 / 2; stage 3 (24 heads) is 0 whatever they say
+SWIN_BWD_SWITCHES = {"default": (384, True, (1, 1, 2)), "one_launch_everywhere": (96, True, (2, 2, 2)),
+                     "proj_in_attn": (1 << 30, True, (1, 1, 1)), "three_launches": (1 << 30, False, (0, 0, 0))}
+
+
+@pytest.mark.parametrize("native", [True, False], ids=["native", "python"])
+@pytest.mark.parametrize("switches", list(SWIN_BWD_SWITCHES))
+def test_swin_backward_routes_in_the_model(M, swin_s_widths_f32, monkeypatch, switches, native):
+    """Every backward route of a Swin block's attention half (swin._bwd_mode 0 / 1 / 2) on both host paths, bf16 against the
+    exact-f32 path of the same model: the bounds of test_bf16_gradients_match_f32_path (loss 1e-3, whole gradient 3e-2).
+    B = 3 gives stages 0 / 1 / 2 an even window count (192 / 48 / 12), so the one launch is admissible at all three."""
+    from mvlt_amd import ops, swin
+    one_minc, proj, want = SWIN_BWD_SWITCHES[switches]
+    monkeypatch.setattr(ops, "NATIVE", native)
+    monkeypatch.setattr(swin, "_SWIN_BWD_ONE", one_minc)
+    monkeypatch.setattr(swin, "_SWIN_BWD_PROJ", proj)
+    for (res, C, nH), mode in zip([(56, 96, 3), (28, 192, 6), (14, 384, 12)], want):
+        for shift in (0, 3):
+            assert swin._bwd_mode(BF16, 3, res, C, nH, shift) == mode, (res, C, nH, shift)
+    assert swin._bwd_mode(BF16, 3, 7, 768, 24, 0) == 0
+    l32, g32 = swin_s_widths_f32
+    l16, g16 = _swin_s_widths_run(M, BF16)
+    assert abs(l16 - l32) < 1e-3 * abs(l32), (l16, l32)
+    assert g16.keys() == g32.keys()
+    num = sum(float((g16[k] - g32[k]).pow(2).sum()) for k in g32)
+    den = sum(float(g32[k].pow(2).sum()) for k in g32)
+    assert (num / den) ** 0.5 < 3e-2, (num / den) ** 0.5
 
 
 # ------------------------------------------------------------------ full-size models
