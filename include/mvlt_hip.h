@@ -280,6 +280,28 @@ typedef struct MvltBeamCand {
     float* lse;                         /* [M] or NULL */
 } MvltBeamCand;
 int mvlt_gemm_beam_candidates(const MvltGemm* p, const MvltBeamCand* c, void* stream);
+/* The logit rules in beam search (HF 4.16 beam_search: the processors act on the LOG-PROBABILITIES, before the beam score is
+ * added -- not on the raw logits, where the six picks above apply them).  Row m = g * num_beams + b is one live hypothesis; c = *col
+ * tokens generated so far, the same for every row; h = the hypothesis' own c tokens after the beam reorder of the previous token
+ * (no [MASK] placeholder; empty at step 0).  All in f32 with no fused multiply-add:
+ *   x, lse_m   as in mvlt_gemm_beam_candidates, lse over ALL N columns of the unprocessed row
+ *   lp = x - lse_m;  seen(n): lp' = lp < 0 ? lp * penalty : lp / penalty (once, however often n occurs);  s = lp' + beam_scores[m]
+ *   banned(n)  the n-gram rule and the min-length rule exactly as worded for MvltLogitRules above
+ * Per sample g: the n_cand largest s over its UNBANNED entries, sorted descending, ties by the lower flat index beam * N + n.  A
+ * banned entry is never returned and changes nothing else (it stays inside lse).  With no bit set and penalty 1 the lists are
+ * those of mvlt_gemm_beam_candidates bit for bit.  A sample with fewer than n_cand unbanned entries gets (-inf, beam 0, token 0)
+ * in the remaining slots; nothing is read or written out of bounds.  Integer comparisons only, no float atomics: the same
+ * operands give the same lists run to run.
+ * mvlt_beam_rules_plan is the PLAN of mvlt_decode_rules_plan over int32 histories seq[m, 0 .. *rules->col - 1], row stride ld_seq
+ * (the layout of MvltBeamStep.seq; *col is clamped into [0, ld_seq]), one workgroup per row, ANY rows >= 1; rules->ids and ld_ids
+ * are ignored.  Stateless like that plan (clear, then set).  Refusals (MVLT_ERR_ARG, nothing launched, nothing written): those of
+ * mvlt_decode_rules_plan without its 64 rows and its ids / ld_ids, and seq NULL, ld_seq < 1.
+ * mvlt_gemm_beam_candidates_rules: the plain product (in row chunks of 64), then the rule-aware selection, which reads
+ * seen / banned / ld_words / penalty only ([M, ld_words] bitmaps; the caller runs the plan first, on the same stream).  Refusals
+ * (nothing launched, nothing written): those of the _rules heads above without their M <= 64 (M = G * num_beams, any size),
+ * ahead of those of mvlt_gemm_beam_candidates. */
+int mvlt_beam_rules_plan(const MvltLogitRules* rules, const int32_t* seq, int64_t ld_seq, int rows, int V, void* stream);
+int mvlt_gemm_beam_candidates_rules(const MvltGemm* p, const MvltBeamCand* c, const MvltLogitRules* rules, void* stream);
 /* MLM decoder product with the forward of F.cross_entropy(ignore_index = -100) in its epilogue (csrc/headce.hip): the training
  * loss and per-token log-probabilities without a pass over stored logits, and with C == NULL without any logits at all.
  * p: A = the transformed hidden rows [M, K], B = W [N = V, K] (torch-Linear layout), bias f32 [V] (MVLT_EPI_BIAS, the only epilogue

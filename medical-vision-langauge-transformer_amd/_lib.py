@@ -206,6 +206,8 @@ SYMBOLS = {
     "mvlt_gemm_sample_filtered_step_rules": (i32, [C.POINTER(MvltGemm), vp, vp, C.POINTER(MvltSampleFilter), C.POINTER(MvltSampleState),
                                                  C.POINTER(MvltLogitRules), vp]),
     "mvlt_gemm_beam_candidates": (i32, [C.POINTER(MvltGemm), C.POINTER(MvltBeamCand), vp]),
+    "mvlt_beam_rules_plan": (i32, [C.POINTER(MvltLogitRules), vp, i64, i32, i32, vp]),
+    "mvlt_gemm_beam_candidates_rules": (i32, [C.POINTER(MvltGemm), C.POINTER(MvltBeamCand), C.POINTER(MvltLogitRules), vp]),
     "mvlt_mlm_head_ce": (i32, [C.POINTER(MvltGemm), C.POINTER(MvltHeadCE), vp]),
     "mvlt_mlm_head_ce_workspace_bytes": (sz, [i32, i32]),
     "mvlt_retrieval_head_supported": (i32, [i32, i32]),

@@ -3,8 +3,10 @@
 // mvlt_gemm_argmax_greedy), sampled (mvlt_gemm_sample, mvlt_gemm_sample_step) and sampled behind a top-k / top-p filter
 // (mvlt_gemm_sample_filtered, mvlt_gemm_sample_filtered_step) -- and the candidate step of beam search
 // (mvlt_gemm_beam_candidates: log-softmax + beam score + top-n per sample).  The six picks also come with the logit rules of
-// constrained decoding in their epilogues (mvlt_gemm_*_rules, fed by mvlt_decode_rules_plan).  No LDS staging in the products: the weight matrix is
-// read once and nothing is reused inside a workgroup, so every wave loads its MFMA fragments straight from global memory.
+// constrained decoding in their epilogues (mvlt_gemm_*_rules, fed by mvlt_decode_rules_plan); the beam candidates apply them to the
+// log-probabilities in their selection (mvlt_gemm_beam_candidates_rules, fed by mvlt_beam_rules_plan).  No LDS staging in the
+// products: the weight matrix is read once and nothing is reused inside a workgroup, so every wave loads its MFMA fragments
+// straight from global memory.
 // Same argument block as the tile kernels of gemm.hip (gemm_dev.h); gemm.hip reaches the plain product through mvlt_skinny_try.
 #include "common.h"
 #include "gemm_dev.h"
@@ -233,31 +235,45 @@ MVLT_DEV float rules_penalise(const float x, const float penalty) { return x < 0
 // the pick kernels read it.  Stateless: both maps are cleared and set again every call (global atomicOr; a workgroup touches only
 // its own row), so a replayed graph carries nothing from token to token.  The n-gram rule is a scan over the start i of every
 // earlier g-gram, one thread per i: h[i .. i+g-2] == the last g-1 tokens bans h[i+g-1].  ids outside [0, V) set no bit.
+// The body is one template over the history's integer type: int64 ids of the greedy loops, int32 live sequences of beam search
+// (mvlt_beam_rules_plan: row m = one hypothesis, h = MvltBeamStep.seq[m, 0 .. c-1], any number of rows).
+template <typename I>
+MVLT_DEV void rules_plan_row(uint32_t* seen, uint32_t* banned, const I* h, const long ld, const int64_t* col, const int g, const int min_length,
+                             const int64_t eos, const int has_eos, const int V) {
+    const int tid = threadIdx.x, nw = (V + 31) >> 5;
+    const long c64 = col[0];
+    const int c = (int)(c64 < 0 ? 0 : (c64 > ld ? ld : c64));          // never past the row of ids
+    for (int w = tid; w < nw; w += 256) { seen[w] = 0u; banned[w] = 0u; }
+    __syncthreads();
+    for (int i = tid; i < c; i += 256) {
+        const I t = h[i];
+        if (t >= 0 && t < V) atomicOr(seen + (t >> 5), 1u << (t & 31));
+        if (g >= 1 && i + g <= c) {          // the g-gram starting at i ends before column c
+            bool same = true;
+            for (int j = 0; j < g - 1; ++j) same = same && h[i + j] == h[c - g + 1 + j];
+            const I b = h[i + g - 1];
+            if (same && b >= 0 && b < V) atomicOr(banned + (b >> 5), 1u << (b & 31));
+        }
+    }
+    if (tid == 0 && has_eos && c64 < min_length && eos >= 0 && eos < V) atomicOr(banned + (eos >> 5), 1u << (eos & 31));
+}
 struct RulesPlan {
     uint32_t* seen; uint32_t* banned; long ld_words; const int64_t* ids; long ld_ids; const int64_t* col;
     int ngram, min_length; int64_t eos; int has_eos, V;
 };
 __global__ __launch_bounds__(256) void decode_rules_plan_kernel(const RulesPlan f) {
-    const int m = blockIdx.x, tid = threadIdx.x, nw = (f.V + 31) >> 5;
-    uint32_t* seen = f.seen + (long)m * f.ld_words;
-    uint32_t* banned = f.banned + (long)m * f.ld_words;
-    const int64_t* h = f.ids + (long)m * f.ld_ids;
-    const long c64 = f.col[0];
-    const int c = (int)(c64 < 0 ? 0 : (c64 > f.ld_ids ? f.ld_ids : c64));          // never past the row of ids
-    for (int w = tid; w < nw; w += 256) { seen[w] = 0u; banned[w] = 0u; }
-    __syncthreads();
-    const int g = f.ngram;
-    for (int i = tid; i < c; i += 256) {
-        const int64_t t = h[i];
-        if (t >= 0 && t < f.V) atomicOr(seen + (t >> 5), 1u << (t & 31));
-        if (g >= 1 && i + g <= c) {          // the g-gram starting at i ends before column c
-            bool same = true;
-            for (int j = 0; j < g - 1; ++j) same = same && h[i + j] == h[c - g + 1 + j];
-            const int64_t b = h[i + g - 1];
-            if (same && b >= 0 && b < f.V) atomicOr(banned + (b >> 5), 1u << (b & 31));
-        }
-    }
-    if (tid == 0 && f.has_eos && c64 < f.min_length && f.eos >= 0 && f.eos < f.V) atomicOr(banned + (f.eos >> 5), 1u << (f.eos & 31));
+    const int m = blockIdx.x;
+    rules_plan_row(f.seen + (long)m * f.ld_words, f.banned + (long)m * f.ld_words, f.ids + (long)m * f.ld_ids, f.ld_ids, f.col, f.ngram,
+                   f.min_length, f.eos, f.has_eos, f.V);
+}
+struct BeamRulesPlan {
+    uint32_t* seen; uint32_t* banned; long ld_words; const int32_t* seq; long ld_seq; const int64_t* col;
+    int ngram, min_length; int64_t eos; int has_eos, V;
+};
+__global__ __launch_bounds__(256) void beam_rules_plan_kernel(const BeamRulesPlan f) {
+    const int m = blockIdx.x;
+    rules_plan_row(f.seen + (long)m * f.ld_words, f.banned + (long)m * f.ld_words, f.seq + (long)m * f.ld_seq, f.ld_seq, f.col, f.ngram,
+                   f.min_length, f.eos, f.has_eos, f.V);
 }
 
 // Decoder GEMM of the last-row MLM head fused with the greedy pick, wide form (round 5): a workgroup = 128 vocabulary columns,
@@ -784,6 +800,13 @@ __global__ __launch_bounds__(FILT_THREADS) void sample_filter_pick_kernel(const 
 // winner" over the rows instead -- slow, exact, the same answer.
 // A workgroup per sample leaves most of the chip idle at small G (measured: profiles/beam_fused.md); splitting a sample over
 // several workgroups needs a second launch for the merge and was not built.
+// With LOGIT RULES (a trailing RulesDev in the pack R, as in the head kernels: the instantiation without one keeps the argument list
+// and the code it had) the processors act where HF 4.16 beam_search puts them, on lp = x - lse ahead of the beam score: a seen entry
+// is penalised once (rules_penalise on lp), a banned entry enters nothing but lse -- not tau, not the list, not the slow rounds.
+// The thread maxima of the processed scores come from two more maxima per beam in pass 1 -- over the thread's unbanned unseen and
+// over its unbanned seen columns: the penalty is monotone inside a class, not across them, and a banned maximum must not decide
+// tau -- so the rows are still read three times; a thread without an unbanned entry holds 0.  Fewer than n_cand unbanned entries in the sample: tau = 0
+// lists them all and the remaining slots are filled with (-inf, 0, 0).
 constexpr int BEAM_THREADS = 1024, BEAM_MAXB = 8, BEAM_MAXC = 16, BEAM_LIST = 1024;
 struct BeamIn {
     const float* x; long ldx; const float* beam_scores; int num_beams, n_cand, N;
@@ -792,13 +815,26 @@ struct BeamIn {
 MVLT_DEV unsigned long long beam_word(float x, float lse, float bs, uint32_t flat) {
     return ((unsigned long long)filt_key(__fadd_rn(__fadd_rn(x, -lse), bs)) << 32) | (unsigned long long)(0xFFFFFFFFu - flat);
 }
+// the rule-aware word of an unbanned entry: HF's beam_search hands its processors the log-probability, so the penalty acts on
+// lp = x - lse (lse over ALL columns, unprocessed) and the beam score is added behind it
+MVLT_DEV unsigned long long beam_word_seen(float x, float lse, float bs, uint32_t flat, bool seen, float penalty) {
+    float lp = __fadd_rn(x, -lse);
+    if (seen) lp = rules_penalise(lp, penalty);
+    return ((unsigned long long)filt_key(__fadd_rn(lp, bs)) << 32) | (unsigned long long)(0xFFFFFFFFu - flat);
+}
+// a slot no unbanned entry is left for (fewer than n_cand of them in the sample): (-inf, beam 0, token 0)
+MVLT_DEV void beam_emit_none(const BeamIn& f, const long o) {
+    f.cand_score[o] = -__builtin_inff(); f.cand_beam[o] = 0; f.cand_tok[o] = 0;
+}
 MVLT_DEV void beam_emit(const BeamIn& f, const long o, const unsigned long long w) {
     const uint32_t key = (uint32_t)(w >> 32), flat = 0xFFFFFFFFu - (uint32_t)w;
     f.cand_score[o] = __uint_as_float(key ^ ((key >> 31) ? 0x80000000u : 0xFFFFFFFFu));
     f.cand_beam[o] = (int32_t)(flat / (uint32_t)f.N);
     f.cand_tok[o] = (int32_t)(flat % (uint32_t)f.N);
 }
-__global__ __launch_bounds__(BEAM_THREADS) void beam_candidates_kernel(const BeamIn f) {
+template <typename... R>
+__global__ __launch_bounds__(BEAM_THREADS) void beam_candidates_kernel(const BeamIn f, const R... rules) {
+    constexpr bool RULES = sizeof...(R) > 0;
     __shared__ float s_f[BEAM_MAXB][16];
     __shared__ float s_lse[BEAM_MAXB], s_bs[BEAM_MAXB];
     __shared__ uint32_t s_tmax[BEAM_THREADS];
@@ -809,12 +845,30 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_candidates_kernel(const Bea
     const float* x0 = f.x + (long)g * nb * f.ldx;
     // ---- 1: thread and row maxima
     float tmax[BEAM_MAXB], rmax[BEAM_MAXB];
+    // RULES: per thread and beam also the largest x among its unbanned UNSEEN and among its unbanned SEEN columns (-inf: none).
+    // x -> lp -> penalised lp -> s is monotone inside either class, so the largest processed s of a class is that of its largest x
+    [[maybe_unused]] float umax[BEAM_MAXB], smax[BEAM_MAXB];
 #pragma unroll
     for (int b = 0; b < BEAM_MAXB; ++b) {
         tmax[b] = -3.0e38f;
+        if constexpr (RULES) { umax[b] = -__builtin_inff(); smax[b] = -__builtin_inff(); }
         if (b < nb) {
             const float* x = x0 + (long)b * f.ldx;
-            for (int n = tid; n < N; n += BEAM_THREADS) tmax[b] = fmaxf(tmax[b], x[n]);
+            if constexpr (RULES) {
+                const RulesDev& rd = rules_arg(rules...);
+                const long w0 = ((long)g * nb + b) * rd.ld_words;
+                for (int n = tid; n < N; n += BEAM_THREADS) {
+                    const float v = x[n];
+                    const uint32_t bit = 1u << (n & 31), bw = rd.banned[w0 + (n >> 5)], sw = rd.seen[w0 + (n >> 5)];
+                    tmax[b] = fmaxf(tmax[b], v);          // the row maximum and lse are those of the unprocessed row
+                    if (!(bw & bit)) {
+                        if (sw & bit) smax[b] = fmaxf(smax[b], v);
+                        else umax[b] = fmaxf(umax[b], v);
+                    }
+                }
+            } else {
+                for (int n = tid; n < N; n += BEAM_THREADS) tmax[b] = fmaxf(tmax[b], x[n]);
+            }
             const float wm = wave_max(tmax[b]);
             if (lane == 0) s_f[b][wave] = wm;
         }
@@ -860,7 +914,20 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_candidates_kernel(const Bea
     __syncthreads();
     // ---- tau: the n_cand-th largest of the thread maxima (threads without a column hold 0, below every key)
     uint32_t mine = 0u;
-    if (tid < N) {
+    if constexpr (RULES) {
+        // the penalty breaks "largest s = s of the largest x" across the two classes and a banned entry may decide nothing: the
+        // largest PROCESSED key of the thread's unbanned entries, from the two class maxima of pass 1 (a thread without an
+        // unbanned entry holds 0, below every key; with fewer than n_cand threads above 0, tau = 0 admits every unbanned entry)
+        const float penalty = rules_arg(rules...).penalty;
+#pragma unroll
+        for (int b = 0; b < BEAM_MAXB; ++b) {
+            if (b < nb) {
+                const float lse = s_lse[b], bs = s_bs[b];
+                if (umax[b] > -__builtin_inff()) mine = max(mine, (uint32_t)(beam_word_seen(umax[b], lse, bs, 0u, false, penalty) >> 32));
+                if (smax[b] > -__builtin_inff()) mine = max(mine, (uint32_t)(beam_word_seen(smax[b], lse, bs, 0u, true, penalty) >> 32));
+            }
+        }
+    } else if (tid < N) {
 #pragma unroll
         for (int b = 0; b < BEAM_MAXB; ++b)
             if (b < nb) mine = max(mine, filt_key(__fadd_rn(__fadd_rn(tmax[b], -s_lse[b]), s_bs[b])));
@@ -884,7 +951,16 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_candidates_kernel(const Bea
             const float* x = x0 + (long)b * f.ldx;
             const float lse = s_lse[b], bs = s_bs[b];
             for (int n = tid; n < N; n += BEAM_THREADS) {
-                const unsigned long long w = beam_word(x[n], lse, bs, (uint32_t)b * (uint32_t)N + (uint32_t)n);
+                unsigned long long w;
+                if constexpr (RULES) {
+                    const RulesDev& rd = rules_arg(rules...);
+                    const long wi = ((long)g * nb + b) * rd.ld_words + (n >> 5);
+                    const uint32_t bit = 1u << (n & 31);
+                    if (rd.banned[wi] & bit) continue;          // a banned entry never enters the list
+                    w = beam_word_seen(x[n], lse, bs, (uint32_t)b * (uint32_t)N + (uint32_t)n, (rd.seen[wi] & bit) != 0u, rd.penalty);
+                } else {
+                    w = beam_word(x[n], lse, bs, (uint32_t)b * (uint32_t)N + (uint32_t)n);
+                }
                 if ((uint32_t)(w >> 32) >= tau) {
                     const int pos = atomicAdd(&s_count, 1);
                     if (pos < BEAM_LIST) s_list[pos] = w;
@@ -902,6 +978,9 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_candidates_kernel(const Bea
             for (int j = 0; j < count; ++j) rank += s_list[j] > w ? 1 : 0;
             if (rank < f.n_cand) beam_emit(f, out0 + rank, w);
         }
+        if constexpr (RULES) {          // fewer unbanned entries than n_cand (tau = 0 listed them all): the rest of the list is empty
+            if (tid >= count && tid < f.n_cand) beam_emit_none(f, out0 + tid);
+        }
         return;
     }
     unsigned long long prev = ~0ull;
@@ -913,7 +992,16 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_candidates_kernel(const Bea
                 const float* x = x0 + (long)b * f.ldx;
                 const float lse = s_lse[b], bs = s_bs[b];
                 for (int n = tid; n < N; n += BEAM_THREADS) {
-                    const unsigned long long w = beam_word(x[n], lse, bs, (uint32_t)b * (uint32_t)N + (uint32_t)n);
+                    unsigned long long w;
+                    if constexpr (RULES) {
+                        const RulesDev& rd = rules_arg(rules...);
+                        const long wi = ((long)g * nb + b) * rd.ld_words + (n >> 5);
+                        const uint32_t bit = 1u << (n & 31);
+                        if (rd.banned[wi] & bit) continue;
+                        w = beam_word_seen(x[n], lse, bs, (uint32_t)b * (uint32_t)N + (uint32_t)n, (rd.seen[wi] & bit) != 0u, rd.penalty);
+                    } else {
+                        w = beam_word(x[n], lse, bs, (uint32_t)b * (uint32_t)N + (uint32_t)n);
+                    }
                     if (w < prev && w > best) best = w;
                 }
             }
@@ -927,7 +1015,11 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_candidates_kernel(const Bea
         __syncthreads();
         best = s_w[0];
         for (int w = 1; w < 16; ++w) if (s_w[w] > best) best = s_w[w];
-        if (tid == 0) beam_emit(f, out0 + c, best);
+        if constexpr (RULES) {          // no unbanned entry below the previous winner: this slot and every later one stay empty
+            if (tid == 0) { if (best != 0ull) beam_emit(f, out0 + c, best); else beam_emit_none(f, out0 + c); }
+        } else {
+            if (tid == 0) beam_emit(f, out0 + c, best);
+        }
         prev = best;
         __syncthreads();          // (s_w is written again by the next round)
     }
@@ -1019,9 +1111,10 @@ template <typename S> int greedy_state(const S* g, GreedyState& st) {
     return MVLT_OK;
 }
 
-// MvltLogitRules -> what the rule-aware heads read, for a product of M rows and N columns (the refusals of mvlt_hip.h)
-int rules_dev(const MvltLogitRules* r, const int M, const int N, RulesDev& rd) {
-    MVLT_CHECK(r && r->seen && r->banned && M >= 1 && M <= 64 && N >= 1, MVLT_ERR_ARG);
+// MvltLogitRules -> what the rule-aware heads read, for a product of M rows and N columns (the refusals of mvlt_hip.h);
+// max_rows: 64 for the six picks (one tile of rows), none for the beam candidates, whose product goes in row chunks
+int rules_dev(const MvltLogitRules* r, const int M, const int N, RulesDev& rd, const int max_rows = 64) {
+    MVLT_CHECK(r && r->seen && r->banned && M >= 1 && M <= max_rows && N >= 1, MVLT_ERR_ARG);
     MVLT_CHECK(r->ld_words >= (long)ceil_div(N, 32) && r->penalty > 0.f && r->ngram >= 0, MVLT_ERR_ARG);          // (a NaN penalty fails > 0)
     rd = RulesDev{r->seen, r->banned, (long)r->ld_words, r->penalty};
     return MVLT_OK;
@@ -1213,9 +1306,11 @@ extern "C" int mvlt_gemm_sample_filtered_step_rules(const MvltGemm* p, float* pa
     return filtered_step_entry(p, part_val, part_idx, filter, g, &rd, stream);
 }
 
-// The beam candidates: the product in row chunks of <= 64 into the one workspace, then the selection.  Every chunk is checked
+// The beam candidates: the product in row chunks of <= 64 into the one workspace, then the selection (`r` = the checked rules of
+// the _rules form: the product stays the plain one, the selection is the rule-aware instantiation).  Every chunk is checked
 // before the first launch: a refused call launches nothing.
-extern "C" int mvlt_gemm_beam_candidates(const MvltGemm* p, const MvltBeamCand* c, void* stream) {
+namespace {
+int beam_candidates_entry(const MvltGemm* p, const MvltBeamCand* c, const RulesDev* r, void* stream) {
     MVLT_CHECK(p && c && p->A && p->B && c->beam_scores && c->x && c->cand_score && c->cand_beam && c->cand_tok, MVLT_ERR_ARG);
     MVLT_CHECK(p->M > 0 && p->N > 0 && p->K > 0 && p->lda > 0 && p->ldb > 0, MVLT_ERR_ARG);
     MVLT_CHECK(c->num_beams >= 1 && c->n_cand >= 1 && p->M % c->num_beams == 0 && c->ldx >= p->N, MVLT_ERR_ARG);
@@ -1242,7 +1337,28 @@ extern "C" int mvlt_gemm_beam_candidates(const MvltGemm* p, const MvltBeamCand* 
     });
     if (rc != MVLT_OK) return rc;
     const BeamIn bi{c->x, (long)c->ldx, c->beam_scores, c->num_beams, c->n_cand, p->N, c->cand_score, c->cand_beam, c->cand_tok, c->lse};
-    hipLaunchKernelGGL(beam_candidates_kernel, dim3(p->M / c->num_beams), dim3(BEAM_THREADS), 0, s, bi);
+    if (r) hipLaunchKernelGGL(beam_candidates_kernel<RulesDev>, dim3(p->M / c->num_beams), dim3(BEAM_THREADS), 0, s, bi, *r);
+    else hipLaunchKernelGGL(beam_candidates_kernel<>, dim3(p->M / c->num_beams), dim3(BEAM_THREADS), 0, s, bi);
+    MVLT_LAUNCH_CHECK();
+    return MVLT_OK;
+}
+}  // namespace
+
+extern "C" int mvlt_gemm_beam_candidates(const MvltGemm* p, const MvltBeamCand* c, void* stream) {
+    return beam_candidates_entry(p, c, nullptr, stream);
+}
+extern "C" int mvlt_gemm_beam_candidates_rules(const MvltGemm* p, const MvltBeamCand* c, const MvltLogitRules* rules, void* stream) {
+    RulesDev rd;          // RULES_OF without its 64 rows: M = G * num_beams, any size
+    { MVLT_CHECK(p, MVLT_ERR_ARG); const int rc_ = rules_dev(rules, p->M, p->N, rd, 0x7FFFFFFF); if (rc_ != MVLT_OK) return rc_; }
+    return beam_candidates_entry(p, c, &rd, stream);
+}
+
+extern "C" int mvlt_beam_rules_plan(const MvltLogitRules* r, const int32_t* seq, int64_t ld_seq, int rows, int V, void* stream) {
+    MVLT_CHECK(r && r->seen && r->banned && r->col && seq, MVLT_ERR_ARG);
+    MVLT_CHECK(rows >= 1 && V >= 1 && ld_seq >= 1 && r->ld_words >= (long)ceil_div(V, 32), MVLT_ERR_ARG);
+    MVLT_CHECK(r->penalty > 0.f && r->ngram >= 0 && r->min_length >= 0, MVLT_ERR_ARG);
+    const BeamRulesPlan f{r->seen, r->banned, (long)r->ld_words, seq, (long)ld_seq, r->col, r->ngram, r->min_length, r->eos_id, r->has_eos, V};
+    hipLaunchKernelGGL(beam_rules_plan_kernel, dim3(rows), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), f);
     MVLT_LAUNCH_CHECK();
     return MVLT_OK;
 }

@@ -33,6 +33,11 @@ gather of every layer's cache by beam index per token.  ``MVLT_BEAM_DEVICE=1`` /
 shapes of the fused route): the scorer's ``process`` runs on the device too (``mvlt_beam_step`` on a ``BeamDeviceState``), so the loop
 has no per-token read-back and is replayed as one HIP graph per token (``_BeamGraph``; ``MVLT_DECODE_GRAPH=0``: eager); ``finalize``
 stays on the host, after one read-back.
+Logit rules in beam search (``beam_search(repetition_penalty=, no_repeat_ngram_size=, min_length=)``): HF 4.16 places the processors
+on the log-probabilities, ahead of the beam score.  The fused and the device route run ``mvlt_beam_rules_plan`` over the int32 live
+sequences (the hypotheses' own tokens after the beam reorder: ``BeamDeviceState.seq`` on the device route) and the rule-aware
+selection of ``mvlt_gemm_beam_candidates_rules`` (``ops.BeamLogitRules``); the plain route applies the same rules as torch ops on
+its ``log_softmax`` rows and uses neither kernel.  All rules off is the code path, and the graph, without them.
 """
 from __future__ import annotations
 
@@ -88,9 +93,10 @@ def _greedy_route(sample_mode, B, filtered, graph_on):
 
 def check_logit_rules(repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, num_beams=1, V=None, max_length=None):
     """(float penalty, int ngram, int min_length) of a constrained decode, or ValueError: penalty > 0 (1.0 = off, no NaN),
-    ngram >= 0 (0 = off), min_length >= 0 (0 = off); any rule switched on needs num_beams <= 1 (beam search has no rule-aware
-    candidate head) and, when ``V`` / ``max_length`` are given, V > max_length: a history of max_length - 1 tokens plus eos can ban
-    max_length columns, and a row must keep one."""
+    ngram >= 0 (0 = off), min_length >= 0 (0 = off); any rule switched on needs num_beams <= 1 (the rules of this function are
+    those of the greedy and sampled picks, on the raw logits; ``beam_search`` takes its own, on the log-probabilities, and checks
+    them here with num_beams = 1) and, when ``V`` / ``max_length`` are given, V > max_length: a history of max_length - 1 tokens
+    plus eos can ban max_length columns, and a row must keep one."""
     pen = float(repetition_penalty)
     if not pen > 0.0 or pen == float("inf"):
         raise ValueError("repetition_penalty must be a positive number (1.0 switches it off)")
@@ -100,9 +106,23 @@ def check_logit_rules(repetition_penalty=1.0, no_repeat_ngram_size=0, min_length
     rules = pen, int(no_repeat_ngram_size), int(min_length)
     if rules != (1.0, 0, 0):
         if num_beams > 1:
-            raise ValueError("repetition_penalty / no_repeat_ngram_size / min_length are not implemented for beam search (num_beams > 1)")
+            raise ValueError("repetition_penalty / no_repeat_ngram_size / min_length with beam search (num_beams > 1) go through "
+                             "decode.beam_search or MVLBertForImageCaption.generate")
         if V is not None and max_length is not None and V <= max_length:
             raise ValueError(f"logit rules can ban up to max_length = {max_length} columns: the vocabulary ({V}) must be larger")
+    return rules
+
+
+def check_beam_rules(repetition_penalty, no_repeat_ngram_size, min_length, num_beams, V, max_length):
+    """The rules of a beam search, or ValueError: the argument checks of ``check_logit_rules`` and, with a rule switched on,
+    V >= max(max_length + 2, 2 * num_beams + 1).  A row bans at most c + 1 <= max_length columns, which leaves every sample
+    2 * num_beams unbanned entries at every step -- at step 0, where ONE row is scored, and later, where each of the num_beams
+    rows keeps two -- so the scorer always finds its num_beams tokens."""
+    rules = check_logit_rules(repetition_penalty, no_repeat_ngram_size, min_length)
+    need = max(max_length + 2, 2 * num_beams + 1)
+    if rules != (1.0, 0, 0) and V < need:
+        raise ValueError(f"logit rules can ban up to max_length = {max_length} columns of a row: {num_beams} beams need a vocabulary "
+                         f"of at least {need} tokens, not {V}")
     return rules
 
 
@@ -695,11 +715,11 @@ class BeamDeviceState:
 
 class _BeamGraph(_DecodeGraph):
     """Beam search per token as one replayed HIP graph, after the model of ``_GreedyGraph``: [mvlt_beam_step, the 2-token cached
-    forward over the B * beams rows, the head transform, mvlt_gemm_beam_candidates], captured on one stream (no parallel
-    branches).  All state is static: ``BeamDeviceState``, the caches, the hidden rows, the logits workspace.  The captured
+    forward over the B * beams rows, the head transform, (with logit rules: mvlt_beam_rules_plan over the state's live sequences,)
+    mvlt_gemm_beam_candidates(_rules)], captured on one stream (no parallel branches).  All state is static: ``BeamDeviceState``, the caches, the hidden rows, the logits workspace.  The captured
     beam step carries src_beams = num_beams also for the lists of step 0 (their beam index is 0, which both values admit)."""
 
-    def __init__(self, model, key, B, nb, n_img, max_length, cd, pad, eos, mask_id, log):
+    def __init__(self, model, key, B, nb, n_img, max_length, cd, pad, eos, mask_id, log, rules=(1.0, 0, 0)):
         dev = next(model.parameters()).device
         H = model.config.hidden_size
         rows = B * nb
@@ -712,6 +732,8 @@ class _BeamGraph(_DecodeGraph):
         self.hlast = self.hfull.view(rows, 2, H)[:, 1]
         V = model.MLM_head_seq2seq.predictions.decoder.out_features
         self.ws = torch.empty(rows * ((V + 3) // 4 * 4), dtype=torch.float32, device=dev)
+        # logit rules: the graph owns the bitmaps; the plan reads the live sequences where the beam step writes them (seq, col)
+        self.rules = ops.BeamLogitRules(V, *rules, eos, self.st.seq, self.st.col) if rules != (1.0, 0, 0) else None
         self.st.reset(self.prefix - 1)          # a valid position for the warm-up and the capture pass: both really run
 
     def step(self):
@@ -724,10 +746,13 @@ class _BeamGraph(_DecodeGraph):
         self.step()
         _step2(model.MVLBert, ar, st.new_ids, st.past, self.kc, self.vc, self.cd, out_last=self.hfull, beam=(self.nb, self.prefix, st.slot))
         t2, W, bias = _head(model, ar, self.hlast)
-        ops.gemm_beam_candidates(t2, W, bias, st.beam_scores, self.nb, 2 * self.nb, out=st.cand, ws=self.ws)
+        if self.rules is not None:          # the bitmaps of the reordered histories, then the rule-aware selection
+            self.rules.plan()
+        ops.gemm_beam_candidates(t2, W, bias, st.beam_scores, self.nb, 2 * self.nb, out=st.cand, ws=self.ws,
+                                 rules=self.rules.struct if self.rules is not None else None)
 
 
-def _beam_device(model, ar, feat, nb, max_length, pad, eos, mask_id, cd, graph_on, cand_log):
+def _beam_device(model, ar, feat, nb, max_length, pad, eos, mask_id, cd, graph_on, cand_log, rules=(1.0, 0, 0)):
     """beam_search with the scorer on the device (``mvlt_beam_step``): no per-token read-back.  ``graph_on``: one graph replay per
     token (``_BeamGraph``), else the eager loop.  The host reads ``alive`` back every 8 tokens; the steps that run past the
     point where every sample is done change no pool (done samples are skipped).  ``finalize`` is the host scorer's."""
@@ -735,19 +760,26 @@ def _beam_device(model, ar, feat, nb, max_length, pad, eos, mask_id, cd, graph_o
     dev = feat.device
     if graph_on:
         key = (B, nb, n_img, max_length, cd, pad, eos, mask_id, ar.flat.data_ptr(), dev.index, cand_log is not None)
-        bg = _BeamGraph.of(model, "_mvlt_beam_graph", key, B, nb, n_img, max_length, cd, pad, eos, mask_id, cand_log is not None)
-        st, kc, vc, ws = bg.st, bg.kc, bg.vc, bg.ws
+        if rules != (1.0, 0, 0):          # a graph with rules takes the beam graph's slot, like another max_length
+            key = key + ("rules",) + tuple(rules)
+        bg = _BeamGraph.of(model, "_mvlt_beam_graph", key, B, nb, n_img, max_length, cd, pad, eos, mask_id, cand_log is not None, rules)
+        st, kc, vc, ws, lr = bg.st, bg.kc, bg.vc, bg.ws, bg.rules
         if bg.log is not None:
             bg.log.zero_()
     else:
         st = BeamDeviceState(B, nb, max_length, pad, eos, mask_id, dev, cand_log=cand_log)
         kc, vc = _alloc_cache(model, B * nb, n_img, max_length, cd, dev)
         ws = None
+        V = model.MLM_head_seq2seq.predictions.decoder.out_features
+        lr = ops.BeamLogitRules(V, *rules, eos, st.seq, st.col) if rules != (1.0, 0, 0) else None
+    rs = lr.struct if lr is not None else None
     # ---- step 0: the prefix into the first cache row of every sample, the candidates of the one scored row per sample
     hlast, prefix = _step0(model.MVLBert, feat, st.new_ids[::nb, 1:2].contiguous(), kc, vc, stride=nb)
     st.reset(prefix - 1)
     t2, W, bias = _head(model, ar, hlast.contiguous())
-    ops.gemm_beam_candidates(t2, W, bias, torch.zeros(B, dtype=torch.float32, device=dev), 1, 2 * nb, out=st.cand, ws=ws)
+    if lr is not None:
+        lr.plan(B)                               # one row per sample, column 0: the empty history (only min_length bears)
+    ops.gemm_beam_candidates(t2, W, bias, torch.zeros(B, dtype=torch.float32, device=dev), 1, 2 * nb, out=st.cand, ws=ws, rules=rs)
 
     def all_done(t):          # after the beam step of token t
         return _sync_due(eos, t + 1) and 0 in st.alive[t + 1 - SYNC_EVERY:t + 1].tolist()
@@ -768,7 +800,9 @@ def _beam_device(model, ar, feat, nb, max_length, pad, eos, mask_id, cd, graph_o
                 break
             hlast = _step2(model.MVLBert, ar, st.new_ids, st.past, kc, vc, cd, beam=(nb, prefix, st.slot))
             t2, W, bias = _head(model, ar, hlast.contiguous())
-            ops.gemm_beam_candidates(t2, W, bias, st.beam_scores, nb, 2 * nb, out=st.cand)
+            if lr is not None:
+                lr.plan()
+            ops.gemm_beam_candidates(t2, W, bias, st.beam_scores, nb, 2 * nb, out=st.cand, rules=rs)
     scorer, seqs, scores = st.scorer()
     out = scorer.finalize(seqs, scores, model.config.max_length, pad, eos)
     return torch.tensor(out, dtype=torch.int64, device=dev)
@@ -783,18 +817,25 @@ def _host_beam_step(scorer, input_ids, cur_len, cands, pad, eos, dev):
             torch.tensor(i_l, dtype=torch.int64, device=dev))
 
 
-def _beam_fused(model, ar, feat, nb, max_length, pad, eos, mask_id, cd, mask_col, mask2):
+def _beam_fused(model, ar, feat, nb, max_length, pad, eos, mask_id, cd, mask_col, mask2, rules=(1.0, 0, 0)):
     """The default route: candidates from ``mvlt_gemm_beam_candidates``, the cache never reordered (the attention follows the slot
     table), the scorer on the host with one read-back per token."""
     mv = model.MVLBert
     B, n_img, _ = feat.shape
     dev = feat.device
     scorer = BeamScorer(B, nb)
+    lr = None
+    if rules != (1.0, 0, 0):          # the history the plan reads: the hypotheses' own tokens, kept in step with the beam reorder
+        V = model.MLM_head_seq2seq.predictions.decoder.out_features
+        hist = torch.zeros((B * nb, max_length), dtype=torch.int32, device=dev)
+        lr = ops.BeamLogitRules(V, *rules, eos, hist, torch.zeros(1, dtype=torch.int64, device=dev))
 
     def candidates(hlast, scores, beams):
         """-> (scores, tokens, beams) of the 2 * nb candidates per sample as host lists: one read-back."""
         t2, W, bias = _head(model, ar, hlast.contiguous())
-        out, _ = ops.gemm_beam_candidates(t2, W, bias, scores, beams, 2 * nb)
+        if lr is not None:
+            lr.plan(t2.shape[0])
+        out, _ = ops.gemm_beam_candidates(t2, W, bias, scores, beams, 2 * nb, rules=lr.struct if lr is not None else None)
         host = out.cpu()
         return host[0].view(torch.float32).tolist(), host[2].tolist(), host[1].tolist()
 
@@ -814,6 +855,10 @@ def _beam_fused(model, ar, feat, nb, max_length, pad, eos, mask_id, cd, mask_col
         # the beam reorder (model.py:758-763) moves table rows, not cache rows.  A finished sample gets beam_idx 0 (a row of
         # sample 0): only the slot VALUES travel, and the kernel clamps them into the sample
         slot = slot.index_select(0, beam_idx)
+        if lr is not None:                               # h of every kept hypothesis: its parent's tokens, then its own
+            lr.seq.copy_(lr.seq.index_select(0, beam_idx))
+            lr.seq[:, cur_len] = beam_tok
+            lr.col.fill_(cur_len + 1)
         hlast = _step2(mv, ar, torch.cat([beam_tok[:, None], mask2], dim=1), past, kc, vc, cd, beam=(nb, prefix, slot))
         slot[:, past - prefix] = own                     # position `past` of every hypothesis now lives in its own row
         past += 1
@@ -822,7 +867,31 @@ def _beam_fused(model, ar, feat, nb, max_length, pad, eos, mask_id, cd, mask_col
     return torch.tensor(seqs, dtype=torch.int64, device=dev)
 
 
-def _beam_plain(model, ar, feat, nb, max_length, pad, eos, mask_id, cd, mask_col, mask2):
+def _rules_torch(logp, hists, rules, eos):
+    """The three rules as torch ops on log-probability rows ``logp`` [rows, V] (changed in place and returned): ``hists`` = the
+    rows' own generated tokens as host lists of one length c.  The placement of HF 4.16 beam_search, with none of the kernels."""
+    penalty, g, min_length = rules
+    c = len(hists[0])
+    if penalty != 1.0 and c > 0:
+        h = torch.tensor(hists, dtype=torch.int64, device=logp.device)
+        sc = logp.gather(1, h)
+        p = torch.full_like(sc, penalty)                 # a tensor divisor: a Python scalar would be turned into its reciprocal
+        logp.scatter_(1, h, torch.where(sc < 0, sc * p, sc / p))
+    if g >= 1 and c + 1 >= g:
+        rows, cols = [], []
+        for m, h in enumerate(hists):
+            last = h[c - g + 1:]
+            for i in range(c - g + 1):
+                if h[i:i + g - 1] == last:
+                    rows.append(m); cols.append(h[i + g - 1])
+        if rows:
+            logp[torch.tensor(rows, device=logp.device), torch.tensor(cols, device=logp.device)] = -float("inf")
+    if eos is not None and c < min_length:
+        logp[:, eos] = -float("inf")
+    return logp
+
+
+def _beam_plain(model, ar, feat, nb, max_length, pad, eos, mask_id, cd, mask_col, mask2, rules=(1.0, 0, 0)):
     """The route of the reference: bf16 logits, ``log_softmax``, ``topk`` and a gather of every layer's cache by beam index per
     token (model.py:758-763), the scorer on the host."""
     mv = model.MVLBert
@@ -837,12 +906,16 @@ def _beam_plain(model, ar, feat, nb, max_length, pad, eos, mask_id, cd, mask_col
         logits, _ = head._logits(ar, t2)
         return torch.log_softmax(logits[:, :V].float(), dim=-1)
 
+    on = rules != (1.0, 0, 0)
     # ---- step 0 on the B images; caches replicated to the beams afterwards
     kc, vc = _alloc_cache(model, B, n_img, max_length, cd, dev)
     hlast, past = _step0(mv, feat, mask_col, kc, vc)
     rep = torch.arange(B, device=dev).repeat_interleave(nb)
     kc, vc = [k.index_select(0, rep) for k in kc], [v.index_select(0, rep) for v in vc]
-    logp = logp_of(hlast).index_select(0, rep)                                # [B*nb, V]
+    logp = logp_of(hlast)
+    if on:                                                                    # step 0: the empty history of the one scored row
+        logp = _rules_torch(logp, [[] for _ in range(B)], rules, eos)
+    logp = logp.index_select(0, rep)                                          # [B*nb, V]
     beam_scores = torch.zeros((B, nb), dtype=torch.float32, device=dev)
     beam_scores[:, 1:] = -1e9
     beam_scores = beam_scores.view(-1)
@@ -860,6 +933,8 @@ def _beam_plain(model, ar, feat, nb, max_length, pad, eos, mask_id, cd, mask_col
             kc[i] = kc[i].index_select(0, beam_idx)
             vc[i] = vc[i].index_select(0, beam_idx)
         logp = logp_of(_step2(mv, ar, torch.cat([beam_tok[:, None], mask2], dim=1), past, kc, vc, cd))
+        if on:                                               # input_ids: the hypotheses' own tokens after the reorder
+            logp = _rules_torch(logp, input_ids, rules, eos)
         past += 1
     seqs = scorer.finalize(input_ids, beam_scores.tolist(), model.config.max_length, pad, eos)
     return torch.tensor(seqs, dtype=torch.int64, device=dev)
@@ -867,7 +942,7 @@ def _beam_plain(model, ar, feat, nb, max_length, pad, eos, mask_id, cd, mask_col
 
 @torch.no_grad()
 def beam_search(model, image_feature, num_beams, learning_strategy='unilm', max_length=None, pad_token_id=None,
-                eos_token_id=None, device_scorer=None, cand_log=None):
+                eos_token_id=None, device_scorer=None, cand_log=None, repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0):
     """``MVLBertForImageCaption.beam_search`` (model.py:636-816) with the KV cache: scores = log_softmax(logits) +
     beam score, top 2*beams over (beam, token), scorer bookkeeping, cache rows gathered by ``beam_idx`` (:758-763).
     Step 0 runs once per image (all beams of a sample start identical and only beam 0 carries score 0, :681-682),
@@ -875,7 +950,17 @@ def beam_search(model, image_feature, num_beams, learning_strategy='unilm', max_
     ``device_scorer`` (None: MVLT_BEAM_DEVICE=1 switches it on; default off): the scorer bookkeeping runs on the device
     (``mvlt_beam_step``) and the loop has no per-token read-back; as a replayed graph unless MVLT_DECODE_GRAPH=0.  Same shapes as
     the fused route (anything else decodes as without the switch), same sequences.  ``cand_log`` (device-scorer route only): an
-    int32 device tensor [max_length, B, 3, 2 * num_beams] that receives the candidate lists every step consumed."""
+    int32 device tensor [max_length, B, 3, 2 * num_beams] that receives the candidate lists every step consumed.
+    ``repetition_penalty`` (1.0 = off) / ``no_repeat_ngram_size`` (0 = off) / ``min_length`` (0 = off): HF's three processors where
+    transformers 4.16 beam_search places them, on the LOG-PROBABILITIES of a hypothesis ahead of its beam score (greedy_search
+    applies them to the raw logits), over the hypothesis' own tokens after the beam reorder.  A banned token is never a
+    candidate and stays inside the log-sum-exp.  Every route returns the same sequences in f32 (the plain route applies the
+    rules as torch ops, the other two in the candidate head); with all three off the call is the one without them.  The
+    vocabulary must hold max(max_length + 2, 2 * num_beams + 1) tokens (ValueError): a row bans at most max_length columns, so
+    every sample keeps 2 * num_beams candidates at every step."""
+    rules = check_beam_rules(repetition_penalty, no_repeat_ngram_size, min_length, num_beams,
+                             model.MLM_head_seq2seq.predictions.decoder.out_features,
+                             max_length if max_length is not None else model.config.max_length)
     if learning_strategy != 'unilm':
         raise NotImplementedError("only learning_strategy='unilm' is coherent with the KV cache (SURVEY.md 3.3)")
     cd, ar, max_length, pad, eos, mask_id, feat = _resolve(model, image_feature, max_length, pad_token_id, eos_token_id)
@@ -887,6 +972,6 @@ def beam_search(model, image_feature, num_beams, learning_strategy='unilm', max_
     graph_on, fused_on, device_on = _env()
     route = _beam_route(nb, cfg.hidden_size // cfg.num_attention_heads, max_length, fused_on, device_scorer, device_on)
     if route == 'device':
-        return _beam_device(model, ar, feat, nb, max_length, pad, eos, mask_id, cd, graph_on, cand_log)
+        return _beam_device(model, ar, feat, nb, max_length, pad, eos, mask_id, cd, graph_on, cand_log, rules)
     search = _beam_fused if route == 'fused' else _beam_plain
-    return search(model, ar, feat, nb, max_length, pad, eos, mask_id, cd, mask_col, mask2)
+    return search(model, ar, feat, nb, max_length, pad, eos, mask_id, cd, mask_col, mask2, rules)

@@ -766,11 +766,15 @@ class MVLBertForImageCaption(MVLBertPretrainedModel):
         (run_report_generation_cxr.py:469-471) instead of the logits -- the mean over the labelled positions, NaN when there
         are none -- computed on the labelled rows only, with the loss inside the decoder product (loss_forward).
         ``repetition_penalty`` / ``no_repeat_ngram_size`` / ``min_length``: the logit rules of ``decode.greedy_search``
-        (``num_beams == 1``; with beams they raise ValueError -- the candidate head has no rules yet)."""
+        (``num_beams == 1``; with beams they raise ValueError here -- this signature passes beam search no options: ``generate``
+        reaches the rules of ``decode.beam_search``)."""
         if labels is not None and num_beams >= 1:
             raise ValueError("labels ask for the training loss: num_beams must be 0")
         from .decode import check_logit_rules
-        rules = check_logit_rules(repetition_penalty, no_repeat_ngram_size, min_length, num_beams=num_beams)
+        rules = check_logit_rules(repetition_penalty, no_repeat_ngram_size, min_length)
+        if rules != (1.0, 0, 0) and num_beams > 1:
+            raise ValueError("forward() passes no logit rules to beam search (num_beams > 1): call generate(num_beams=..., "
+                             "repetition_penalty=..., no_repeat_ngram_size=..., min_length=...)")
         Arena.of(self, compute_dtype_of(self))
         image_feature = self.conv(image)
         if labels is not None:
@@ -784,6 +788,30 @@ class MVLBertForImageCaption(MVLBertPretrainedModel):
                                  seed=seed, temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=rules[0],
                                  no_repeat_ngram_size=rules[1], min_length=rules[2])
         return self.encode_forward(image_feature, caption, learning_strategy)
+
+    @torch.no_grad()
+    def generate(self, image, num_beams=1, learning_strategy='unilm', sample_mode='greedy', max_length=None, seed=None, temperature=1.0,
+                 top_k=0, top_p=1.0, repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, device_scorer=None):
+        """The one call that reaches every decode option (the reference leaves ``generate`` an empty stub).  ``num_beams == 1``:
+        ``decode.greedy_search`` -> (ids, token scores), greedy or sampled, with filters and logit rules on the raw logits.
+        ``num_beams > 1``: ``decode.beam_search`` -> sequences [B, <= max_length], with the logit rules on the log-probabilities
+        (HF 4.16) and ``device_scorer``; the sampling options must stay at their defaults (ValueError).  Returns what ``forward``
+        returns for the same ``num_beams``."""
+        if num_beams < 1:
+            raise ValueError("generate() decodes: num_beams must be at least 1")
+        from . import decode
+        if num_beams > 1 and (sample_mode != 'greedy' or seed is not None or float(temperature) != 1.0 or top_k != 0 or top_p != 1.0):
+            raise ValueError("sample_mode / seed / temperature / top_k / top_p belong to num_beams == 1: beam search does not sample")
+        Arena.of(self, compute_dtype_of(self))
+        image_feature = self.conv(image)
+        if num_beams > 1:
+            return decode.beam_search(self, image_feature, num_beams, learning_strategy=learning_strategy, max_length=max_length,
+                                      device_scorer=device_scorer, repetition_penalty=repetition_penalty,
+                                      no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length)
+        return decode.greedy_search(self, image_feature, learning_strategy=learning_strategy, sample_mode=sample_mode,
+                                    max_length=max_length, seed=seed, temperature=temperature, top_k=top_k, top_p=top_p,
+                                    repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                                    min_length=min_length)
 
     def encode_forward(self, image_feature, caption, learning_strategy):
         text_out, _, _, sep_out = self.MVLBert(text_idx=caption, text_mask=None, image_feature=image_feature,

@@ -512,14 +512,46 @@ def gemm_sample_filtered_step(A, W, bias, state, top_k=0, top_p=1.0, rules=None)
 BEAM_MAX_BEAMS, BEAM_MAX_CAND = 8, 16          # limits of mvlt_gemm_beam_candidates (csrc/skinny.hip BEAM_MAXB / BEAM_MAXC)
 
 
-def gemm_beam_candidates(A, W, bias, beam_scores, num_beams, n_cand, want_lse=False, out=None, ws=None):
+def beam_rules_plan(rules, seq, rows, V):
+    """Rebuild the bitmaps of ``rules`` (a prepared ``L.MvltLogitRules``; its ids / ld_ids are not read) for the first ``rows`` rows
+    from the int32 live sequences ``seq`` [>= rows, ld] of beam search and ``rules.col`` (mvlt_beam_rules_plan: one launch, any
+    number of rows)."""
+    assert seq.dtype == torch.int32 and seq.dim() == 2 and seq.stride(1) == 1 and seq.shape[0] >= rows
+    L.check(L.lib().mvlt_beam_rules_plan(C.byref(rules), _p(seq), seq.stride(0), int(rows), int(V), _stream()), "mvlt_beam_rules_plan")
+
+
+class BeamLogitRules:
+    """The logit rules of a beam search over ``seq.shape[0]`` = B * num_beams hypotheses of a V-column head: the two bitmaps
+    [rows, ceil(V / 32)], the history ``seq`` (int32 [rows, max_length]: the hypotheses' own tokens after the beam reorder, the layout
+    of MvltBeamStep.seq) and ``col`` (int64 [1], the number of generated tokens) -- device tensors this object keeps alive -- and
+    the prepared struct.  ``plan(rows)`` before every candidate call (step 0 scores one row per sample: rows = B, col = 0)."""
+
+    def __init__(self, V, penalty, ngram, min_length, eos, seq, col):
+        assert seq.dtype == torch.int32 and seq.dim() == 2 and seq.stride(1) == 1 and col.dtype == torch.int64
+        self.rows, self.V, self.seq, self.col = seq.shape[0], V, seq, col
+        self.ld_words = (V + 31) // 32
+        self.maps = torch.zeros((2, self.rows, self.ld_words), dtype=torch.int32, device=seq.device)
+        r = self.struct = L.MvltLogitRules()
+        r.seen, r.banned, r.ld_words = _p(self.maps[0]), _p(self.maps[1]), self.ld_words
+        r.penalty, r.ngram, r.min_length = float(penalty), int(ngram), int(min_length)
+        r.ids, r.ld_ids, r.col = None, 0, _p(col)
+        r.eos_id, r.has_eos = (eos if eos is not None else -1), int(eos is not None)
+
+    def plan(self, rows=None):
+        beam_rules_plan(self.struct, self.seq, self.rows if rows is None else rows, self.V)
+
+
+def gemm_beam_candidates(A, W, bias, beam_scores, num_beams, n_cand, want_lse=False, out=None, ws=None, rules=None):
     """The candidate step of beam search without the logits round trip (mvlt_gemm_beam_candidates): A: [G * num_beams, K] (the
     beams of sample g are the rows g * num_beams .. + num_beams; any number of rows), W: [N, K], beam_scores f32 [G * num_beams].
     Per sample the n_cand largest log_softmax(A @ W^T + bias) + beam score over (beam, token), sorted descending, ties by the
     lower beam * N + token.  Returns ``(out, lse)``: ``out`` one int32 tensor [3, G, n_cand] -- out[0] viewed as f32 holds the
     scores, out[1] the beams, out[2] the tokens (one buffer: one read-back) -- and lse f32 [rows] or None.
     ``out`` / ``ws``: caller-owned buffers for the lists (int32 [3, G, n_cand], contiguous) and the f32 logits workspace (at least
-    rows * ldx elements, ldx = N rounded up to 4) -- a replayed decode loop reads the lists at a fixed address."""
+    rows * ldx elements, ldx = N rounded up to 4) -- a replayed decode loop reads the lists at a fixed address.
+    ``rules``: a prepared ``L.MvltLogitRules`` whose bitmaps ``beam_rules_plan`` has filled for these rows -- the rules act on the
+    log-probabilities ahead of the beam score, banned entries are never listed (mvlt_gemm_beam_candidates_rules); a sample with
+    fewer than n_cand unbanned entries ends its list with (-inf, 0, 0)."""
     p, M, N = _head_gemm(A, W, bias)
     assert beam_scores.dtype == torch.float32 and beam_scores.is_contiguous() and beam_scores.numel() == M
     ldx = (N + 3) // 4 * 4
@@ -536,6 +568,9 @@ def gemm_beam_candidates(A, W, bias, beam_scores, num_beams, n_cand, want_lse=Fa
     c = L.MvltBeamCand()
     c.num_beams, c.n_cand, c.beam_scores, c.x, c.ldx = int(num_beams), int(n_cand), _p(beam_scores), _p(ws), ldx
     c.cand_score, c.cand_beam, c.cand_tok, c.lse = _p(out[0]), _p(out[1]), _p(out[2]), (_p(lse) if want_lse else None)
+    if rules is not None:
+        L.check(L.lib().mvlt_gemm_beam_candidates_rules(C.byref(p), C.byref(c), C.byref(rules), _stream()), "mvlt_gemm_beam_candidates_rules")
+        return out, lse
     L.check(L.lib().mvlt_gemm_beam_candidates(C.byref(p), C.byref(c), _stream()), "mvlt_gemm_beam_candidates")
     return out, lse
 

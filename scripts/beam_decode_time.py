@@ -8,7 +8,10 @@ from the head product to the candidates), attention (the cached-attention launch
 Two more routes run in the same rounds: the device scorer (mvlt_beam_step, MVLT_BEAM_DEVICE=1) as an eager loop
 (MVLT_DECODE_GRAPH=0, "device") and as one replayed HIP graph per token ("graph"); both are compared with the fused host-scorer
 route.  A replayed graph makes no per-token Python calls, so it has no per-token split.
-BATCHES ("8,32"), ROUNDS (5), MAXLEN (150), BEAMS (5), ROUTES ("fused,plain,device,graph")."""
+RULES ("penalty,ngram,min_length", e.g. "1.2,3,10"; unset: none) adds every route once more with the logit rules switched on
+("fused+rules", ...: model.generate, the plan launch and the rule-aware selection), interleaved with the rules-off decodes in the
+same rounds of the same process, and prints on against off per route with the share of tokens the rules changed.
+BATCHES ("8,32"), ROUNDS (5), MAXLEN (150), BEAMS (5), ROUTES ("fused,plain,device,graph"), SPLIT ("1"; "0": no per-token split)."""
 import os, statistics, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -25,12 +28,18 @@ ENV = {"fused": dict(MVLT_BEAM_FUSED="1", MVLT_BEAM_DEVICE="0", MVLT_DECODE_GRAP
        "device": dict(MVLT_BEAM_FUSED="1", MVLT_BEAM_DEVICE="1", MVLT_DECODE_GRAPH="0"),
        "graph": dict(MVLT_BEAM_FUSED="1", MVLT_BEAM_DEVICE="1", MVLT_DECODE_GRAPH="1")}
 ROUTES = tuple((n, n) for n in os.environ.get("ROUTES", "fused,plain,device,graph").split(","))
+RULES = os.environ.get("RULES")
+RULES = (float(RULES.split(",")[0]), int(RULES.split(",")[1]), int(RULES.split(",")[2])) if RULES else None
+RULED = tuple((n + "+rules", n) for n, _ in ROUTES) if RULES else ()
 
 
-def run(img, flag):
+def run(img, flag, rules=None):
     os.environ.update(ENV[flag])
     torch.cuda.synchronize(); t = time.time()
-    out = model(img, None, BEAMS, "unilm")
+    if rules is None:
+        out = model(img, None, BEAMS, "unilm")
+    else:
+        out = model.generate(img, num_beams=BEAMS, repetition_penalty=rules[0], no_repeat_ngram_size=rules[1], min_length=rules[2])
     torch.cuda.synchronize()
     return (time.time() - t) * 1e3, out
 
@@ -104,18 +113,18 @@ class Split:
 
 for B in [int(b) for b in os.environ.get("BATCHES", "8,32").split(",")]:
     img = torch.randn(B, 3, 224, 224, device="cuda")
-    times, outs = {name: [] for name, _ in ROUTES}, {}
+    times, outs = {name: [] for name, _ in ROUTES + RULED}, {}
     for r in range(ROUNDS + 1):                       # round 0 warms up
-        for name, flag in ROUTES:
-            ms, outs[name] = run(img, flag)
+        for name, flag in ROUTES + RULED:
+            ms, outs[name] = run(img, flag, RULES if name.endswith("+rules") else None)
             if r:
                 times[name].append(ms)
     def same_as_fused(name):
         return outs["fused"].shape == outs[name].shape and bool((outs["fused"] == outs[name]).all())
 
-    for name, _ in ROUTES:
+    for name, _ in ROUTES + RULED:
         v = times[name]
-        print(f"B={B:3d} beams={BEAMS} {name:6s} median {statistics.median(v):8.2f} ms/batch  (min {min(v):.2f} max {max(v):.2f}, spread "
+        print(f"B={B:3d} beams={BEAMS} {name:12s} median {statistics.median(v):8.2f} ms/batch  (min {min(v):.2f} max {max(v):.2f}, spread "
               f"{max(v) - min(v):.2f} over {len(v)} rounds)", flush=True)
     if "plain" in times and "fused" in times:
         gain = statistics.median(times["plain"]) - statistics.median(times["fused"])
@@ -128,8 +137,17 @@ for B in [int(b) for b in os.environ.get("BATCHES", "8,32").split(",")]:
             print(f"B={B:3d} {name} is {gain:+.2f} ms/batch ({1e3 * gain / MAXLEN:+.1f} us/token) against fused, whose spread is "
                   f"{max(times['fused']) - min(times['fused']):.2f} ms ({name}: {max(times[name]) - min(times[name]):.2f}); same sequences as "
                   f"fused: {same_as_fused(name)}", flush=True)
+    for name, _ in RULED:          # rules on against off, the same route in the same rounds
+        off = name[:-len("+rules")]
+        cost = statistics.median(times[name]) - statistics.median(times[off])
+        a, b = outs[name], outs[off]
+        w = min(a.shape[1], b.shape[1])
+        print(f"B={B:3d} {name} {RULES} is {cost:+.2f} ms/batch ({1e3 * cost / MAXLEN:+.1f} us/token) against {off}, whose spread is "
+              f"{max(times[off]) - min(times[off]):.2f} ms; tokens changed by the rules: {100.0 * float((a[:, :w] != b[:, :w]).float().mean()):.1f} %; "
+              f"same sequences as fused+rules: {outs['fused+rules'].shape == a.shape and bool((outs['fused+rules'] == a).all()) if 'fused+rules' in outs else None}",
+              flush=True)
     for name, flag in ROUTES:
-        if name == "graph":
+        if name == "graph" or os.environ.get("SPLIT", "1") == "0":
             continue
         with Split() as sp:
             run(img, flag)
