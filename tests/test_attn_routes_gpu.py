@@ -6,7 +6,10 @@ ops.attn_route first (forward and backward): a threshold that moves a shape off 
 re-pointed instead of quietly testing another kernel.  Outputs start filled with NaN; packed rows leave gaps of NaN
 rows in qkv / dout that must not be read, and the gap rows of out / dqkv and the lse entries at q >= seq_len must keep
 their fill.  A backward whose forward route is unsupported (f32 beyond 192 rows) reads the reference's out / lse.
-The KV-cache kernels (mvlt_attn_cached) and the fused Swin half (mvlt_swin_wmsa2_fwd / _bwd, stage by stage) follow."""
+The KV-cache kernels (mvlt_attn_cached) and the fused Swin half (mvlt_swin_wmsa2_fwd / _bwd, stage by stage) follow.
+Everything here calls ops.* directly.  How a Swin block wires these kernels together -- swin.py _block_fwd / _block_bwd and
+csrc/host.cpp swin_block_fwd / swin_block_bwd, every forward and backward mode on both host paths -- is judged per element in
+tests/test_swin_attn_half_gpu.py (reference: tests/swin_attn_half_ref.py, proven in tests/test_swin_attn_half_cpu.py)."""
 import math
 
 import pytest
