@@ -278,7 +278,6 @@ class MVLBert(nn.Module):
         B, n_img, H = feat.shape
         T = 0 if text_idx is None else text_idx.shape[1]
         Lq = n_img + 2 + T
-        nH = cfg.num_attention_heads
         train = self.training
         p_h = cfg.hidden_dropout_prob if train else 0.0
         p_a = cfg.attention_probs_dropout_prob if train else 0.0
@@ -287,49 +286,19 @@ class MVLBert(nn.Module):
         # pack = (row_start, seq_len, R): activations are [R, H] with the trailing zero-padded caption positions
         # of every sample left out (forward_packed); otherwise dense [B*Lq, H]
         rows = B * Lq if pack is None else pack[2]
-        rd = pack[4] if (pack is not None and len(pack) > 4) else None     # row count on the device (auto-packed batch)
         x = ops.embed_fwd(text_idx, feat, self.word_embeddings.weight.data, self.position_embeddings.weight.data,
                           self.token_type_embeddings.weight.data, cfg.cls_token_id, cfg.sep_token_id,
                           pack=pack).view(rows, H)
         mode = L.ATTN_SEQ2SEQ if seq2seq else L.ATTN_BIDIR
-        akw = dict(text_ids=mask_ids, image_mask=image_mask, obj_end=n_img + 1, pack=pack)
+        c = self._layer_ctx(mode, B, Lq, mask_ids, T, image_mask, n_img + 1, pack, seed, p_h, p_a, ops.NATIVE)
+        akw, native = c["akw"], c["native"]
         layers = []
-        native = ops.NATIVE
-        if native:
-            # one native call per BertLayer (csrc/host.cpp bert_layer_fwd): same launches, ~4 us of host time each
-            hx, st = ops.host(), ops.stream_int()
-            attn_desc = self._attn_desc(mode, B, Lq, nH, mask_ids, T, image_mask, n_img + 1, pack)
-            sd = ops.s64(seed)
-            for i, layer in enumerate(self.encoder.layer):
-                if tail_at is not None and ar.__dict__.get("_opt_tail") is not None:
-                    tail.wait_for(tail_at[i])
-                w, f, _ = self._layer_desc(ar, layer)
-                out = hx.bert_layer_fwd(x, w, f, H, cfg.intermediate_size, layer.output.LayerNorm.eps, attn_desc,
-                                        p_h, p_a, sd, i, save, st)
-                x = out[0]
-                if save:
-                    layers.append(out[1:])
-        for i, layer in enumerate(() if native else self.encoder.layer):
+        for i in range(len(self.encoder.layer)):
             if tail_at is not None and ar.__dict__.get("_opt_tail") is not None:
                 tail.wait_for(tail_at[i])
-            sa, so = layer.attention.self, layer.attention.output
-            qkv = ops.gemm(x, ar.compute(sa.query.weight, 3 * H), bias=ar.master_span(sa.query.bias, 3 * H), m_dev=rd)
-            ctx, lse = ops.attn_fwd(qkv, mode, B, Lq, nH, H // nH, (H // nH) ** -0.5,
-                                    dropout=(p_a, seed, 8 * i + 0), **akw)
-            y1 = ops.gemm(ctx, ar.compute(so.dense.weight), bias=so.dense.bias.data, dropout=(p_h, seed, 8 * i + 1),
-                          residual=x, m_dev=rd)
-            x1, m1, r1, _ = ops.layernorm_fwd(y1, so.LayerNorm.weight.data, so.LayerNorm.bias.data, so.LayerNorm.eps,
-                                              save_stats=save, rows_dev=rd)
-            h = torch.empty((rows, cfg.intermediate_size), dtype=cd, device=x.device)
-            a = ops.gemm(x1, ar.compute(layer.intermediate.dense.weight), bias=layer.intermediate.dense.bias.data,
-                         gelu=True, save_pre=h, m_dev=rd)
-            y2 = ops.gemm(a, ar.compute(layer.output.dense.weight), bias=layer.output.dense.bias.data,
-                          dropout=(p_h, seed, 8 * i + 2), residual=x1, m_dev=rd)
-            x2, m2, r2, _ = ops.layernorm_fwd(y2, layer.output.LayerNorm.weight.data, layer.output.LayerNorm.bias.data,
-                                              layer.output.LayerNorm.eps, save_stats=save, rows_dev=rd)
+            x, lsv = self._layer_fwd(ar, i, x, c, save)
             if save:
-                layers.append((x, qkv, ctx, lse, y1, m1, r1, x1, h, a, y2, m2, r2))
-            x = x2
+                layers.append(lsv)
         hidden = x.view(B, Lq, H) if pack is None else x
         pooled = cls = None
         if tail is not None and ar.__dict__.get("_opt_tail") is not None:
@@ -379,6 +348,101 @@ class MVLBert(nn.Module):
             d = ar._views[key] = (w, f, gr)
         return d
 
+    # ---- one BertLayer, forward and backward: the bodies of the loops of _forward / _backward (the tests call them directly)
+    def _layer_ctx(self, mode, B, Lq, mask_ids, T, image_mask, obj_end, pack, seed, p_h, p_a, native):
+        """What every layer of one pass shares.  _backward adds "lnq" (the deferred LayerNorm reduce of the Python path) and,
+        on the native path, "side" (the side stream's handle)."""
+        c = dict(native=native, mode=mode, B=B, Lq=Lq, seed=seed, p_h=p_h, p_a=p_a, pack=pack,
+                 rows=B * Lq if pack is None else pack[2],
+                 rd=pack[4] if (pack is not None and len(pack) > 4) else None,     # row count on the device (auto-packed batch)
+                 akw=dict(text_ids=mask_ids, image_mask=image_mask, obj_end=obj_end, pack=pack))
+        if native:
+            c.update(hx=ops.host(), st=ops.stream_int(), sd=ops.s64(seed),
+                     attn_desc=self._attn_desc(mode, B, Lq, self.config.num_attention_heads, mask_ids, T, image_mask, obj_end, pack))
+        return c
+
+    def _layer_fwd(self, ar, i, x, c, save):
+        """Layer i on the rows x [rows, H] -> (x2, saved).  saved is None without `save`, else what _layer_bwd takes:
+        native [x, qkv, ctx, lse, y1, st1, x1, h, act, y2, st2] (st = [2, rows]: mean, then rstd),
+        Python (x, qkv, ctx, lse, y1, m1, r1, x1, h, a, y2, m2, r2)."""
+        cfg = self.config
+        layer = self.encoder.layer[i]
+        H, nH = cfg.hidden_size, cfg.num_attention_heads
+        p_h, p_a, seed, rd = c["p_h"], c["p_a"], c["seed"], c["rd"]
+        if c["native"]:
+            # one native call per BertLayer (csrc/host.cpp bert_layer_fwd): same launches, ~4 us of host time each
+            w, f, _ = self._layer_desc(ar, layer)
+            out = c["hx"].bert_layer_fwd(x, w, f, H, cfg.intermediate_size, layer.output.LayerNorm.eps, c["attn_desc"],
+                                         p_h, p_a, c["sd"], i, save, c["st"])
+            return out[0], (out[1:] if save else None)
+        sa, so = layer.attention.self, layer.attention.output
+        qkv = ops.gemm(x, ar.compute(sa.query.weight, 3 * H), bias=ar.master_span(sa.query.bias, 3 * H), m_dev=rd)
+        ctx, lse = ops.attn_fwd(qkv, c["mode"], c["B"], c["Lq"], nH, H // nH, (H // nH) ** -0.5,
+                                dropout=(p_a, seed, 8 * i + 0), **c["akw"])
+        y1 = ops.gemm(ctx, ar.compute(so.dense.weight), bias=so.dense.bias.data, dropout=(p_h, seed, 8 * i + 1),
+                      residual=x, m_dev=rd)
+        x1, m1, r1, _ = ops.layernorm_fwd(y1, so.LayerNorm.weight.data, so.LayerNorm.bias.data, so.LayerNorm.eps,
+                                          save_stats=save, rows_dev=rd)
+        h = torch.empty((c["rows"], cfg.intermediate_size), dtype=x.dtype, device=x.device)
+        a = ops.gemm(x1, ar.compute(layer.intermediate.dense.weight), bias=layer.intermediate.dense.bias.data,
+                     gelu=True, save_pre=h, m_dev=rd)
+        y2 = ops.gemm(a, ar.compute(layer.output.dense.weight), bias=layer.output.dense.bias.data,
+                      dropout=(p_h, seed, 8 * i + 2), residual=x1, m_dev=rd)
+        x2, m2, r2, _ = ops.layernorm_fwd(y2, layer.output.LayerNorm.weight.data, layer.output.LayerNorm.bias.data,
+                                          layer.output.LayerNorm.eps, save_stats=save, rows_dev=rd)
+        return x2, ((x, qkv, ctx, lse, y1, m1, r1, x1, h, a, y2, m2, r2) if save else None)
+
+    def _layer_bwd(self, ar, i, saved, dx, c):
+        """Backward of layer i from what _layer_fwd saved and dx [rows, H] -> dx_in; the twelve parameter gradients go to the
+        arena (the LayerNorm ones once the deferred reduce is flushed, the weight ones on the side stream)."""
+        cfg = self.config
+        layer = self.encoder.layer[i]
+        H, nH = cfg.hidden_size, cfg.num_attention_heads
+        p_h, p_a, seed, rd = c["p_h"], c["p_a"], c["seed"], c["rd"]
+        g = ar.grad_view
+        sa, so, lo, li = layer.attention.self, layer.attention.output, layer.output, layer.intermediate
+        if c["native"]:
+            w, f, gr = self._layer_desc(ar, layer)
+            dx_in = c["hx"].bert_layer_bwd(dx, saved, w, f, gr, H, cfg.intermediate_size, c["attn_desc"], p_h, p_a, c["sd"], i,
+                                           c["st"], c["side"])
+            ar.mark(lo.LayerNorm.weight, lo.LayerNorm.bias, lo.dense.weight, lo.dense.bias, li.dense.weight,
+                    li.dense.bias, so.LayerNorm.weight, so.LayerNorm.bias, so.dense.weight, so.dense.bias,
+                    sa.query.weight, sa.key.weight, sa.value.weight, sa.query.bias, sa.key.bias, sa.value.bias)
+            return dx_in
+        lnq = c["lnq"]
+        (x, qkv, ctx, lse, y1, m1, r1, x1, h, a, y2, m2, r2) = saved
+        if p_h > 0:
+            dy2, dz2 = ops.layernorm_bwd(dx, y2, m2, r2, lo.LayerNorm.weight.data, g(lo.LayerNorm.weight),
+                                         g(lo.LayerNorm.bias), branch=dict(dropout=(p_h, seed, 8 * i + 2)), defer=lnq,
+                                         rows_dev=rd)
+        else:
+            dy2 = dz2 = ops.layernorm_bwd(dx, y2, m2, r2, lo.LayerNorm.weight.data, g(lo.LayerNorm.weight),
+                                          g(lo.LayerNorm.bias), defer=lnq, rows_dev=rd)
+        dh = ops.gemm(dz2, ar.compute(lo.dense.weight), b_kmajor=True, mul_gelu_grad=h, m_dev=rd)
+        dx1 = ops.gemm(dh, ar.compute(li.dense.weight), b_kmajor=True, residual=dy2, m_dev=rd)
+        if p_h > 0:
+            dy1, dz1 = ops.layernorm_bwd(dx1, y1, m1, r1, so.LayerNorm.weight.data, g(so.LayerNorm.weight),
+                                         g(so.LayerNorm.bias), branch=dict(dropout=(p_h, seed, 8 * i + 1)), defer=lnq,
+                                         rows_dev=rd)
+        else:
+            dy1 = dz1 = ops.layernorm_bwd(dx1, y1, m1, r1, so.LayerNorm.weight.data, g(so.LayerNorm.weight),
+                                          g(so.LayerNorm.bias), defer=lnq, rows_dev=rd)
+        dctx = ops.gemm(dz1, ar.compute(so.dense.weight), b_kmajor=True, m_dev=rd)
+        dqkv = ops.attn_bwd(dctx, qkv, ctx, lse, c["mode"], c["B"], c["Lq"], nH, H // nH, (H // nH) ** -0.5,
+                            dropout=(p_a, seed, 8 * i + 0), **c["akw"])
+        dx_in = ops.gemm(dqkv, ar.compute(sa.query.weight, 3 * H), b_kmajor=True, residual=dy1, m_dev=rd)
+        # weight / bias gradients on the side stream (off the critical path)
+        xtra = () if rd is None else (rd,)
+        with ops.on_side(dx.device, dz2, a, dh, x1, dz1, ctx, dqkv, x):
+            ops.wgrad_group([(dz2, a, g(lo.dense.weight), g(lo.dense.bias)) + xtra,
+                             (dh, x1, g(li.dense.weight), g(li.dense.bias)) + xtra,
+                             (dz1, ctx, g(so.dense.weight), g(so.dense.bias)) + xtra,
+                             (dqkv, x, g(sa.query.weight, 3 * H), g(sa.query.bias, 3 * H)) + xtra])
+        ar.mark(lo.LayerNorm.weight, lo.LayerNorm.bias, lo.dense.weight, lo.dense.bias, li.dense.weight,
+                li.dense.bias, so.LayerNorm.weight, so.LayerNorm.bias, so.dense.weight, so.dense.bias,
+                sa.query.weight, sa.key.weight, sa.value.weight, sa.query.bias, sa.key.bias, sa.value.bias)
+        return dx_in
+
     def _backward(self, sv, dhidden, dpooled):
         ar: Arena = sv["ar"]
         backward_begin(ar)
@@ -386,10 +450,8 @@ class MVLBert(nn.Module):
         g = ar.grad_view
         cfg = self.config
         B, Lq, H = sv["B"], sv["Lq"], cfg.hidden_size
-        nH = cfg.num_attention_heads
         seed, p_h, p_a = sv["seed"], sv["p_h"], sv["p_a"]
         pack, rows = sv["pack"], sv["rows"]
-        rd = pack[4] if (pack is not None and len(pack) > 4) else None
         if dhidden is None:                      # only the pooled output was used (VQA / retrieval heads)
             dx = torch.zeros((rows, H), dtype=sv["layers"][0][0].dtype, device=sv["layers"][0][0].device)
             dhidden = dx.new_empty(0)
@@ -408,58 +470,18 @@ class MVLBert(nn.Module):
                 dx.index_add_(0, pack[3], ops.gemm(dpre, ar.compute(pd.weight), b_kmajor=True))
             ar.mark(pd.weight, pd.bias)
         native = sv.get("native", False)
+        akw = sv["akw"]
+        c = self._layer_ctx(sv["mode"], B, Lq, akw["text_ids"], sv["T"], akw["image_mask"], akw["obj_end"], pack, seed, p_h, p_a,
+                            native)
+        c["lnq"] = lnq
         if native:
-            hx, st, side = ops.host(), ops.stream_int(), ops.side_int(dx.device)
-            akw = sv["akw"]
-            attn_desc = self._attn_desc(sv["mode"], B, Lq, nH, akw["text_ids"], sv["T"], akw["image_mask"], akw["obj_end"], pack)
-            sd = ops.s64(seed)
-            for i in range(len(self.encoder.layer) - 1, -1, -1):
-                layer = self.encoder.layer[i]
-                sa, so, lo, li = layer.attention.self, layer.attention.output, layer.output, layer.intermediate
-                w, f, gr = self._layer_desc(ar, layer)
-                dx = hx.bert_layer_bwd(dx, sv["layers"][i], w, f, gr, H, cfg.intermediate_size, attn_desc, p_h, p_a, sd, i,
-                                       st, side)
+            c["side"] = ops.side_int(dx.device)
+        for i in range(len(self.encoder.layer) - 1, -1, -1):
+            dx = self._layer_bwd(ar, i, sv["layers"][i], dx, c)
+            if native:
                 sv["layers"][i] = None
-                ar.mark(lo.LayerNorm.weight, lo.LayerNorm.bias, lo.dense.weight, lo.dense.bias, li.dense.weight,
-                        li.dense.bias, so.LayerNorm.weight, so.LayerNorm.bias, so.dense.weight, so.dense.bias,
-                        sa.query.weight, sa.key.weight, sa.value.weight, sa.query.bias, sa.key.bias, sa.value.bias)
-            hx.lnq_flush(st)
-        for i in range(len(self.encoder.layer) - 1, -1, -1) if not native else ():
-            layer = self.encoder.layer[i]
-            sa, so = layer.attention.self, layer.attention.output
-            (x, qkv, ctx, lse, y1, m1, r1, x1, h, a, y2, m2, r2) = sv["layers"][i]
-            lo, li = layer.output, layer.intermediate
-            if p_h > 0:
-                dy2, dz2 = ops.layernorm_bwd(dx, y2, m2, r2, lo.LayerNorm.weight.data, g(lo.LayerNorm.weight),
-                                             g(lo.LayerNorm.bias), branch=dict(dropout=(p_h, seed, 8 * i + 2)), defer=lnq,
-                                             rows_dev=rd)
-            else:
-                dy2 = dz2 = ops.layernorm_bwd(dx, y2, m2, r2, lo.LayerNorm.weight.data, g(lo.LayerNorm.weight),
-                                              g(lo.LayerNorm.bias), defer=lnq, rows_dev=rd)
-            dh = ops.gemm(dz2, ar.compute(lo.dense.weight), b_kmajor=True, mul_gelu_grad=h, m_dev=rd)
-            dx1 = ops.gemm(dh, ar.compute(li.dense.weight), b_kmajor=True, residual=dy2, m_dev=rd)
-            if p_h > 0:
-                dy1, dz1 = ops.layernorm_bwd(dx1, y1, m1, r1, so.LayerNorm.weight.data, g(so.LayerNorm.weight),
-                                             g(so.LayerNorm.bias), branch=dict(dropout=(p_h, seed, 8 * i + 1)), defer=lnq,
-                                             rows_dev=rd)
-            else:
-                dy1 = dz1 = ops.layernorm_bwd(dx1, y1, m1, r1, so.LayerNorm.weight.data, g(so.LayerNorm.weight),
-                                              g(so.LayerNorm.bias), defer=lnq, rows_dev=rd)
-            dctx = ops.gemm(dz1, ar.compute(so.dense.weight), b_kmajor=True, m_dev=rd)
-            dqkv = ops.attn_bwd(dctx, qkv, ctx, lse, sv["mode"], B, Lq, nH, H // nH, (H // nH) ** -0.5,
-                                dropout=(p_a, seed, 8 * i + 0), **sv["akw"])
-            dx_in = ops.gemm(dqkv, ar.compute(sa.query.weight, 3 * H), b_kmajor=True, residual=dy1, m_dev=rd)
-            # weight / bias gradients on the side stream (off the critical path)
-            xtra = () if rd is None else (rd,)
-            with ops.on_side(dx.device, dz2, a, dh, x1, dz1, ctx, dqkv, x):
-                ops.wgrad_group([(dz2, a, g(lo.dense.weight), g(lo.dense.bias)) + xtra,
-                                 (dh, x1, g(li.dense.weight), g(li.dense.bias)) + xtra,
-                                 (dz1, ctx, g(so.dense.weight), g(so.dense.bias)) + xtra,
-                                 (dqkv, x, g(sa.query.weight, 3 * H), g(sa.query.bias, 3 * H)) + xtra])
-            dx = dx_in
-            ar.mark(lo.LayerNorm.weight, lo.LayerNorm.bias, lo.dense.weight, lo.dense.bias, li.dense.weight,
-                    li.dense.bias, so.LayerNorm.weight, so.LayerNorm.bias, so.dense.weight, so.dense.bias,
-                    sa.query.weight, sa.key.weight, sa.value.weight, sa.query.bias, sa.key.bias, sa.value.bias)
+        if native:
+            c["hx"].lnq_flush(c["st"])
         lnq.flush()
         # ---- embeddings: dense f32 table gradients, like nn.Embedding in the reference
         we, pe, te = self.word_embeddings.weight, self.position_embeddings.weight, self.token_type_embeddings.weight
