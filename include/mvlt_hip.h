@@ -904,6 +904,27 @@ typedef struct MvltMlmMask {
 } MvltMlmMask;
 int mvlt_mlm_mask(const MvltMlmMask* p, void* stream);
 
+/* Fused fine-tuning image transform: Pillow-exact resize evaluated at the pixels of an O x O crop only, optional horizontal
+ * flip, and ToTensor + Normalize as a table lookup -- the torchvision pipelines of run_report_generation_cxr.py:24-36 and
+ * run_retrieval_iuxray.py:52-65 and the PIL resize of run_pretrain_rgc_roco_medicat.py:103-106, one launch per batch of B
+ * ragged uint8 HWC RGB sources.  Image b is the hw[2b] x hw[2b+1] x 3 bytes at src + src_off[b].  Per image and axis
+ * (0 = horizontal, 1 = vertical) and per output index t < O the host supplies Pillow's tap table: bounds [B,2,O,2] =
+ * (first source index, tap count in 1 .. kmax) and coef [B,2,O,kmax] (22-bit fixed point; taps past the count MUST be 0), already restricted to
+ * the crop's columns and rows.  With X = flip[b] ? O-1-x : x:
+ *     H[r][X]   = clip8((2^21 + sum_i coef[b][0][X][i] * src_b[r][first_X + i]) >> 22)       (rounded to uint8, as Pillow does)
+ *     v[y][x]   = clip8((2^21 + sum_j coef[b][1][y][j] * H[first_y + j][X]) >> 22)
+ *     MVLT_IMGXF_F32_CHW: out f32 [B,3,O,O] = lut[c][v]     (lut f32 [3,256], e.g. (k/255 - mean_c) / std_c built by the caller)
+ *     MVLT_IMGXF_U8_HWC:  out uint8 [B,O,O,3] = v           (lut unused, may be NULL)
+ * Integer arithmetic throughout: the result is bit-identical to Pillow's Image.resize + crop + flip (and to torch's own
+ * arithmetic through the table).  All pointers are device memory.  The kernel TRUSTS the tables: first + count must not pass the
+ * source axis and count must not pass kmax -- the caller checks that before it uploads them (data.py: plan_image_transform).
+ * The arguments are scalars, not a struct: the struct registry (MVLT_STRUCT_COUNT) and MVLT_ABI_VERSION stay as they are.
+ * MVLT_ERR_ARG (nothing launched): a NULL pointer (lut only for MVLT_IMGXF_F32_CHW), B outside 1 .. 65535, kmax outside
+ * 1 .. 65, out_size outside 8 .. 224 or not a multiple of 8, an unknown mode, out not 16-byte aligned. */
+enum { MVLT_IMGXF_F32_CHW = 0, MVLT_IMGXF_U8_HWC = 1 };
+int mvlt_image_transform(const uint8_t* src, const int64_t* src_off, const int32_t* hw, const int32_t* bounds, const int32_t* coef,
+                         const uint8_t* flip, const float* lut, void* out, int B, int out_size, int kmax, int mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

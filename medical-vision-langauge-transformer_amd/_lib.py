@@ -18,6 +18,7 @@ EPI_BIAS, EPI_GELU, EPI_SAVE_PRE, EPI_DROPOUT = 1, 2, 4, 8
 EPI_ROWSCALE, EPI_RESIDUAL, EPI_ROWMAP, EPI_MUL_GELU_GRAD = 16, 32, 64, 128
 EPI_OUT_F32, EPI_ACCUM, EPI_TAIL = 256, 512, 1024
 ATTN_SWIN, ATTN_BIDIR, ATTN_SEQ2SEQ = 0, 1, 2
+IMGXF_F32_CHW, IMGXF_U8_HWC = 0, 1
 # enum MvltAttnRoute (mvlt_attn_route)
 ATTN_ROUTES = ("UNSUPPORTED", "SWIN_FWD", "BERT_FWD_KT5", "BERT_FWD_KT9", "BERT_FWD_KT13", "SWIN_BWD_KS0", "SWIN_BWD_KS3",
                "SWIN_BWD_KS6", "SWIN_BWD_KS12", "SWIN_BWD", "BERT_BWD2_NW5", "BERT_BWD2_NW6", "BERT_BWD_SPLIT_KT5",
@@ -278,6 +279,7 @@ SYMBOLS = {
     "mvlt_prefetch": (i32, [C.POINTER(MvltRange), i32, vp]),
     "mvlt_image_normalize": (i32, [vp, vp, i32, i32, i32, vp]),
     "mvlt_mlm_mask": (i32, [C.POINTER(MvltMlmMask), vp]),
+    "mvlt_image_transform": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
 }
 
 # ctypes mirror of every struct, in the order of the MVLT_STRUCT_* ids of the header
