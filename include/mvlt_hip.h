@@ -544,6 +544,25 @@ int mvlt_attn_route(const MvltAttn* p, int bwd);
  * MVLT_ATTN_ROUTE_SWIN_BWD_KS3 / 6 / 12, answered by that same route function: callers ask before they choose between
  * dout_weight and a separate projection dgrad. */
 int mvlt_swin_bwd_proj_supported(int dtype, int nseq, int nH, int hd, int shift);
+/* Attention maps (MVLBert modes): the probabilities mvlt_attn_fwd never materialises, recomputed from the call's qkv and the lse
+ * it wrote (HF BertSelfAttention's attention_probs, modeling_bert.py:130, what output_attentions returns), eval mode:
+ *     out[s, h, i, j] = exp(scale * q_{q0+i} . k_{k0+j} + bias(q0+i, k0+j) - lse[s, h, q0+i])        f32 [nseq, nH, nq, nk]
+ * for the queries [q0, q0 + nq) and the keys [k0, k0 + nk) of every sequence; bias is the additive term of the forward (BIDIR:
+ * -10000 on padded text keys and on image_mask == 0; SEQ2SEQ: -10000 unless k <= q or k <= obj_end), so masked entries are
+ * exactly 0.  *p is the descriptor of that layer's forward call: dtype, mode, nseq, L, nH, hd, qkv, scale, text_ids / T /
+ * image_mask / obj_end, row_start / seq_len are read, and lse (written by the forward); out, the dropout and the backward
+ * fields are ignored.  The forward's arithmetic: operands in the compute dtype, f32 accumulation over hd, __expf.
+ * Packed rows: keys >= seq_len[s] are exactly 0, query rows >= seq_len[s] are rows of zeros (their lse is not read), activation
+ * rows outside every sequence are not read.
+ * flags: MVLT_ATTNMAP_HEAD_MEAN -- out is [nseq, 1, nq, nk], the mean over heads (summed in head order inside one workgroup);
+ *        MVLT_ATTNMAP_RENORM    -- every OUTPUT row (after the head mean, if both are set) is divided by its own sum over the
+ *                                  selected keys: the attention within the key range; a row whose sum is 0 stays 0.
+ * One launch, no atomics.  The arguments are scalars and an existing struct: the struct registry and MVLT_ABI_VERSION stay.
+ * MVLT_ERR_ARG (nothing launched): a NULL p / qkv / lse / out, unknown flag bits, a range outside [0, L], nq <= 0 or nk <= 0,
+ * the mode checks of mvlt_attn_fwd, qkv not 16-byte aligned.  MVLT_ERR_UNSUPPORTED: MVLT_ATTN_SWIN, hd != 64, nk > 208 (the
+ * forward's own L range), a dtype other than bf16 / f32. */
+enum { MVLT_ATTNMAP_HEAD_MEAN = 1, MVLT_ATTNMAP_RENORM = 2 };
+int mvlt_attn_probs(const MvltAttn* p, int q0, int nq, int k0, int nk, int flags, float* out, void* stream);
 
 /* ------------------------------------------------------------------ fused Swin (S)W-MSA (SURVEY.md 8b `swin_wmsa`)
  * The attention half of SwinTransformerBlock.forward in ONE launch (visual_feature_extractor.py:356-384 around

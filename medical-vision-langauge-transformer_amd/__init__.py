@@ -26,6 +26,8 @@ from .model import (Conv_layer, MVLBertConfig, MVLBertConfigforVQA, MVLBertConfi
                     MVLBertPretrainConfig, MVLBertRetrieval)
 from . import retrieval  # noqa: F401
 from .retrieval import evaluate, recall_ranks, score_all_pairs  # noqa: F401
+from . import attention  # noqa: F401
+from .attention import image_heatmap  # noqa: F401
 from . import data  # noqa: F401
 from .data import (CaptionBatches, ImageStore, PretrainBatches, plan_image_transform, resize_coeffs,  # noqa: F401
                    transform_images, write_image_store)

@@ -18,6 +18,7 @@ EPI_BIAS, EPI_GELU, EPI_SAVE_PRE, EPI_DROPOUT = 1, 2, 4, 8
 EPI_ROWSCALE, EPI_RESIDUAL, EPI_ROWMAP, EPI_MUL_GELU_GRAD = 16, 32, 64, 128
 EPI_OUT_F32, EPI_ACCUM, EPI_TAIL = 256, 512, 1024
 ATTN_SWIN, ATTN_BIDIR, ATTN_SEQ2SEQ = 0, 1, 2
+ATTNMAP_HEAD_MEAN, ATTNMAP_RENORM = 1, 2
 IMGXF_F32_CHW, IMGXF_U8_HWC = 0, 1
 # enum MvltAttnRoute (mvlt_attn_route)
 ATTN_ROUTES = ("UNSUPPORTED", "SWIN_FWD", "BERT_FWD_KT5", "BERT_FWD_KT9", "BERT_FWD_KT13", "SWIN_BWD_KS0", "SWIN_BWD_KS3",
@@ -229,6 +230,7 @@ SYMBOLS = {
     "mvlt_attn_bwd_ev": (i32, [C.POINTER(MvltAttn), vp, vp]),
     "mvlt_attn_route": (i32, [C.POINTER(MvltAttn), i32]),
     "mvlt_swin_bwd_proj_supported": (i32, [i32, i32, i32, i32, i32]),
+    "mvlt_attn_probs": (i32, [C.POINTER(MvltAttn), i32, i32, i32, i32, i32, vp, vp]),
     "mvlt_swin_wmsa_supported": (i32, [i32, i32, i32]),
     "mvlt_swin_wmsa_fwd": (i32, [C.POINTER(MvltSwinWmsa), vp]),
     "mvlt_swin_wmsa2_supported": (i32, [i32, i32, i32, i32, i32]),

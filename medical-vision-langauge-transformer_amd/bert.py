@@ -176,6 +176,49 @@ class MVLBert(nn.Module):
             return (hidden[:, obj_end + 1:text_end], hidden[:, 1:obj_end], pooler_output, hidden[:, obj_end])
         return EncoderOutput(hidden), pooler_output
 
+    # ------------------------------------------------------------------ attention maps (HF output_attentions)
+    @torch.no_grad()
+    def attention_maps(self, text_idx, image_feature, image_mask=None, seq2seq_mask=False, layers=None,
+                       queries='cls', keys='image', head_mean=True, renorm=False):
+        """Where the model looked: (maps f32 [n_layers_selected, B, nH or 1, nq, nk], hidden [B, L, H], pooled or None).
+        maps[l, b, h, i, j] is the attention probability (modeling_bert.py:130, HF ``output_attentions``) of query position
+        i on key position j in selected layer l; ``head_mean`` averages the heads, ``renorm`` divides every row by its sum
+        over the selected keys (the attention within, say, the image tokens).  ``queries`` / ``keys``: 'cls' | 'image' | 'sep'
+        | 'text' | 'all' or an explicit (start, count) (attention.resolve_range); ``layers``: indices, negative allowed, None =
+        every layer.  hidden / pooled are what ``forward`` returns for the same inputs -- the same launches, with each
+        selected layer's qkv and lse handed to mvlt_attn_probs before the next layer runs.  Eval mode only: with dropout the
+        saved lse is not that of the probabilities that were applied.  Dense layout."""
+        from .attention import resolve_layers, resolve_range
+        if self.training:
+            raise ValueError("attention_maps needs eval mode: with attention dropout the saved softmax statistics are not "
+                             "those of the probabilities that were applied")
+        if not image_feature.is_cuda:
+            raise RuntimeError("mvlt_amd runs on the GPU only (no CPU fallback)")
+        cfg = self.config
+        cd = compute_dtype_of(self)
+        B, n_img, _ = image_feature.shape
+        T = 0 if text_idx is None else text_idx.shape[1]
+        sel = resolve_layers(layers, len(self.encoder.layer))
+        qr, kr = resolve_range(queries, n_img, T), resolve_range(keys, n_img, T)
+        nH = cfg.num_attention_heads
+        hd = cfg.hidden_size // nH
+        if text_idx is not None:
+            text_idx = text_idx.contiguous()
+        im_u8 = None if image_mask is None else (image_mask != 0).to(torch.uint8).contiguous()
+        feat = image_feature if image_feature.dtype == cd else image_feature.to(cd)
+        maps = torch.empty((len(sel), B, 1 if head_mean else nH, qr[1], kr[1]), dtype=torch.float32,
+                           device=image_feature.device)
+
+        def tap(i, saved, c):                    # saved[1] = qkv, saved[3] = lse on both host paths (_layer_fwd)
+            for slot, layer in enumerate(sel):
+                if layer == i:
+                    ops.attn_probs(saved[1], saved[3], c["mode"], B, c["Lq"], nH, hd, hd ** -0.5, qr, kr,
+                                   head_mean=head_mean, renorm=renorm, out=maps[slot], **c["akw"])
+
+        with ops.pin_stream():
+            hidden, pooled, _ = self._forward(feat.contiguous(), text_idx, text_idx, im_u8, bool(seq2seq_mask), False, tap=tap)
+        return maps, hidden, (pooled if self.pooler is not None else None)
+
     # ------------------------------------------------------------------ packed rows (pre-training fast path)
     def forward_packed(self, text_idx, image_feature, text_lengths, seq2seq_mask=False):
         """Same encoder on PACKED rows: sample b keeps positions [0, n_img + 2 + text_lengths[b]) and its
@@ -263,7 +306,9 @@ class MVLBert(nn.Module):
         return hidden, pooled, trow
 
     # ------------------------------------------------------------------ engine
-    def _forward(self, feat, text_idx, mask_ids, image_mask, seq2seq, save, pack=None, pool=True):
+    def _forward(self, feat, text_idx, mask_ids, image_mask, seq2seq, save, pack=None, pool=True, tap=None):
+        """``tap`` (attention_maps): called as tap(i, saved_i, ctx) right after layer i with what _layer_fwd saves; the layer's
+        saved tensors are then dropped, so at most one layer's activations are alive.  Needs save = False."""
         cfg = self.config
         cd = feat.dtype
         ar = Arena.of(self, cd)
@@ -296,8 +341,10 @@ class MVLBert(nn.Module):
         for i in range(len(self.encoder.layer)):
             if tail_at is not None and ar.__dict__.get("_opt_tail") is not None:
                 tail.wait_for(tail_at[i])
-            x, lsv = self._layer_fwd(ar, i, x, c, save)
-            if save:
+            x, lsv = self._layer_fwd(ar, i, x, c, save or tap is not None)
+            if tap is not None:
+                tap(i, lsv, c)
+            elif save:
                 layers.append(lsv)
         hidden = x.view(B, Lq, H) if pack is None else x
         pooled = cls = None

@@ -627,6 +627,26 @@ class MVLBertForVQA(MVLBertPretrainedModel):
             prob = ops.softmax_rows(logits.contiguous(), logits.shape[1])
         return prob, logits
 
+    @torch.no_grad()
+    def attention_maps(self, image, question, image_mask=None, **sel):
+        """(prob, logits, maps): the answer of ``forward`` and where the encoder looked while it formed it.  ``sel``: layers,
+        queries, keys, head_mean, renorm of ``MVLBert.attention_maps`` (default: [CLS] -> image tokens, mean over heads, every
+        layer; ``attention.image_heatmap`` turns the last axis into the 7 x 7 grid).  Eval mode only."""
+        _maps_need_eval(self)
+        Arena.of(self, compute_dtype_of(self))
+        image_feature = self.conv(image)
+        maps, _, pooled = self.MVLBert.attention_maps(question, image_feature, image_mask=image_mask, **sel)
+        lin = self.final_mlp[1]
+        logits = _LinearFn.apply(_token(lin, pooled.device), pooled, lin, 0.0, False)
+        prob = ops.softmax_rows(logits.contiguous(), logits.shape[1])
+        return prob, logits, maps
+
+
+def _maps_need_eval(model):
+    if model.training:
+        raise ValueError("attention_maps needs eval mode: with dropout the saved softmax statistics are not those of the "
+                         "probabilities that were applied")
+
 
 class MVLBertForRetrieval(MVLBertPretrainedModel):
     """model.py:423-476: transform (dense+GELU+LN) + Linear(768,2)."""
@@ -649,6 +669,18 @@ class MVLBertForRetrieval(MVLBertPretrainedModel):
             with torch.no_grad():
                 return ops.softmax_rows(logits.contiguous(), logits.shape[1])
         return logits
+
+    @torch.no_grad()
+    def attention_maps(self, image, caption, image_mask=None, **sel):
+        """(prob, maps): the match probabilities of ``forward(image, caption)`` and the encoder's attention maps
+        (``MVLBert.attention_maps``; default [CLS] -> image tokens, mean over heads, every layer).  Eval mode only."""
+        _maps_need_eval(self)
+        Arena.of(self, compute_dtype_of(self))
+        image_feature = self.conv(image)
+        maps, _, pooled = self.MVLBert.attention_maps(caption, image_feature, image_mask=image_mask, **sel)
+        tr, lin = self.final_mlp[0], self.final_mlp[1]
+        logits = _TransformLinearFn.apply(_token(lin, pooled.device), pooled, tr, lin, False)
+        return ops.softmax_rows(logits.contiguous(), logits.shape[1]), maps
 
     # ---- all-pairs scoring (retrieval.py): the image tower once per image, one packed encoder pass per chunk of pairs
     def _check_eval(self, what):
@@ -821,6 +853,20 @@ class MVLBertForImageCaption(MVLBertPretrainedModel):
         if learning_strategy == 'normal':
             return self.MLM_head_seq2seq(torch.cat([sep_out[:, None], text_out[:, :-1]], dim=1)).transpose(1, 2)
         raise NotImplementedError("learning_strategy:", learning_strategy, "is not implemented! Try 'unilm' or 'normal'.")
+
+    @torch.no_grad()
+    def attention_maps(self, image, caption, learning_strategy='unilm', **sel):
+        """maps: the encoder's attention in the teacher-forced pass over ``caption`` (int64 [B, T], e.g. what ``generate``
+        returned) under the seq2seq mask -- for 'unilm' the numbers the KV-cache loop computes token by token.  Default
+        selection ``queries='text'``: report position -> image tokens, mean over heads, every layer
+        (``MVLBert.attention_maps``).  The masks do not depend on ``learning_strategy`` (it only moves the rows the MLM head
+        reads), so neither do the maps; it is checked as in ``encode_forward``.  Eval mode only."""
+        _maps_need_eval(self)
+        if learning_strategy not in ('unilm', 'normal'):
+            raise NotImplementedError("learning_strategy:", learning_strategy, "is not implemented! Try 'unilm' or 'normal'.")
+        sel.setdefault('queries', 'text')
+        Arena.of(self, compute_dtype_of(self))
+        return self.MVLBert.attention_maps(caption, self.conv(image), seq2seq_mask=True, **sel)[0]
 
     # ---- training loss and token scoring: the head runs on gathered rows and never hands logits to torch
     def _head_rows(self, image_feature, caption, learning_strategy):

@@ -975,6 +975,26 @@ def attn_fwd(qkv, mode, nseq, Lq, nH, hd, scale, out=None, lse=None, **kw):
     return out, lse
 
 
+def attn_probs(qkv, lse, mode, nseq, Lq, nH, hd, scale, q_range, k_range, head_mean=False, renorm=False, out=None, **kw):
+    """Attention maps (mvlt_attn_probs): f32 [nseq, nH or 1, nq, nk], exp(scale q.k + mask - lse) for the queries
+    q_range = (q0, nq) and the keys k_range = (k0, nk) of every sequence, from the qkv / lse of an eval-mode attn_fwd call with
+    the same mode and keywords (text_ids, image_mask, obj_end, pack).  head_mean: the mean over heads; renorm: every output row
+    divided by its sum over the selected keys.  out: optional caller buffer (one allocation can hold every layer)."""
+    _need_cuda(qkv, lse)
+    rows = nseq * Lq if kw.get("pack") is None else kw["pack"][2]
+    assert qkv.is_contiguous() and qkv.shape == (rows, 3 * nH * hd)
+    assert lse.is_contiguous() and lse.dtype == torch.float32 and lse.shape == (nseq, nH, Lq)
+    (q0, nq), (k0, nk) = (int(v) for v in q_range), (int(v) for v in k_range)
+    shape = (nseq, 1 if head_mean else nH, nq, nk)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=qkv.device)
+    assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.shape == shape
+    p = _attn_struct(qkv, None, lse, mode, nseq, Lq, nH, hd, scale, **kw)
+    flags = (L.ATTNMAP_HEAD_MEAN if head_mean else 0) | (L.ATTNMAP_RENORM if renorm else 0)
+    L.check(L.lib().mvlt_attn_probs(C.byref(p), q0, nq, k0, nk, flags, _p(out), _stream()), "mvlt_attn_probs")
+    return out
+
+
 def swin_bwd_proj_supported(dtype, nseq, nH, hd, shift):
     """MvltAttn.dout_weight (the output projection's dgrad inside the Swin attention backward): what the dispatch itself answers."""
     return bool(L.lib().mvlt_swin_bwd_proj_supported(_DT[dtype], nseq, nH, hd, shift))
