@@ -381,6 +381,40 @@ int mvlt_recall_ranks(const float* scores, int64_t ld, int Ni, int Nc, const int
  * a DEVICE int32 [nk], overwritten.  One workgroup, fixed order. */
 int mvlt_recall_counts(const int32_t* rank, int n, const int32_t* ks, int nk, int32_t* counts, void* stream);
 
+/* Report metrics (compute_scores of run_report_generation_cxr.py:274-312 -- BLEU-1..4, ROUGE-L, CIDEr -- on WordPiece id rows in
+ * place of the strings that test() :335-349 builds on the host).  A row int64 [T <= 512] ends before its first id that is one of
+ * the n_stop (0 .. 8) ids of the HOST array stop_ids, or at T.  flags: DEVICE uint8 [V], bit 1 CONT (the piece glues to the
+ * previous one, "##..."), bit 2 JOIN ("-", the .replace(' - ', '-') of :346), bit 4 BREAK (".", the .replace('.', ' .') of
+ * :290-291); NULL: every id is a word.  An id outside [0, V) has flags 0 and never indexes the table.  With n pieces left,
+ * JOIN piece i glues to its left when 0 < i < n - 1, piece i + 1 is not CONT and piece i was not itself pulled by a gluing
+ * piece i - 1; it then pulls piece i + 1.  Piece i starts a word when i == 0, else when it is BREAK, else not when it is CONT,
+ * pulled or gluing, else it does.  A word is its sequence of piece ids, an n-gram its sequence of words; both are compared
+ * through 64-bit keys: mix = the splitmix64 finaliser, fold(h, v) = mix(h + 0x9E3779B97F4A7C15 + v), a word = fold over its ids
+ * from 0x243F6A8885A308D3, an n-gram of order n = fold over its word keys from 0x13198A2E03707344 + n, read as int64;
+ * INT64_MAX is "no key" (a key equal to it becomes INT64_MAX - 1).  Two different n-grams among K collide with probability
+ * about K^2 / 2^65.
+ *
+ * mvlt_report_ngram_keys: one workgroup per row of ids [rows, ld >= T]; keys int64 [rows, 4, T]: slot j of order n holds the key
+ * of the row's j-th n-gram when it is the first occurrence in the row, INT64_MAX otherwise (duplicates, unused slots);
+ * n_words int32 [rows].  Sorting all keys and counting equal neighbours gives the document frequency of CiderScorer.compute_doc_freq.
+ *
+ * mvlt_report_stats: one workgroup per row of hyp [rows, ldh >= Th], scored against row index[row] (int32, NULL: row itself,
+ * rows <= N) of ref [N, ldr >= Tr]; an index outside [0, N) scores against an empty reference and reports its length as -1.
+ * stats int32 [rows, 11] = hypothesis words, reference words, correct[4] (sum over the distinct hypothesis n-grams of min(count
+ * in hypothesis, count in reference)), guess[4] (max(0, words - n + 1)), LCS length over words.  cider f64 [rows] follows
+ * CiderScorer.compute_cider with one reference: tf-idf = count * (log N - log max(1, df)), df from the sorted table df_keys int64
+ * [K] / df_counts int32 [K] by binary search (absent: 0); per order sum over the distinct hypothesis n-grams of min(h, r) * r,
+ * divided by sqrt(sum h^2) * sqrt(sum r^2) when both are non-zero, times exp(-d^2 / 72) with d the difference of the two bigram
+ * counts; the mean of the four orders times 10.  f64 throughout, every sum in a fixed order (no atomics): two runs agree bit
+ * for bit.  All pointers but stop_ids are device memory.  Scalar arguments only: the struct registry and MVLT_ABI_VERSION stay.
+ * MVLT_ERR_ARG (nothing launched): a NULL required pointer, rows or N < 1, T outside 1 .. 512, ld < T, n_stop outside 0 .. 8,
+ * flags with V < 1, K < 0, K > 0 without tables, index NULL with rows > N, misaligned pointers. */
+int mvlt_report_ngram_keys(const int64_t* ids, int64_t ld, int rows, int T, const uint8_t* flags, int V, const int64_t* stop_ids,
+                           int n_stop, int64_t* keys, int32_t* n_words, void* stream);
+int mvlt_report_stats(const int64_t* hyp, int64_t ldh, int rows, int Th, const int64_t* ref, int64_t ldr, int N, int Tr,
+                      const int32_t* index, const uint8_t* flags, int V, const int64_t* stop_ids, int n_stop, const int64_t* df_keys,
+                      const int32_t* df_counts, int K, int32_t* stats, double* cider, void* stream);
+
 /* Decode step (model.py:82-108: 2 new tokens per sample): skinny product with the reduction split over workgroups:
  * acc[s][M][N] (f32, k_splits slabs) = A[:, k-slice s] B[:, k-slice s]^T, M <= 64, both operands k-contiguous, no epilogue;
  * k_splits workgroups share every 16-column tile, each WRITES the slab of its slice (plain stores: no float atomics, nothing

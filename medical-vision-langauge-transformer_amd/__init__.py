@@ -26,6 +26,8 @@ from .model import (Conv_layer, MVLBertConfig, MVLBertConfigforVQA, MVLBertConfi
                     MVLBertPretrainConfig, MVLBertRetrieval)
 from . import retrieval  # noqa: F401
 from .retrieval import evaluate, recall_ranks, score_all_pairs  # noqa: F401
+from . import report_metrics  # noqa: F401
+from .report_metrics import ReferenceSet, ReportScorer, word_flags  # noqa: F401  (evaluate / score: report_metrics.evaluate)
 from . import attention  # noqa: F401
 from .attention import image_heatmap  # noqa: F401
 from . import data  # noqa: F401

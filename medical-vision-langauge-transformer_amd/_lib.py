@@ -216,6 +216,8 @@ SYMBOLS = {
     "mvlt_retrieval_head": (i32, [C.POINTER(MvltRetrievalHead), vp]),
     "mvlt_recall_ranks": (i32, [vp, i64, i32, i32, vp, vp, vp, vp, vp]),
     "mvlt_recall_counts": (i32, [vp, i32, C.POINTER(i32), i32, vp, vp]),
+    "mvlt_report_ngram_keys": (i32, [vp, i64, i32, i32, vp, i32, C.POINTER(i64), i32, vp, vp, vp]),
+    "mvlt_report_stats": (i32, [vp, i64, i32, i32, vp, i64, i32, i32, vp, vp, i32, C.POINTER(i64), i32, vp, vp, i32, vp, vp, vp]),
     "mvlt_gemm_skinny_accum": (i32, [C.POINTER(MvltGemm), vp, i32, vp]),
     "mvlt_layernorm_acc_fwd": (i32, [i32, vp, i32, vp, vp, vp, vp, f32, i32, i32, vp, vp]),
     "mvlt_colsum": (i32, [i32, vp, i64, i32, i32, vp, i32, vp, vp]),

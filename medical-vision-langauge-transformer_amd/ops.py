@@ -676,6 +676,62 @@ def recall_counts(rank, ks, out=None):
     return out
 
 
+REPORT_MAX_PIECES = 512          # a row of mvlt_report_ngram_keys / mvlt_report_stats (BERT's position limit)
+
+
+def _report_rows(ids, what):
+    assert ids.dim() == 2 and ids.dtype == torch.int64 and ids.stride(1) == 1 and ids.shape[0] > 0, f"{what}: int64 [rows, T]"
+    if not 0 < ids.shape[1] <= REPORT_MAX_PIECES:
+        raise ValueError(f"{what}: a row holds {ids.shape[1]} pieces, the kernels take 1 .. {REPORT_MAX_PIECES}")
+
+
+def _report_common(flags, stop_ids):
+    if flags is not None:
+        assert flags.dtype == torch.uint8 and flags.dim() == 1 and flags.is_contiguous() and flags.numel() > 0
+    stops = [int(s) for s in stop_ids]
+    if len(stops) > 8:
+        raise ValueError("at most 8 stop ids")
+    return (C.c_int64 * max(len(stops), 1))(*stops), len(stops), (flags.numel() if flags is not None else 0)
+
+
+def report_ngram_keys(ids, flags, stop_ids):
+    """(keys int64 [rows, 4, T], n_words int32 [rows]): the distinct n-grams of every row as 64-bit keys, INT64_MAX elsewhere
+    (mvlt_report_ngram_keys)."""
+    _need_cuda(ids, flags)
+    _report_rows(ids, "ids")
+    arr, ns, V = _report_common(flags, stop_ids)
+    rows, T = ids.shape
+    keys = torch.empty((rows, 4, T), dtype=torch.int64, device=ids.device)
+    n_words = torch.empty(rows, dtype=torch.int32, device=ids.device)
+    L.check(L.lib().mvlt_report_ngram_keys(_p(ids), _ld(ids), rows, T, _p(flags), V, arr, ns, _p(keys), _p(n_words), _stream()),
+            "mvlt_report_ngram_keys")
+    return keys, n_words
+
+
+def report_stats(hyp, ref, index, flags, stop_ids, df_keys, df_counts):
+    """(stats int32 [rows, 11], cider f64 [rows]) of hyp [rows, Th] against ref[index] (ref [N, Tr]; index int32 [rows] or None:
+    row i against reference i); see mvlt_report_stats."""
+    _need_cuda(hyp, ref, index, flags, df_keys, df_counts)
+    _report_rows(hyp, "hyp")
+    _report_rows(ref, "ref")
+    arr, ns, V = _report_common(flags, stop_ids)
+    rows, N = hyp.shape[0], ref.shape[0]
+    if index is None:
+        if rows > N:
+            raise ValueError(f"{rows} hypotheses for {N} references: pass index")
+    else:
+        assert index.dtype == torch.int32 and index.is_contiguous() and index.numel() == rows
+    assert df_keys.dtype == torch.int64 and df_counts.dtype == torch.int32 and df_keys.is_contiguous() and df_counts.is_contiguous()
+    assert df_keys.numel() == df_counts.numel()
+    stats = torch.empty((rows, 11), dtype=torch.int32, device=hyp.device)
+    cider = torch.empty(rows, dtype=torch.float64, device=hyp.device)
+    K = df_keys.numel()
+    L.check(L.lib().mvlt_report_stats(_p(hyp), _ld(hyp), rows, hyp.shape[1], _p(ref), _ld(ref), N, ref.shape[1], _p(index), _p(flags),
+                                      V, arr, ns, _p(df_keys) if K else None, _p(df_counts) if K else None, K, _p(stats), _p(cider),
+                                      _stream()), "mvlt_report_stats")
+    return stats, cider
+
+
 def gumbel_noise(seed, tag, rows, N, device):
     """The noise of gemm_sample as the kernel computes it, f32 [rows, N] (tests)."""
     out = torch.empty((rows, N), dtype=torch.float32, device=device)
