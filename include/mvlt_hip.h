@@ -332,6 +332,57 @@ typedef struct MvltHeadCE {
 } MvltHeadCE;
 int mvlt_mlm_head_ce(const MvltGemm* p, const MvltHeadCE* h, void* stream);
 size_t mvlt_mlm_head_ce_workspace_bytes(int M, int V);
+/* Sequence-level loss on decoded id rows (csrc/seqloss.hip): the loss of self-critical / reward-weighted fine-tuning,
+ *   L = - sum_b sum_{t < len_b} w[b, t] log p(seq[b, t] | image, seq[b, :t]) / N,   N = sum_b len_b
+ * (the reference's --scst path, run_report_generation.py:315-361, names a RewardCriterion it never defines: the definition is
+ * this project's).  len_b = 1 + the index of the first id equal to eos in row b ([END] is itself scored); without one, the index
+ * of the first id <= 0 (PAD); with neither, T.  Scalar and pointer arguments only: the struct registry and MVLT_ABI_VERSION stay.
+ *
+ * mvlt_seq_loss_plan: ids int64 [B, ld >= T], eos (negative: none), weights f32 read at weights[b * w_stride_b + t * w_stride_t]
+ * (element strides, either may be 0), row0 / row_step: the encoder row of position (b, t) is row0 + b * row_step + t.  One
+ * launch, one workgroup, no host sync, stateless (everything below is written on every call):
+ *   len int32 [B];  tf_ids int64 [B, T] = ids for t < len_b, 0 behind (the teacher-forcing input: the encoder masks the tail as
+ *   padding);  rows_dev int32 [1] = N;  and the packed plan in the layout mvlt_label_plan gives for labels = ids on the scored
+ *   positions and -100 elsewhere: slot off_b + t (off = exclusive prefix sum of len) holds position (b, t), t < len_b:
+ *   gather_row int32 [B T] = its encoder row, sel_labels int64 [B T] = ids[b, t], row_weight f32 [B T] = its weight; the
+ *   positions behind the ends follow from slot N on in (b, t) order with their encoder row, label -100 and weight 0.
+ *   A negative id ahead of an [END] has no token: its slot carries label -100 and weight 0 and its tf_ids entry is 0 (it keeps
+ *   its place in the prefix and counts in N: the one case in which the packing is not mvlt_label_plan's).
+ *   Two things the plan does not judge.  A PAD (id 0) ahead of an [END] lies inside the prefix: it is scored as label 0 with
+ *   its weight, while the encoder treats the position as it treats any PAD inside a caption.  Ids must be below the vocabulary size V of the head that
+ *   follows: mvlt_mlm_head_ce leaves x_label unwritten for a label >= V, so mvlt_seq_loss_fwd would add an undefined term for
+ *   that row (nothing here knows V, and checking it needs a read-back: the caller's contract, as for the caption ids of the
+ *   CE route).
+ * Refusals (MVLT_ERR_ARG, nothing launched, nothing written): a NULL pointer, B outside 1 .. 4096, T outside 1 .. 512, ld < T,
+ * a negative stride / row0 / row_step, a last row beyond INT32_MAX, int64 operands not 8-byte or the others not 4-byte aligned.
+ *
+ * mvlt_seq_loss_fwd: acc[0] = sum over i < n of row_weight[i] * (lse[i] - x_label[i]), acc[1] = (float)n, n = min(rows,
+ * *rows_dev) (rows_dev NULL: rows), from the lse / x_label mvlt_mlm_head_ce wrote.  A row of weight 0 adds nothing and its lse /
+ * x_label are not read.  One workgroup; summation shape (fixed, no float atomics, the same operands give the same bits): thread
+ * t adds its terms fl(w * fl(lse - x_label)) of rows t, t + 1024, ... in order, then a binary tree over the 1024 partial sums
+ * in LDS (t += t + 512, t += t + 256, ...).  *rows_dev = 0 gives (0, 0).
+ * Refusals (MVLT_ERR_ARG, nothing launched): NULL lse / x_label / row_weight / acc, rows outside 1 .. 4096 * 512, a pointer
+ * not 4-byte aligned.
+ *
+ * mvlt_ce_bwd_weighted: mvlt_ce_bwd_ragged with a coefficient per row.  For rows i < min(rows, *rows_dev) with labels[i] >= 0
+ *   dlogits[i, n] = c_i * (__expf(x[i, n] - lse[i]) - [n == labels[i]])   n < V,
+ *   c_i = fl(fl(fl(grad_scale * *grad_scale_dev) / max(*count, 1)) * row_weight[i])
+ * -- the scalar first, so row_weight == 1 gives the bits of mvlt_ce_bwd_ragged.  Columns V .. ld - 1 and rows with a negative
+ * label are zero-filled; a row with row_weight == 0 is zero-filled without reading its logits or its lse (a non-finite logit
+ * there cannot leak); rows at or beyond *rows_dev are neither read nor written.  dlogits == logits (in place) is allowed;
+ * bf16 and f32.  When ld is a multiple of 16 bytes (8 bf16 / 4 f32 elements) rows move as 16-byte vectors, two in flight per
+ * thread; any other ld takes an element-wise loop.  Grid: rows x column slices, at most 2048 workgroups, rows beyond it strided.
+ * Refusals (MVLT_ERR_ARG, nothing launched, nothing written): NULL logits / labels / lse / row_weight / count / dlogits, rows or
+ * V < 1, ld < V or ld > INT32_MAX, logits / dlogits not 16-byte aligned when ld is a multiple of 16 bytes (not element-aligned
+ * otherwise), labels not 8-byte and the f32 / int32 operands not 4-byte aligned.  MVLT_ERR_UNSUPPORTED: another dtype. */
+int mvlt_seq_loss_plan(const int64_t* ids, int64_t ld, int B, int T, int64_t eos, const float* weights, int64_t w_stride_b,
+                       int64_t w_stride_t, int row0, int row_step, int32_t* len, int64_t* tf_ids, int32_t* gather_row,
+                       int64_t* sel_labels, float* row_weight, int32_t* rows_dev, void* stream);
+int mvlt_seq_loss_fwd(const float* lse, const float* x_label, const float* row_weight, int rows, const int32_t* rows_dev,
+                      float* acc, void* stream);
+int mvlt_ce_bwd_weighted(int dtype, const void* logits, int64_t ld, int rows, int V, const int64_t* labels, const float* lse,
+                         const float* row_weight, const float* count, float grad_scale, const float* grad_scale_dev,
+                         void* dlogits, const int32_t* rows_dev, void* stream);
 
 /* ------------------------------------------------------------------ retrieval (csrc/retrieval.hip)
  * Scoring head of MVLBertForRetrieval (model.py:444-476) on the packed output of one encoder pass over P (image, caption)

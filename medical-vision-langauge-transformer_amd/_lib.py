@@ -266,6 +266,9 @@ SYMBOLS = {
     "mvlt_ce_bwd": (i32, [i32, vp, i64, i32, i32, vp, vp, vp, f32, vp, vp, vp]),
     "mvlt_ce_fwd_ragged": (i32, [i32, vp, i64, i32, i32, vp, vp, vp, vp, vp, vp]),
     "mvlt_ce_bwd_ragged": (i32, [i32, vp, i64, i32, i32, vp, vp, vp, f32, vp, vp, vp, vp]),
+    "mvlt_seq_loss_plan": (i32, [vp, i64, i32, i32, i64, vp, i64, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "mvlt_seq_loss_fwd": (i32, [vp, vp, vp, i32, vp, vp, vp]),
+    "mvlt_ce_bwd_weighted": (i32, [i32, vp, i64, i32, i32, vp, vp, vp, vp, f32, vp, vp, vp, vp]),
     "mvlt_gelu_bwd": (i32, [i32, vp, vp, vp, i64, vp]),
     "mvlt_softmax_rows": (i32, [i32, vp, i64, i32, i32, vp, vp]),
     "mvlt_adamw": (i32, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp]),

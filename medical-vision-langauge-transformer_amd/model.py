@@ -301,6 +301,41 @@ class _MlmLossFn(torch.autograd.Function):
         return None, dx, None, None, None, None, None, None
 
 
+class _SeqLossFn(torch.autograd.Function):
+    """MLM head + the sequence loss -sum_i w_i log p_i / N on the packed scored rows (mvlt_seq_loss_plan's layout): the fused
+    head's lse / x_label feed mvlt_seq_loss_fwd, the backward is mvlt_ce_bwd_weighted in place over the logits."""
+
+    @staticmethod
+    def forward(ctx, token, x, head, labels, weights, save, rd, label_sync=None):
+        ar = Arena.of(head, x.dtype)
+        ar.refresh_shadow()
+        dec = head.predictions.decoder
+        V = dec.out_features
+        with ops.pin_stream():
+            pre, t1, t2, mean, rstd = head._transform(ar, x, save, rd)
+            _, lse, x_label, logits = ops.mlm_head_ce(t2, ar.compute(dec.weight), dec.bias.data, labels, V, rows_dev=rd,
+                                                      want_logits=save)
+            acc = ops.seq_loss_fwd(lse, x_label, weights, rows_dev=rd)
+        if label_sync is not None:
+            # data parallel, as in _MlmLossFn: N becomes N_global / world, so the rank average is the global-batch loss
+            acc = torch.cat([acc[:1], label_sync(acc[1:2])])
+        loss = acc[0] / acc[1]          # nan when nothing is scored, as the CE loss
+        ctx.head = head
+        ctx.saved = (ar, V, x, pre, t1, t2, mean, rstd, logits, labels, weights, lse, acc, rd) if save else None
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        ar, V, x, pre, t1, t2, mean, rstd, logits, labels, weights, lse, acc, rd = ctx.saved
+        backward_begin(ar)
+        gs = dloss.reshape(1).to(torch.float32).contiguous()
+        with ops.pin_stream():
+            dlogits = ops.ce_bwd_weighted(logits, V, labels, lse, weights, acc, grad_scale=1.0, grad_scale_dev=gs, rows_dev=rd)
+            dx = ctx.head._backward_from_dlogits(ar, dlogits, V, x, pre, t1, t2, mean, rstd, rd)
+        ctx.saved = None
+        return None, dx, None, None, None, None, None, None
+
+
 class _GatherRowsFn(torch.autograd.Function):
     """x = hidden[gather_row] with the backward pass of the labelled-row head: only the first `count` gathered rows
     carry a gradient and their source rows are distinct, so the backward pass is one scatter into a zeroed buffer
@@ -899,6 +934,60 @@ class MVLBertForImageCaption(MVLBertPretrainedModel):
         # (the label-count all-reduce is a collective: grad-mode forwards only, as in MVLBertForPretraining.forward)
         return _MlmLossFn.apply(_token(head, hidden.device), x.contiguous(), head, sel_labels, torch.is_grad_enabled(), rd,
                                 self.__dict__.get("_mvlt_label_sync") if torch.is_grad_enabled() else None, True)
+
+    def _check_sequence_loss(self, batch, sequences, weights, learning_strategy):
+        """The refusals of sequence_loss, before anything is launched."""
+        if learning_strategy not in ('unilm', 'normal'):
+            raise NotImplementedError("learning_strategy:", learning_strategy, "is not implemented! Try 'unilm' or 'normal'.")
+        if not torch.is_tensor(sequences) or sequences.dim() != 2 or sequences.dtype != torch.int64:
+            raise ValueError("sequences must be an int64 tensor [B, T]")
+        B, T = sequences.shape
+        if B != batch:
+            raise ValueError(f"{B} sequences for {batch} images")
+        if not (0 < B <= ops.SEQ_LOSS_MAX_B and 0 < T <= ops.SEQ_LOSS_MAX_T):
+            raise ValueError(f"sequences [{B}, {T}]: 1 .. {ops.SEQ_LOSS_MAX_B} rows of 1 .. {ops.SEQ_LOSS_MAX_T} ids "
+                             "(BERT's position limit)")
+        if not torch.is_tensor(weights) or weights.dtype != torch.float32 or tuple(weights.shape) not in ((B,), (B, T)):
+            raise ValueError(f"weights must be a float32 tensor [{B}] or [{B}, {T}]")
+        if weights.requires_grad:
+            raise ValueError("weights are constants of the loss (an advantage): detach them")
+        if weights.device != sequences.device:
+            raise ValueError("weights and sequences must be on one device")
+
+    def sequence_loss(self, image, sequences, weights, learning_strategy='unilm', eos_token_id=None):
+        """Scalar f32 ``-sum_b sum_{t < len_b} w[b, t] log p(seq[b, t] | image, seq[b, :t]) / sum_b len_b`` with autograd: the
+        loss of reward-weighted (self-critical) fine-tuning on decoded rows.  ``sequences`` int64 [B, T <= 512]; ``weights``
+        float32 [B] or [B, T] without gradient; ``len_b`` = 1 + the index of the first ``eos_token_id`` ([END] is scored), else
+        the index of the first id <= 0 (PAD), else T.  ``eos_token_id=None`` reads ``config.eos_token_id``; a negative value (or
+        a config without one) leaves PAD as the only end.  The teacher-forced pass sees the sequences with everything behind
+        ``len_b`` set to PAD and follows ``self.training`` (dropout, DropPath).  A batch without a scored token gives NaN.  No
+        host synchronisation; logits never reach torch.
+        Not checked (it would need a read-back): every id must be below ``vocab_size`` -- the fused head writes no label logit
+        for a larger one and the loss is then undefined, where the cross-entropy route gives NaN.  A PAD (id 0) AHEAD of an
+        [END] is inside the prefix: it is scored as label 0 with its weight, while the encoder treats that position as it treats any
+        PAD inside a caption (rows that ``generate`` returns pad only behind their [END]); a negative id there is skipped (weight 0)."""
+        self._check_sequence_loss(image.shape[0], sequences, weights, learning_strategy)
+        Arena.of(self, compute_dtype_of(self))
+        return self.sequence_loss_from_features(self.conv(image), sequences, weights, learning_strategy, eos_token_id)
+
+    def sequence_loss_from_features(self, image_feature, sequences, weights, learning_strategy='unilm', eos_token_id=None):
+        """``sequence_loss`` on the image tower's output (``self.conv(image)``), for callers that decode from the same features."""
+        self._check_sequence_loss(image_feature.shape[0], sequences, weights, learning_strategy)
+        eos = self.config.eos_token_id if eos_token_id is None else eos_token_id
+        B, T = sequences.shape
+        n_img = image_feature.shape[1]
+        Lq = n_img + 2 + T
+        first = n_img + (2 if learning_strategy == 'unilm' else 1)           # the numbers of _head_rows' row table
+        seq = sequences if sequences.stride(1) == 1 else sequences.contiguous()
+        with ops.pin_stream():
+            _, tf_ids, gather_row, sel_labels, row_weight, rd = ops.seq_loss_plan(seq, eos, weights, first, Lq)
+        hidden, _ = self._head_rows(image_feature, tf_ids, learning_strategy)
+        assert hidden.shape[0] == B * Lq
+        x = _GatherRowsFn.apply(hidden, gather_row, rd)
+        head = self.MLM_head_seq2seq
+        grad = torch.is_grad_enabled()
+        return _SeqLossFn.apply(_token(head, hidden.device), x.contiguous(), head, sel_labels, row_weight, grad, rd,
+                                self.__dict__.get("_mvlt_label_sync") if grad else None)
 
     @torch.no_grad()
     def caption_logprobs(self, image, caption, learning_strategy='unilm'):

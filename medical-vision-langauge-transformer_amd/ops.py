@@ -1567,6 +1567,62 @@ def ce_bwd(logits, V, labels, lse, acc, grad_scale=1.0, out=None, grad_scale_dev
     return out
 
 
+SEQ_LOSS_MAX_B, SEQ_LOSS_MAX_T = 4096, 512          # one workgroup plans the batch (mvlt_seq_loss_plan)
+
+
+def seq_loss_plan(ids, eos, weights, row0, row_step):
+    """Decoded id rows -> the labelled-row plan of the sequence loss (mvlt_seq_loss_plan).  ids int64 [B, T] (unit column stride),
+    eos (None / negative: only PAD ends a row), weights f32 [B] or [B, T] (any strides), row0 / row_step: the encoder row of
+    position (b, t) is row0 + b * row_step + t.  Returns ``(len i32 [B], tf_ids i64 [B, T], gather_row i32 [B T], sel_labels i64
+    [B T], row_weight f32 [B T], rows_dev i32 [1])`` -- the last four as ``label_plan`` lays them out."""
+    _need_cuda(ids, weights)
+    assert ids.dim() == 2 and ids.dtype == torch.int64 and ids.stride(1) == 1
+    B, T = ids.shape
+    if not (0 < B <= SEQ_LOSS_MAX_B and 0 < T <= SEQ_LOSS_MAX_T):
+        raise ValueError(f"sequences [{B}, {T}]: the plan takes 1 .. {SEQ_LOSS_MAX_B} rows of 1 .. {SEQ_LOSS_MAX_T} ids")
+    assert weights.dtype == torch.float32 and tuple(weights.shape) in ((B,), (B, T))
+    wsb, wst = weights.stride(0), (weights.stride(1) if weights.dim() == 2 else 0)
+    assert wsb >= 0 and wst >= 0
+    dev = ids.device
+    N = B * T
+    i32buf = torch.empty(B + N + 1, dtype=torch.int32, device=dev)
+    i64buf = torch.empty(2 * N, dtype=torch.int64, device=dev)
+    rw = torch.empty(N, dtype=torch.float32, device=dev)
+    ln, gr, rd = i32buf[:B], i32buf[B:B + N], i32buf[B + N:]
+    tf, sel = i64buf[:N].view(B, T), i64buf[N:]
+    L.check(L.lib().mvlt_seq_loss_plan(_p(ids), ids.stride(0) if B > 1 else max(ids.stride(0), T), B, T,
+                                       -1 if eos is None else int(eos), _p(weights), wsb, wst, int(row0), int(row_step), _p(ln),
+                                       _p(tf), _p(gr), _p(sel), _p(rw), _p(rd), _stream()), "mvlt_seq_loss_plan")
+    return ln, tf, gr, sel, rw, rd
+
+
+def seq_loss_fwd(lse, x_label, row_weight, rows_dev=None):
+    """acc f32 [2] = (sum of row_weight * (lse - x_label) over the first *rows_dev rows, their number), in a fixed order."""
+    _need_cuda(lse, x_label, row_weight)
+    rows = lse.numel()
+    for t in (lse, x_label, row_weight):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == rows
+    acc = torch.empty(2, dtype=torch.float32, device=lse.device)
+    L.check(L.lib().mvlt_seq_loss_fwd(_p(lse), _p(x_label), _p(row_weight), rows, _p(rows_dev), _p(acc), _stream()),
+            "mvlt_seq_loss_fwd")
+    return acc
+
+
+def ce_bwd_weighted(logits, V, labels, lse, row_weight, acc, grad_scale=1.0, out=None, grad_scale_dev=None, rows_dev=None):
+    """ce_bwd with a weight per row (mvlt_ce_bwd_weighted): dlogits = (grad_scale * grad_scale_dev / max(acc[1], 1)) *
+    row_weight[i] * (softmax - onehot), in place over the logits unless ``out`` is given."""
+    if out is None:
+        out = logits
+    if grad_scale_dev is not None:
+        assert grad_scale_dev.dtype == torch.float32 and grad_scale_dev.numel() == 1
+    assert row_weight.dtype == torch.float32 and row_weight.is_contiguous() and row_weight.numel() == logits.shape[0]
+    assert out.stride(0) == logits.stride(0) and out.dtype == logits.dtype
+    L.check(L.lib().mvlt_ce_bwd_weighted(_dt(logits), _p(logits), logits.stride(0), logits.shape[0], V, _p(labels), _p(lse),
+                                         _p(row_weight), C.c_void_p(acc.data_ptr() + 4), float(grad_scale), _p(grad_scale_dev),
+                                         _p(out), _p(rows_dev), _stream()), "mvlt_ce_bwd_weighted")
+    return out
+
+
 def gelu_bwd(x, dy, out=None):
     dx = torch.empty_like(x) if out is None else out
     L.check(L.lib().mvlt_gelu_bwd(_dt(x), _p(x), _p(dy), _p(dx), x.numel(), _stream()), "mvlt_gelu_bwd")
