@@ -256,6 +256,41 @@ int mvlt_gemm_sample_filtered_rules(const MvltGemm* p, float* part_val, int32_t*
                                     const MvltLogitRules* rules, void* stream);
 int mvlt_gemm_sample_filtered_step_rules(const MvltGemm* p, float* part_val, int32_t* part_idx, const MvltSampleFilter* filter,
                                          const MvltSampleState* g, const MvltLogitRules* rules, void* stream);
+/* Last-row MLM head with a PER-ROW pick over any number of rows R = p->M (K sampled reports per image next to a greedy row in one
+ * decode pass).  Two device tables of R entries say what row r does:
+ *   noise_row[r] (int32)  >= 0: sampled, y = x + G with G the noise of mvlt_gemm_sample at index (uint32)noise_row[r] * N + n
+ *                         < 0 : greedy, y = x
+ *   inv_t[r] (f32)        the row's inverse temperature; the caller guarantees 0 < inv_t[r] < inf (device data: not checked)
+ * Per element, in f32 with no fused multiply-add: x = (A W^T + bias)[r, n] * inv_t[r] -- the two rounded operations of
+ * mvlt_gemm_sample; the _rules forms apply the penalty to the raw logit ahead of inv_t and drop banned columns, as there.
+ * Every row, sampled or greedy, has the same outputs:
+ *   out_idx[r] = first argmax_n y,  out_logprob[r] = x[out_idx[r]] - logsumexp_n x
+ * so the score of a GREEDY row is the log-probability of its token at inv_t[r], NOT the raw maximum logit that mvlt_gemm_argmax /
+ * mvlt_gemm_argmax_greedy record.  The noise index wraps in uint32: a bad noise_row selects other noise and never an address;
+ * nothing is read at a table index >= R.  Rows go in groups of 64 inside the call, each group streaming the weights once; the
+ * finish is one workgroup per row.  A row's result depends on its own A row, noise_row and inv_t only -- not on R, not on the
+ * other rows.  Bit for bit by construction: noise_row[r] = r and a uniform inv_t (R <= 64) give the tokens and scores of
+ * mvlt_gemm_sample; noise_row < 0 and inv_t = 1 the tokens of mvlt_gemm_argmax's wide form; the _rules form on rows r0 .. r0 + 63 with
+ * noise_row[r] = r - r0 what mvlt_gemm_sample_rules gives for that chunk (its bitmaps at row r0).
+ * part_val: scratch, 4 * R * ceil(N / 16) floats; part_idx: R * ceil(N / 16).  The _rules forms read bitmaps of R rows
+ * (mvlt_decode_rules_plan fills them 64 rows at a time).
+ * Refusals (nothing is launched, nothing written).  MVLT_ERR_ARG: p, A, B, part_val, part_idx, noise_row, inv_t or (stand-alone)
+ * out_idx / out_logprob NULL, bias NULL with MVLT_EPI_BIAS, R < 1, N / K / lda / ldb < 1, R * N >= 2^32; the _rules forms: the
+ * refusals of the other _rules heads without their M <= 64.  MVLT_ERR_UNSUPPORTED: K not a whole number of k-blocks, operands
+ * not k-contiguous or not 16-byte aligned (every 64-row group is checked), an epilogue bit other than MVLT_EPI_BIAS. */
+int mvlt_gemm_pick_rows(const MvltGemm* p, float* part_val, int32_t* part_idx, const int32_t* noise_row, const float* inv_t,
+                        int64_t* out_idx, float* out_logprob, uint64_t seed, uint32_t tag, void* stream);
+int mvlt_gemm_pick_rows_rules(const MvltGemm* p, float* part_val, int32_t* part_idx, const int32_t* noise_row, const float* inv_t,
+                              int64_t* out_idx, float* out_logprob, uint64_t seed, uint32_t tag, const MvltLogitRules* rules,
+                              void* stream);
+/* The graph form: the bookkeeping of mvlt_gemm_sample_step over the R rows of `g` (ids, scores, new_ids, unfinished of R rows;
+ * one ticket per row; col and past advance once per call), seed = *g->seed and tag = g->tag0 + *col read on the device.
+ * g->inv_temperature is not read: the table is the temperature.  Also MVLT_ERR_ARG: g, g->seed or a state pointer
+ * mvlt_gemm_sample_step requires NULL. */
+int mvlt_gemm_pick_rows_step(const MvltGemm* p, float* part_val, int32_t* part_idx, const int32_t* noise_row, const float* inv_t,
+                             const MvltSampleState* g, void* stream);
+int mvlt_gemm_pick_rows_step_rules(const MvltGemm* p, float* part_val, int32_t* part_idx, const int32_t* noise_row, const float* inv_t,
+                                   const MvltSampleState* g, const MvltLogitRules* rules, void* stream);
 /* Last-row MLM head fused with the candidate step of beam search (model.py:700-720: log_softmax + beam score, top 2 * beams over
  * (beam, token)).  The M = G * num_beams rows of the product are the hypotheses of G samples, rows g * num_beams .. + num_beams
  * the beams of sample g.  Per row m, all in f32 with no fused multiply-add:

@@ -30,6 +30,7 @@ from . import report_metrics  # noqa: F401
 from .report_metrics import ReferenceSet, ReportScorer, word_flags  # noqa: F401  (evaluate / score: report_metrics.evaluate)
 from . import scst  # noqa: F401
 from .scst import self_critical_loss  # noqa: F401  (the loss it weights: MVLBertForImageCaption.sequence_loss)
+from .decode import sample_many  # noqa: F401  (K sampled reports per image in one decode pass; generate(num_return_sequences=K))
 from . import attention  # noqa: F401
 from .attention import image_heatmap  # noqa: F401
 from . import data  # noqa: F401

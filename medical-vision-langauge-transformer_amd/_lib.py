@@ -201,6 +201,10 @@ SYMBOLS = {
     "mvlt_decode_rules_plan": (i32, [C.POINTER(MvltLogitRules), i32, i32, vp]),
     "mvlt_gemm_argmax_rules": (i32, [C.POINTER(MvltGemm), vp, vp, vp, vp, C.POINTER(MvltLogitRules), vp]),
     "mvlt_gemm_argmax_greedy_rules": (i32, [C.POINTER(MvltGemm), vp, vp, C.POINTER(MvltGreedyState), C.POINTER(MvltLogitRules), vp]),
+    "mvlt_gemm_pick_rows": (i32, [C.POINTER(MvltGemm), vp, vp, vp, vp, vp, vp, u64, u32, vp]),
+    "mvlt_gemm_pick_rows_rules": (i32, [C.POINTER(MvltGemm), vp, vp, vp, vp, vp, vp, u64, u32, C.POINTER(MvltLogitRules), vp]),
+    "mvlt_gemm_pick_rows_step": (i32, [C.POINTER(MvltGemm), vp, vp, vp, vp, C.POINTER(MvltSampleState), vp]),
+    "mvlt_gemm_pick_rows_step_rules": (i32, [C.POINTER(MvltGemm), vp, vp, vp, vp, C.POINTER(MvltSampleState), C.POINTER(MvltLogitRules), vp]),
     "mvlt_gemm_sample_rules": (i32, [C.POINTER(MvltGemm), vp, vp, vp, vp, u64, u32, f32, C.POINTER(MvltLogitRules), vp]),
     "mvlt_gemm_sample_step_rules": (i32, [C.POINTER(MvltGemm), vp, vp, C.POINTER(MvltSampleState), C.POINTER(MvltLogitRules), vp]),
     "mvlt_gemm_sample_filtered_rules": (i32, [C.POINTER(MvltGemm), vp, vp, C.POINTER(MvltSampleFilter), vp, vp, u64, u32, f32,

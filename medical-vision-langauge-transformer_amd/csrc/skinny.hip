@@ -1,7 +1,8 @@
 // Everything the decode path runs at M <= 64 (see include/mvlt_hip.h): the skinny product behind mvlt_gemm, its K-split form
 // (mvlt_gemm_skinny_accum), and the MLM head fused with the pick of the next token -- greedy (mvlt_gemm_argmax,
-// mvlt_gemm_argmax_greedy), sampled (mvlt_gemm_sample, mvlt_gemm_sample_step) and sampled behind a top-k / top-p filter
-// (mvlt_gemm_sample_filtered, mvlt_gemm_sample_filtered_step) -- and the candidate step of beam search
+// mvlt_gemm_argmax_greedy), sampled (mvlt_gemm_sample, mvlt_gemm_sample_step), sampled behind a top-k / top-p filter
+// (mvlt_gemm_sample_filtered, mvlt_gemm_sample_filtered_step) and greedy or sampled per row over any number of rows
+// (mvlt_gemm_pick_rows, mvlt_gemm_pick_rows_step) -- and the candidate step of beam search
 // (mvlt_gemm_beam_candidates: log-softmax + beam score + top-n per sample).  The six picks also come with the logit rules of
 // constrained decoding in their epilogues (mvlt_gemm_*_rules, fed by mvlt_decode_rules_plan); the beam candidates apply them to the
 // log-probabilities in their selection (mvlt_gemm_beam_candidates_rules, fed by mvlt_beam_rules_plan).  No LDS staging in the
@@ -554,6 +555,109 @@ __global__ __launch_bounds__(256) void sample_pick_kernel(const float* part_val,
         const float score = __fadd_rn(bx, -lse);
         if (STEP) pick_bookkeeping(st, m, M, col, bi, score);
         else { out_idx[m] = bi; out_logprob[m] = score; }
+    }
+}
+
+// PER-ROW pick (mvlt_gemm_pick_rows / _step: K sampled reports per image next to a greedy row, any number of rows).  A SIBLING of
+// gemm_sample128_kernel (a fourth copy of the main loop, for the reason given there; gemm_sample128_kernel itself is untouched):
+// the same loads and MFMAs in the same order, and per element (m, n) of the launch, all in f32 with no fused multiply-add,
+//     x = (acc + bias[n]) * inv_t[row0 + m];   y = noise_row[row0 + m] >= 0 ? x + gumbel_noise(seed, tag, noise_row * N + n) : x
+// so a greedy row is the sampled pick without its noise term and every row has one definition of token (first index of the
+// largest y) and score (x_token - logsumexp x).  A launch covers the <= 64 rows row0 .. row0 + p.M of a call over `rows` rows
+// (p.A and the rule bitmaps already point at row row0); the two tables and the parts are indexed by the row of the CALL:
+// part_val[j][rows][nparts] in the layout sample_pick_kernel finishes, one workgroup per row for any number of rows.  Rows of a
+// partial tile read the tables at the launch's last row, like they read A; the noise index wraps in uint32.
+struct PickRows { const int32_t* noise_row; const float* inv_t; int row0, rows; };
+template <typename T, int NRT, typename... R>
+__global__ __launch_bounds__(64 * SKINNY_WAVES) void gemm_pick_rows128_kernel(const GemmDev p, float* part_val, int* part_idx, int nparts, const SampleIn si,
+                                                                              const PickRows pr, const R... rules) {
+    constexpr bool RULES = sizeof...(R) > 0;
+    using M_ = Mma<T>;
+    using Frag = typename M_::Frag;
+    constexpr int KB = M_::KB, E = TypeInfo<T>::E, UNR = NRT <= 2 ? 12 : 8;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), r15 = lane & 15, g = lane >> 4;
+    const int n0 = (blockIdx.x * SKINNY_WAVES + wave) * 16;
+    if (n0 >= p.N) return;
+    const uint64_t seed = si.seed_dev ? si.seed_dev[0] : si.seed;
+    const uint32_t tag = si.tag0 + (si.col ? (uint32_t)si.col[0] : 0u);
+    const T* A = reinterpret_cast<const T*>(p.A);
+    const T* brow = reinterpret_cast<const T*>(p.B) + (long)min(n0 + r15, p.N - 1) * p.ldb + g * E;
+    const T* arow[NRT];
+#pragma unroll
+    for (int i = 0; i < NRT; ++i) arow[i] = A + (long)min(16 * i + r15, p.M - 1) * p.lda + g * E;
+    f32x4 acc[NRT];
+#pragma unroll
+    for (int i = 0; i < NRT; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int nkb = p.K / KB;
+    for (int kb0 = 0; kb0 < nkb; kb0 += UNR) {
+        Frag fb[UNR], fa[UNR][NRT];
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            const int k = min(kb0 + u, nkb - 1) * KB;          // past the end: reload the last block, never multiplied
+            fb[u] = skinny_wload(reinterpret_cast<const Frag*>(brow + k));
+#pragma unroll
+            for (int i = 0; i < NRT; ++i) fa[u][i] = *reinterpret_cast<const Frag*>(arow[i] + k);
+        }
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            if (kb0 + u < nkb) {
+#pragma unroll
+                for (int i = 0; i < NRT; ++i) M_::mma(acc[i], fb[u], fa[u][i]);
+            }
+        }
+    }
+    // acc[i][r] <-> n = n0 + 4 g + r, m = 16 i + r15
+    f32x4 bias4{0.f, 0.f, 0.f, 0.f};
+    if (p.epi & MVLT_EPI_BIAS) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bias4[r] = p.bias[min(n0 + 4 * g + r, p.N - 1)];
+    }
+    const int part = blockIdx.x * SKINNY_WAVES + wave;
+    const long plane = (long)pr.rows * nparts;
+#pragma unroll
+    for (int i = 0; i < NRT; ++i) {
+        const int m = 16 * i + r15;
+        const int mt = pr.row0 + min(m, p.M - 1);          // the table row, clamped like the A row: < pr.rows
+        const int nr = pr.noise_row[mt];
+        const float inv_t = pr.inv_t[mt];
+        const uint32_t idx0 = (uint32_t)nr * (uint32_t)p.N;
+        float x[4];
+        float best = -3.0e38f, bx = 0.f, xm = -3.0e38f; int bi = 0x7fffffff;
+        uint32_t bits = 0u;          // RULES: seen (bits 0-3) and banned (bits 4-7) of this lane's four columns
+        if constexpr (RULES) bits = rules_bits(rules_arg(rules...), m, p.M, n0 + 4 * g);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int n = n0 + 4 * g + r;
+            if constexpr (RULES) {          // the rules act on the raw logit, ahead of the temperature
+                float raw = __fadd_rn(acc[i][r], bias4[r]);
+                if ((bits >> r) & 1u) raw = rules_penalise(raw, rules_arg(rules...).penalty);
+                x[r] = __fmul_rn(raw, inv_t);
+            } else {
+                x[r] = __fmul_rn(__fadd_rn(acc[i][r], bias4[r]), inv_t);
+            }
+            float y = x[r];          // a greedy row: y = x
+            if (nr >= 0) y = __fadd_rn(x[r], gumbel_noise(seed, tag, idx0 + (uint32_t)n));
+            if (n < p.N && !(RULES && ((bits >> (4 + r)) & 1u))) {
+                if (y > best) { best = y; bi = n; bx = x[r]; }          // ascending n: ties keep the first index
+                xm = fmaxf(xm, x[r]);
+            }
+        }
+#pragma unroll
+        for (int o = 16; o < 64; o <<= 1) {
+            const float ov = __shfl_xor(best, o, 64), ox = __shfl_xor(bx, o, 64); const int oi = __shfl_xor(bi, o, 64);
+            if (BEATS(ov, oi, best, bi)) { best = ov; bi = oi; bx = ox; }
+            xm = fmaxf(xm, __shfl_xor(xm, o, 64));
+        }
+        float se = 0.f;          // (the notes of gemm_sample128_kernel on xm and on all-banned parts hold here)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) se += (n0 + 4 * g + r < p.N && !(RULES && ((bits >> (4 + r)) & 1u))) ? __expf(x[r] - xm) : 0.f;
+        se += __shfl_xor(se, 16, 64);
+        se += __shfl_xor(se, 32, 64);
+        if (g == 0 && m < p.M) {
+            const long o = (long)(pr.row0 + m) * nparts + part;
+            part_val[o] = best; part_val[plane + o] = bx; part_val[2 * plane + o] = xm; part_val[3 * plane + o] = se;
+            part_idx[o] = bi;
+        }
     }
 }
 
@@ -1184,8 +1288,56 @@ int sample_step_entry(const MvltGemm* p, float* part_val, int32_t* part_idx, con
     MVLT_LAUNCH_CHECK();
     return MVLT_OK;
 }
+// The per-row pick: every check ahead of the first launch (a refused call launches nothing), then one product launch per group
+// of 64 rows -- each streams the weights once, with the 1-4 row-tile instantiation of its row count -- and ONE finish over all
+// rows (sample_pick_kernel: a workgroup per row, the ticket counts p->M rows).  `g`: the step form's state, nullptr: stand-alone.
+int pick_rows_entry(const MvltGemm* p, float* part_val, int32_t* part_idx, const int32_t* noise_row, const float* inv_t, int64_t* out_idx,
+                    float* out_logprob, uint64_t seed, uint32_t tag, const MvltSampleState* g, const bool step, const RulesDev* r, void* stream) {
+    MVLT_CHECK(p && p->A && p->B && part_val && part_idx && noise_row && inv_t, MVLT_ERR_ARG);
+    MVLT_CHECK(p->M >= 1 && p->N > 0 && p->K > 0 && p->lda > 0 && p->ldb > 0 && (long)p->M * p->N < (1L << 32), MVLT_ERR_ARG);
+    if (p->epilogue & MVLT_EPI_BIAS) MVLT_CHECK(p->bias, MVLT_ERR_ARG);
+    GreedyState st{};
+    SampleIn si{nullptr, seed, nullptr, tag, 1.0f};
+    if (step) {
+        MVLT_CHECK(g && g->seed, MVLT_ERR_ARG);
+        { const int rc = greedy_state(g, st); if (rc != MVLT_OK) return rc; }
+        si = SampleIn{g->seed, 0, g->col, g->tag0, 1.0f};
+    } else {
+        MVLT_CHECK(out_idx && out_logprob, MVLT_ERR_ARG);
+    }
+    MVLT_CHECK(!p->a_kmajor && !p->b_kmajor && (p->epilogue & ~(MVLT_EPI_BIAS)) == 0, MVLT_ERR_UNSUPPORTED);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int nblk = parts_of(p);
+    const int rc = by_dtype(p->dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        for (int pass = 0; pass < 2; ++pass) {          // 0: check every group, 1: launch
+            for (int r0 = 0; r0 < p->M; r0 += 64) {
+                MvltGemm q = *p;
+                q.M = p->M - r0 < 64 ? p->M - r0 : 64;
+                q.A = reinterpret_cast<const T*>(p->A) + (long)r0 * p->lda;
+                q.m_dev = nullptr;
+                if (pass == 0) { MVLT_CHECK(skinny_ok<T>(&q), MVLT_ERR_UNSUPPORTED); continue; }
+                const GemmDev d = skinny_dev(&q);
+                const PickRows pr{noise_row, inv_t, r0, p->M};
+                const dim3 grid(ceil_div(nblk, SKINNY_WAVES)), block(64 * SKINNY_WAVES);
+                if (r) {
+                    const RulesDev rg{r->seen + (long)r0 * r->ld_words, r->banned + (long)r0 * r->ld_words, r->ld_words, r->penalty};
+                    LAUNCH_NRT(gemm_pick_rows128_kernel, T, q.M, grid, block, s, d, part_val, part_idx, nblk, si, pr, rg);
+                } else {
+                    LAUNCH_NRT(gemm_pick_rows128_kernel, T, q.M, grid, block, s, d, part_val, part_idx, nblk, si, pr);
+                }
+            }
+        }
+        return (int)MVLT_OK;
+    });
+    if (rc != MVLT_OK) return rc;
+    if (step) hipLaunchKernelGGL(sample_pick_kernel<true>, dim3(p->M), dim3(256), 0, s, part_val, part_idx, nblk, p->M, st, (int64_t*)nullptr, (float*)nullptr);
+    else hipLaunchKernelGGL(sample_pick_kernel<false>, dim3(p->M), dim3(256), 0, s, part_val, part_idx, nblk, p->M, GreedyState{}, out_idx, out_logprob);
+    MVLT_LAUNCH_CHECK();
+    return MVLT_OK;
+}
 // the rules of a _rules call, checked ahead of everything else: rc != MVLT_OK refuses the call
-#define RULES_OF(rd, rules, p)                                                                  \
+#define RULES_OF(rd, rules, p)                                                                 \
     RulesDev rd;                                                                                \
     { MVLT_CHECK(p, MVLT_ERR_ARG); const int rc_ = rules_dev(rules, (p)->M, (p)->N, rd); if (rc_ != MVLT_OK) return rc_; }
 }  // namespace
@@ -1236,6 +1388,30 @@ extern "C" int mvlt_gemm_sample_step_rules(const MvltGemm* p, float* part_val, i
                                            const MvltLogitRules* rules, void* stream) {
     RULES_OF(rd, rules, p);
     return sample_step_entry(p, part_val, part_idx, g, &rd, stream);
+}
+
+// the per-row pick and its rules: the bitmaps cover all p->M rows (RULES_OF without its 64 rows)
+#define RULES_OF_ROWS(rd, rules, p)                                                                  \
+    RulesDev rd;                                                                                     \
+    { MVLT_CHECK(p, MVLT_ERR_ARG); const int rc_ = rules_dev(rules, (p)->M, (p)->N, rd, 0x7FFFFFFF); if (rc_ != MVLT_OK) return rc_; }
+extern "C" int mvlt_gemm_pick_rows(const MvltGemm* p, float* part_val, int32_t* part_idx, const int32_t* noise_row, const float* inv_t,
+                                   int64_t* out_idx, float* out_logprob, uint64_t seed, uint32_t tag, void* stream) {
+    return pick_rows_entry(p, part_val, part_idx, noise_row, inv_t, out_idx, out_logprob, seed, tag, nullptr, false, nullptr, stream);
+}
+extern "C" int mvlt_gemm_pick_rows_rules(const MvltGemm* p, float* part_val, int32_t* part_idx, const int32_t* noise_row, const float* inv_t,
+                                         int64_t* out_idx, float* out_logprob, uint64_t seed, uint32_t tag, const MvltLogitRules* rules,
+                                         void* stream) {
+    RULES_OF_ROWS(rd, rules, p);
+    return pick_rows_entry(p, part_val, part_idx, noise_row, inv_t, out_idx, out_logprob, seed, tag, nullptr, false, &rd, stream);
+}
+extern "C" int mvlt_gemm_pick_rows_step(const MvltGemm* p, float* part_val, int32_t* part_idx, const int32_t* noise_row, const float* inv_t,
+                                        const MvltSampleState* g, void* stream) {
+    return pick_rows_entry(p, part_val, part_idx, noise_row, inv_t, nullptr, nullptr, 0, 0, g, true, nullptr, stream);
+}
+extern "C" int mvlt_gemm_pick_rows_step_rules(const MvltGemm* p, float* part_val, int32_t* part_idx, const int32_t* noise_row,
+                                              const float* inv_t, const MvltSampleState* g, const MvltLogitRules* rules, void* stream) {
+    RULES_OF_ROWS(rd, rules, p);
+    return pick_rows_entry(p, part_val, part_idx, noise_row, inv_t, nullptr, nullptr, 0, 0, g, true, &rd, stream);
 }
 
 // the two launches of the filtered pick: x = the product (bit for bit gemm_sample128_kernel's), then a workgroup per row

@@ -23,6 +23,10 @@ Logit rules (``repetition_penalty`` / ``no_repeat_ngram_size`` / ``min_length``,
 kernel rebuilds two bitmaps per row (tokens seen, tokens banned) from the device-side history before every pick and the ``_rules``
 forms of the head entry points apply them in their epilogues (``ops.LogitRules``) -- in the graph and in the eager loop alike, any B
 (rows in chunks of 64; rules never fall back to torch picks).  All rules off is the code path without them.
+Several reports per image (``sample_many``): K sampled rows and, optionally, the greedy row of every image decode in ONE pass over
+B * S rows.  Step 0 runs once per image, the cached steps read the shared prefix through ``mvlt_attn_cached_beam`` with a constant
+slot table (no cache row is copied), and ``mvlt_gemm_pick_rows(_step)`` picks for all rows at once: two device tables say per row
+whether it is greedy or sampled, which noise row it draws with, and its temperature.  Eager loop or ``_MultiSampleGraph``.
 Beam search (``beam_search``): same cached steps over B*beams rows, scorer bookkeeping on the host restated from HF
 transformers 4.16 (parity with the reference unpinned).  Default route (beams <= 8, head_dim 64): the candidates of a token come
 from ``mvlt_gemm_beam_candidates`` (head + log-softmax + beam score + top 2*beams per sample, f32 logits through a workspace) and
@@ -551,6 +555,192 @@ def greedy_search(model, image_feature, learning_strategy='unilm', sample_mode='
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
     search = _greedy_graph_loop if loop == 'graph' else _greedy_eager_loop
     return search(model, ar, feat, max_length, pad, eos, mask_id, cd, pick, seed, temperature, top_k, top_p, rules)
+
+
+# ----------------------------------------------------------------------------- K sampled reports per image in one pass
+def multi_sample_tables(B, num_samples, include_greedy, temperature, max_length):
+    """The row tables of ``sample_many`` as CPU tensors, a pure function of its arguments: rows r = b * S + s with
+    S = num_samples + include_greedy; ``noise_row`` int32 [R] (-1 on the greedy row s = 0, else b * num_samples + k: the draws do
+    not depend on include_greedy), ``inv_t`` f32 [R] (1 on greedy rows, the f32 value of 1 / temperature elsewhere) and ``slot``
+    int32 [R, max_length] with slot[r, :] = r % S (every row reads its own generated positions; the prefix comes from row b * S)."""
+    g = int(bool(include_greedy))
+    S = num_samples + g
+    s = torch.arange(B * S, dtype=torch.int64) % S
+    b = torch.arange(B * S, dtype=torch.int64) // S
+    sampled = s >= g
+    noise_row = torch.where(sampled, b * num_samples + (s - g), torch.full_like(s, -1)).to(torch.int32)
+    inv_t = torch.where(sampled, torch.tensor(1.0 / float(temperature), dtype=torch.float64), torch.tensor(1.0, dtype=torch.float64))
+    slot = s.to(torch.int32)[:, None].expand(B * S, max_length).contiguous()
+    return noise_row, inv_t.to(torch.float32), slot
+
+
+class _MultiSampleGraph(_DecodeGraph):
+    """``_GreedyGraph`` over R = B * S rows that share the image prefix of their image: body = the per-row pick
+    (``mvlt_gemm_pick_rows_step``: greedy and sampled rows in one head, any R) + the 2-token cached forward through
+    ``mvlt_attn_cached_beam`` with the constant slot table -- one stream, no parallel branches, static buffers only.  What a row
+    does (greedy or sampled, its noise row, its temperature) is DATA in two device tables the loop fills per call, so one capture
+    serves every num_samples / include_greedy / temperature with the same S."""
+
+    def __init__(self, model, key, B, S, n_img, max_length, cd, pad, eos, mask_id, rules=(1.0, 0, 0)):
+        dev = next(model.parameters()).device
+        H = model.config.hidden_size
+        R = B * S
+        self.key, self.model, self.cd, self.graph, self.S = key, model, cd, None, S
+        self.prefix = n_img + 2
+        self.kc, self.vc = _alloc_cache(model, R, n_img, max_length, cd, dev)
+        self.past = torch.full((1,), self.prefix - 1, dtype=torch.int32, device=dev)      # a valid position for the warm-up pass, which really runs
+        self.col = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.new_ids = torch.full((R, 2), mask_id, dtype=torch.int64, device=dev)
+        self.hfull = torch.zeros((R * 2, H), dtype=cd, device=dev)
+        self.hlast = self.hfull.view(R, 2, H)[:, 1]
+        self.unfinished = torch.ones(R, dtype=torch.int64, device=dev)
+        self.ids = torch.zeros((R, max_length), dtype=torch.int64, device=dev)
+        self.scores = torch.zeros((R, max_length), dtype=torch.float32, device=dev)
+        self.alive = torch.ones(max_length, dtype=torch.int64, device=dev)
+        self.seed = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.noise_row = torch.full((R,), -1, dtype=torch.int32, device=dev)
+        self.inv_t = torch.ones(R, dtype=torch.float32, device=dev)
+        self.slot = torch.zeros((R, max_length), dtype=torch.int32, device=dev)
+        st = self.state = L.MvltSampleState()
+        st.seed, st.tag0, st.inv_temperature = self.seed.data_ptr(), SAMPLE_TAG0, 1.0
+        st.unfinished, st.eos_id, st.pad_id, st.has_eos = self.unfinished.data_ptr(), (eos if eos is not None else -1), pad, int(eos is not None)
+        st.col, st.past = self.col.data_ptr(), self.past.data_ptr()
+        st.ids, st.ld_ids, st.scores, st.ld_scores = self.ids.data_ptr(), max_length, self.scores.data_ptr(), max_length
+        st.alive, st.new_ids, st.ld_new, st.ticket = self.alive.data_ptr(), self.new_ids.data_ptr(), 2, self.ticket.data_ptr()
+        self.rules = None
+        if rules != (1.0, 0, 0):
+            V = model.MLM_head_seq2seq.predictions.decoder.out_features
+            self.rules = ops.LogitRules(V, *rules, eos, self.ids, self.col)
+
+    def head(self):
+        t2, W, bias = _head(self.model, Arena.of(self.model, self.cd), self.hlast)
+        rules = None
+        if self.rules is not None:
+            self.rules.plan()
+            rules = self.rules.struct()
+        ops.gemm_pick_rows_step(t2, W, bias, self.state, self.noise_row, self.inv_t, rules=rules)
+
+    def body(self):
+        self.head()
+        _step2(self.model.MVLBert, Arena.of(self.model, self.cd), self.new_ids, self.past, self.kc, self.vc, self.cd, out_last=self.hfull,
+               beam=(self.S, self.prefix, self.slot))
+
+
+def _multi_graph_loop(model, ar, feat, S, tables, max_length, pad, eos, mask_id, cd, seed, rules):
+    B, n_img, _ = feat.shape
+    key = (B, S, n_img, max_length, cd, pad, eos, mask_id, ar.flat.data_ptr(), feat.device.index)
+    if rules != (1.0, 0, 0):
+        key = key + ("rules",) + tuple(rules)
+    gg = _MultiSampleGraph.of(model, "_mvlt_multi_sample_graph", key, B, S, n_img, max_length, cd, pad, eos, mask_id, rules)
+    gg.seed.fill_(ops.s64(int(seed) & ((1 << 64) - 1)))
+    for dst, src in zip((gg.noise_row, gg.inv_t, gg.slot), tables):
+        dst.copy_(src)
+    hlast, past = _step0(model.MVLBert, feat, gg.new_ids[::S, 1:2].contiguous(), gg.kc, gg.vc, stride=S)
+    gg.past.fill_(past - 1); gg.col.zero_(); gg.unfinished.fill_(1); gg.alive.zero_(); gg.ticket.zero_()
+    gg.hlast.copy_(hlast.repeat_interleave(S, 0))
+    done = 0
+    for t in range(max_length - 1):
+        gg.graph.replay()
+        done = t + 1
+        if _sync_due(eos, done) and 0 in gg.alive[done - SYNC_EVERY:done].tolist():
+            break
+    else:
+        gg.head()                                # last token: head only
+        done = max_length
+    n_out, _ = _cut(gg.alive[:done].tolist() if eos is not None else [], done)
+    return gg.ids[:, :n_out].clone(), gg.scores[:, :n_out].clone()
+
+
+def _multi_eager_loop(model, ar, feat, S, tables, max_length, pad, eos, mask_id, cd, seed, rules):
+    mv = model.MVLBert
+    B, n_img, _ = feat.shape
+    dev, R = feat.device, B * S
+    V = model.MLM_head_seq2seq.predictions.decoder.out_features
+    noise_row, inv_t, slot = (t.to(dev) for t in tables)
+    kc, vc = _alloc_cache(model, R, n_img, max_length, cd, dev)
+    mask_col = torch.full((R, 1), mask_id, dtype=torch.int64, device=dev)
+    lr = None
+    if rules != (1.0, 0, 0):
+        lr = ops.LogitRules(V, *rules, eos, torch.zeros((R, max_length), dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int64, device=dev))
+    hlast, past = _step0(mv, feat, mask_col[:B], kc, vc, stride=S)
+    prefix = past
+    hlast = hlast.repeat_interleave(S, 0)
+    unfinished = torch.ones(R, dtype=torch.int64, device=dev)
+    ids_cols, scores, alive, flags = [], [], [], []
+    while len(ids_cols) < max_length:
+        t2, W, bias = _head(model, ar, hlast.contiguous())
+        rs = None
+        if lr is not None:
+            lr.plan()
+            rs = lr.struct()
+        nxt, score = ops.gemm_pick_rows(t2, W, bias, noise_row, inv_t, seed, SAMPLE_TAG0 + len(ids_cols), rules=rs)
+        if eos is not None:
+            nxt = nxt * unfinished + pad * (1 - unfinished)
+            unfinished = unfinished * (nxt != eos).long()
+            alive.append(unfinished.max())
+        if lr is not None:
+            lr.ids[:, len(ids_cols)] = nxt
+            lr.col.fill_(len(ids_cols) + 1)
+        ids_cols.append(nxt[:, None])
+        scores.append(score[:, None])
+        if _sync_due(eos, len(ids_cols), last=max_length):
+            block = torch.stack(alive[-SYNC_EVERY:]).tolist()
+            flags[len(alive) - len(block):] = block
+            if 0 in block:
+                break
+        if len(ids_cols) >= max_length:
+            break
+        new_ids = torch.cat([nxt[:, None], mask_col], dim=1)
+        hlast = _step2(mv, ar, new_ids, past, kc, vc, cd, beam=(S, prefix, slot))
+        past += 1
+    n_out, _ = _cut(flags, len(ids_cols))
+    return torch.cat(ids_cols[:n_out], dim=-1), torch.cat(scores[:n_out], dim=-1)
+
+
+@torch.no_grad()
+def sample_many(model, image_feature, num_samples, include_greedy=True, seed=None, temperature=1.0, max_length=None,
+                pad_token_id=None, eos_token_id=None, repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0):
+    """``num_samples`` sampled reports per image, and the greedy report when ``include_greedy``, in ONE decode pass over
+    R = B * S rows, S = num_samples + include_greedy: ``(ids int64 [B, S, n], scores f32 [B, S, n])``.  Row s = 0 of an image
+    is the greedy row when included (decoded at temperature 1), the samples follow (decoded at ``temperature``).
+    ``scores[b, s, c]`` is the log-probability of ``ids[b, s, c]`` at the row's temperature -- for the greedy row too, where
+    ``greedy_search`` records the raw logit; the entries of a row behind its eos (where ``ids`` holds PAD) are unspecified.
+    The outputs are cut at the column where the last row finished, like ``greedy_search``; ``scores`` has as many columns as ``ids``.
+
+    Sample k of image b draws with the noise ``greedy_search(sample_mode='sample')`` gives batch row ``b * num_samples + k``
+    (tag SAMPLE_TAG0 + column), whatever ``include_greedy`` says: ``sample_many(num_samples=1, include_greedy=False, seed=s)``
+    draws the tokens of ``greedy_search(sample_mode='sample', seed=s)``.  ``seed=None``: a 63-bit seed from torch's default CPU
+    generator.  Step 0 (the pass over [CLS] image [SEP] [MASK]) runs once per image and its K / V are stored once per image; the
+    cached steps read them through ``mvlt_attn_cached_beam`` with a constant table, no cache row is ever copied, and one head
+    (``mvlt_gemm_pick_rows``) picks for all R rows.  ``MVLT_DECODE_GRAPH=0`` runs the eager loop, anything else a replayed graph
+    of its own (it never recaptures the greedy, sampled or beam graph); both give the same ids.
+    Only the 'unilm' strategy; no ``top_k`` / ``top_p`` (a filter needs the whole row in a workspace and a finish of its own);
+    the logit rules are ``greedy_search``'s (the vocabulary must exceed max_length); head_dim must be 64 (ValueError)."""
+    if int(num_samples) != num_samples or num_samples < 1:
+        raise ValueError("num_samples must be a positive integer")
+    num_samples = int(num_samples)
+    if not float(temperature) > 0.0 or float(temperature) == float("inf"):
+        raise ValueError("temperature must be positive")
+    rules = check_logit_rules(repetition_penalty, no_repeat_ngram_size, min_length)
+    cfg = model.config
+    if cfg.hidden_size // cfg.num_attention_heads != 64:
+        raise ValueError("sample_many reads the shared prefix through mvlt_attn_cached_beam, which needs head_dim 64")
+    cd, ar, max_length, pad, eos, mask_id, feat = _resolve(model, image_feature, max_length, pad_token_id, eos_token_id)
+    V = model.MLM_head_seq2seq.predictions.decoder.out_features
+    if rules != (1.0, 0, 0):
+        check_logit_rules(*rules, V=V, max_length=max_length)
+    B = feat.shape[0]
+    S = num_samples + int(bool(include_greedy))
+    if B * S * V >= 2 ** 32:
+        raise ValueError(f"{B * S} rows of {V} logits: the noise index rows * V must stay below 2^32")
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+    tables = multi_sample_tables(B, num_samples, include_greedy, temperature, max_length)
+    loop = _multi_graph_loop if _env()[0] else _multi_eager_loop
+    ids, scores = loop(model, ar, feat, S, tables, max_length, pad, eos, mask_id, cd, seed, rules)
+    n = ids.shape[1]
+    return ids.view(B, S, n), scores.view(B, S, n)
 
 
 # ----------------------------------------------------------------------------- beam search (model.py:636-816)

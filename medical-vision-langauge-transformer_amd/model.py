@@ -858,19 +858,37 @@ class MVLBertForImageCaption(MVLBertPretrainedModel):
 
     @torch.no_grad()
     def generate(self, image, num_beams=1, learning_strategy='unilm', sample_mode='greedy', max_length=None, seed=None, temperature=1.0,
-                 top_k=0, top_p=1.0, repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, device_scorer=None):
+                 top_k=0, top_p=1.0, repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, device_scorer=None,
+                 num_return_sequences=1):
         """The one call that reaches every decode option (the reference leaves ``generate`` an empty stub).  ``num_beams == 1``:
         ``decode.greedy_search`` -> (ids, token scores), greedy or sampled, with filters and logit rules on the raw logits.
         ``num_beams > 1``: ``decode.beam_search`` -> sequences [B, <= max_length], with the logit rules on the log-probabilities
         (HF 4.16) and ``device_scorer``; the sampling options must stay at their defaults (ValueError).  Returns what ``forward``
-        returns for the same ``num_beams``."""
+        returns for the same ``num_beams``.
+        ``num_return_sequences=K > 1`` (``num_beams == 1`` and ``sample_mode='sample'`` without ``top_k`` / ``top_p``; anything
+        else raises ValueError): K sampled reports per image from one decode pass, ``decode.sample_many(include_greedy=False)``
+        -> (ids [B, K, n], log-probabilities [B, K, n]).  K = 1 is the call without the argument."""
         if num_beams < 1:
             raise ValueError("generate() decodes: num_beams must be at least 1")
         from . import decode
         if num_beams > 1 and (sample_mode != 'greedy' or seed is not None or float(temperature) != 1.0 or top_k != 0 or top_p != 1.0):
             raise ValueError("sample_mode / seed / temperature / top_k / top_p belong to num_beams == 1: beam search does not sample")
+        if int(num_return_sequences) != num_return_sequences or num_return_sequences < 1:
+            raise ValueError("num_return_sequences must be a positive integer")
+        if num_return_sequences > 1:
+            if num_beams != 1 or sample_mode != 'sample':
+                raise ValueError("num_return_sequences > 1 returns sampled reports: it needs num_beams == 1 and sample_mode='sample'")
+            k_, p_ = ops.check_sample_filter(top_k, top_p)
+            if k_ != 0 or p_ < 1.0:
+                raise ValueError("num_return_sequences > 1 decodes in one pass, which has no top_k / top_p filter")
+            if learning_strategy != 'unilm':
+                raise NotImplementedError("only learning_strategy='unilm' is coherent with the KV cache (SURVEY.md 3.3)")
         Arena.of(self, compute_dtype_of(self))
         image_feature = self.conv(image)
+        if num_return_sequences > 1:
+            return decode.sample_many(self, image_feature, int(num_return_sequences), include_greedy=False, seed=seed,
+                                      temperature=temperature, max_length=max_length, repetition_penalty=repetition_penalty,
+                                      no_repeat_ngram_size=no_repeat_ngram_size, min_length=min_length)
         if num_beams > 1:
             return decode.beam_search(self, image_feature, num_beams, learning_strategy=learning_strategy, max_length=max_length,
                                       device_scorer=device_scorer, repetition_penalty=repetition_penalty,

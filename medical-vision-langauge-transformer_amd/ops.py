@@ -444,6 +444,48 @@ def gemm_sample_step(A, W, bias, state, rules=None):
     L.check(L.lib().mvlt_gemm_sample_step(C.byref(p), _p(pv), _p(pi), C.byref(state), _stream()), "mvlt_gemm_sample_step")
 
 
+def _pick_rows_tables(M, noise_row, inv_t):
+    assert noise_row.dtype == torch.int32 and noise_row.is_cuda and noise_row.is_contiguous() and noise_row.numel() == M
+    assert inv_t.dtype == torch.float32 and inv_t.is_cuda and inv_t.is_contiguous() and inv_t.numel() == M
+
+
+def gemm_pick_rows(A, W, bias, noise_row, inv_t, seed, tag, rules=None):
+    """The MLM head with a per-row pick over any number of rows (mvlt_gemm_pick_rows).  ``noise_row`` int32 [M]: >= 0 draws the
+    row by Gumbel-max with the noise gemm_sample gives row ``noise_row[r]``, < 0 picks it greedily; ``inv_t`` f32 [M]: the
+    row's inverse temperature (0 < inv_t < inf, not checked: device data).  Every row returns its token and the token's
+    log-probability at its temperature -- for a greedy row too, where gemm_argmax returns the raw logit.
+    ``rules``: a prepared ``L.MvltLogitRules`` over all M rows (``LogitRules.struct()``).
+    A: [M, K] (rows may be strided), W: [N, K] -> (int64 [M], f32 [M])."""
+    p, M, N = _head_gemm(A, W, bias)
+    _pick_rows_tables(M, noise_row, inv_t)
+    pv, pi = _sample_parts(M, N, A.device)
+    idx = torch.empty(M, dtype=torch.int64, device=A.device)
+    lp = torch.empty(M, dtype=torch.float32, device=A.device)
+    seed, tag = int(seed) & ((1 << 64) - 1), int(tag) & 0xFFFFFFFF
+    if rules is not None:
+        L.check(L.lib().mvlt_gemm_pick_rows_rules(C.byref(p), _p(pv), _p(pi), _p(noise_row), _p(inv_t), _p(idx), _p(lp), seed, tag,
+                                                  C.byref(rules), _stream()), "mvlt_gemm_pick_rows_rules")
+        return idx, lp
+    L.check(L.lib().mvlt_gemm_pick_rows(C.byref(p), _p(pv), _p(pi), _p(noise_row), _p(inv_t), _p(idx), _p(lp), seed, tag, _stream()),
+            "mvlt_gemm_pick_rows")
+    return idx, lp
+
+
+def gemm_pick_rows_step(A, W, bias, state, noise_row, inv_t, rules=None):
+    """gemm_pick_rows with the per-token bookkeeping of gemm_sample_step over the M rows of ``state``, a prepared
+    ``L.MvltSampleState`` (mvlt_gemm_pick_rows_step; decode._MultiSampleGraph).  The tables are read at their address every
+    call: a captured graph keeps them alive."""
+    p, M, N = _head_gemm(A, W, bias)
+    _pick_rows_tables(M, noise_row, inv_t)
+    pv, pi = _sample_parts(M, N, A.device)
+    if rules is not None:
+        L.check(L.lib().mvlt_gemm_pick_rows_step_rules(C.byref(p), _p(pv), _p(pi), _p(noise_row), _p(inv_t), C.byref(state), C.byref(rules),
+                                                       _stream()), "mvlt_gemm_pick_rows_step_rules")
+        return
+    L.check(L.lib().mvlt_gemm_pick_rows_step(C.byref(p), _p(pv), _p(pi), _p(noise_row), _p(inv_t), C.byref(state), _stream()),
+            "mvlt_gemm_pick_rows_step")
+
+
 def check_sample_filter(top_k, top_p):
     """(int top_k, float top_p) of a sampled pick, or ValueError: top_k >= 0 (0 = off), top_p > 0 (>= 1 = off), no NaN."""
     if isinstance(top_k, float) and top_k != top_k:
