@@ -814,6 +814,13 @@ int mvlt_label_plan(const int64_t* labels, const int64_t* text_row, int N, int32
 int mvlt_rows_scatter(int dtype, const void* in, void* out, int rows, int C, const int32_t* rowmap,
                       const int32_t* count, void* stream);
 int mvlt_embed_fwd(const MvltEmbed* p, void* stream);
+/* mvlt_embed_fwd with the position of batch row b shifted by row_shift[b] (int32 [B], device): position row
+ * pos + pos_offset (+ *pos_offset_dev) + row_shift[b], clamped into [0, pos_rows).  Meant for the cached-step layout (n_img = -1,
+ * type_override = 0) of a decode whose rows carry prompts of different lengths.  The same sums in the same order: an all-zero
+ * table is bit for bit mvlt_embed_fwd.  MVLT_ERR_ARG: what mvlt_embed_fwd refuses, a NULL row_shift, pos_rows <= 0 (the clamp
+ * needs the table's size) or pos_offset outside [0, pos_rows).  An existing struct plus a pointer: the struct registry and
+ * MVLT_ABI_VERSION stay as they are. */
+int mvlt_embed_fwd_rows(const MvltEmbed* p, const int32_t* row_shift, void* stream);
 /* backward: ONLY dword is accumulated (float atomics over the batch's token ids, the [CLS] / [SEP] rows included): zero it
  * first.  dpos / dtype_emb are OVERWRITTEN with ordered batch sums -- a second call does not add to the first -- and rows
  * outside the range in use are zeroed only when pos_rows / type_rows are given (see the struct). */
@@ -933,6 +940,20 @@ typedef struct MvltAttnCached {
                                            is replayed without host involvement keeps its position on the GPU) */
 } MvltAttnCached;
 int mvlt_attn_cached(const MvltAttnCached* p, void* stream);
+/* The same step for a batch whose rows sit at DIFFERENT positions (ragged text prompts in front of a decode): batch row b is at
+ *   past_b = past + row_shift[b]          (row_shift: int32 [B], device; <= 0 in the decode loops; past = p->past or *p->past_dev)
+ * It appends its n_new K/V rows at past_b .. past_b + n_new - 1 of its OWN cache row and attends to the keys [0, past_b) of the
+ * cache plus the new rows, causal over the new rows.  The kernel is mvlt_attn_cached's (one copy of the loop, a template
+ * parameter): the walk over the key blocks, the online softmax and the 4-wave merge for bf16 are functions of the row's own key
+ * count, so row b's output is bit for bit what mvlt_attn_cached gives for that row alone at past_b, and an all-zero table
+ * reproduces mvlt_attn_cached bit for bit.
+ * Cache slots of a row at and beyond past_b + n_new are never read: whatever a dense prefill left there is harmless.
+ * past_b is clamped on the device into [0, cache_cap - n_new]: a bad table gives wrong attention, never an access outside the
+ * row's cache (the convention of mvlt_attn_cached_beam).
+ * MVLT_ERR_ARG: NULL pointers (row_shift included), n_new > cache_cap, and with a host `past`: past < 0 or past + n_new >
+ * cache_cap.  MVLT_ERR_UNSUPPORTED: hd != 64, n_new > 4, operands not 16-byte aligned (there is no serial form).
+ * An existing struct plus a pointer: the struct registry (MVLT_STRUCT_COUNT) and MVLT_ABI_VERSION stay as they are. */
+int mvlt_attn_cached_rows(const MvltAttnCached* p, const int32_t* row_shift, void* stream);
 /* The same step for beam search, with a cache that is NEVER reordered: the rows are the hypotheses of rows / num_beams samples
  * (rows g * num_beams .. + num_beams the beams of sample g) and a table says in which cache row each generated position of each
  * hypothesis lives.  Key position k of row r, g = r / num_beams:

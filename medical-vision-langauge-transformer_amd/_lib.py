@@ -255,6 +255,7 @@ SYMBOLS = {
     "mvlt_label_plan": (i32, [vp, vp, i32, vp, vp, vp, vp]),
     "mvlt_rows_scatter": (i32, [i32, vp, vp, i32, i32, vp, vp, vp]),
     "mvlt_embed_fwd": (i32, [C.POINTER(MvltEmbed), vp]),
+    "mvlt_embed_fwd_rows": (i32, [C.POINTER(MvltEmbed), vp, vp]),
     "mvlt_embed_bwd": (i32, [C.POINTER(MvltEmbed), vp]),
     "mvlt_rows_transform": (i32, [i32, vp, vp, i32, i32, vp, vp, i32, f32, u64, u32, vp]),
     "mvlt_cast": (i32, [i32, vp, i32, vp, i64, vp]),
@@ -283,6 +284,7 @@ SYMBOLS = {
     "mvlt_grad_sumsq": (i32, [vp, i64, vp, i32, vp]),
     "mvlt_grad_norm_finish": (i32, [vp, i32, f32, f32, i32, vp, vp, vp]),
     "mvlt_attn_cached": (i32, [C.POINTER(MvltAttnCached), vp]),
+    "mvlt_attn_cached_rows": (i32, [C.POINTER(MvltAttnCached), vp, vp]),
     "mvlt_attn_cached_beam": (i32, [C.POINTER(MvltAttnCachedBeam), vp]),
     "mvlt_beam_step": (i32, [C.POINTER(MvltBeamStep), vp]),
     "mvlt_argmax": (i32, [i32, vp, i64, i32, i32, vp, vp]),

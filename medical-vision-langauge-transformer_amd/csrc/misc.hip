@@ -127,8 +127,17 @@ __global__ __launch_bounds__(256) void rows_scatter_kernel(const T* in, T* out, 
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void embed_fwd_kernel(const EmbDev p) {
+// Ragged prompts in front of a decode (mvlt_embed_fwd_rows, mvlt_attn_cached_rows): a kernel instantiated with a trailing
+// `const int32_t* row_shift` argument moves batch row b by row_shift[b]; without it the pack is empty, the kernel has the
+// parameters and the code it always had, and `rows_shifted` folds the difference away.
+MVLT_DEV int row_shift_of(int) { return 0; }
+MVLT_DEV int row_shift_of(int b, const int32_t* row_shift) { return row_shift[b]; }
+
+// With a row_shift table: the position of batch row b is shifted by row_shift[b] and clamped into the table [0, pos_rows); the
+// same three rows are added in the same order.
+template <typename T, typename... RowShift>
+__global__ __launch_bounds__(256) void embed_fwd_kernel(const EmbDev p, RowShift... row_shift) {
+    constexpr bool rows_shifted = sizeof...(RowShift) > 0;
     const int HV = p.H / 4;
     const long total = (long)p.B * p.L * HV;
     const T* img = reinterpret_cast<const T*>(p.img);
@@ -144,7 +153,9 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const EmbDev p) {
                            : load4f(img + ((long)b * p.n_img + (posi - 1)) * p.H + c);
         const int ty = p.type_override >= 0 ? p.type_override : (posi <= p.n_img + 1 ? 1 : 0);
         v += load4f(p.type + (long)ty * p.H + c);
-        v += load4f(p.pos + (long)(posi + pos_off) * p.H + c);
+        long prow = posi + pos_off;
+        if (rows_shifted) prow = max(0L, min(prow + row_shift_of(b, row_shift...), (long)p.pos_rows - 1));
+        v += load4f(p.pos + prow * p.H + c);
         store4f(out + row * p.H + c, v);
     }
 }
@@ -594,15 +605,21 @@ __global__ __launch_bounds__(64) void grad_norm_finish_kernel(const double* part
 // layer at past = 200; the two-pass LDS version 21 us.)
 // NW waves per (b, head) take the key blocks round-robin (a report of 150 tokens has <= 202 keys = 4 blocks of 64: one
 // memory round trip per wave instead of four dependent ones) and meet in LDS: wave 0 merges the (max, sum, P.V) triples.
+// With a row_shift table (mvlt_attn_cached_rows): the one position `past` becomes a position per batch row, past + row_shift[b],
+// clamped into [0, cache_cap - n_new] so that a bad table cannot reach outside the row's cache.  Everything below is a function
+// of the row's own `past` (append slots, key count, key blocks, causal mask, which waves see a key), so a row's output is what
+// the launch without a table gives for that row alone at its position, and slots at and beyond past_b + n_new are never read.
 constexpr int CACHED_MAXNEW = 4, CACHED_MAXK = 1 << 20, CACHED_U = 8;
-template <typename T, int NW>
-__global__ __launch_bounds__(64 * NW) void attn_cached_kernel(const MvltAttnCached p) {
+template <typename T, int NW, typename... RowShift>
+__global__ __launch_bounds__(64 * NW) void attn_cached_kernel(const MvltAttnCached p, RowShift... row_shift) {
+    constexpr bool rows_shifted = sizeof...(RowShift) > 0;
     constexpr int E = TypeInfo<T>::E, HD = 64, FC = HD / E, KG = 64 / FC;
     using Vec = typename TypeInfo<T>::Vec;
     __shared__ float wm[NW][CACHED_MAXNEW], wl[NW][CACHED_MAXNEW], wo[NW][CACHED_MAXNEW][HD];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, fc = lane % FC, kg = lane / FC;
     const int h = blockIdx.x % p.nH, b = blockIdx.x / p.nH;
-    const int past = p.past_dev ? *p.past_dev : p.past;
+    int past = p.past_dev ? *p.past_dev : p.past;
+    if (rows_shifted) past = (int)max(0L, min((long)past + row_shift_of(b, row_shift...), (long)p.cache_cap - p.n_new));
     const int C = p.nH * HD;
     const T* qkv = reinterpret_cast<const T*>(p.qkv_new) + (long)b * p.n_new * 3 * C + h * HD + fc * E;
     T* kc = reinterpret_cast<T*>(p.k_cache) + ((long)b * p.nH + h) * p.cache_cap * HD + fc * E;
@@ -1100,6 +1117,16 @@ extern "C" int mvlt_embed_fwd(const MvltEmbed* p, void* stream) {
     MVLT_LAUNCH_CHECK();
     return MVLT_OK;
 }
+extern "C" int mvlt_embed_fwd_rows(const MvltEmbed* p, const int32_t* row_shift, void* stream) {
+    EmbDev d{}; int rc = fill_emb(p, d); if (rc) return rc;
+    MVLT_CHECK(row_shift && p->out && (p->n_img < 0 || p->image_feature), MVLT_ERR_ARG);
+    MVLT_CHECK(p->pos_rows > 0 && p->pos_offset >= 0 && p->pos_offset < p->pos_rows, MVLT_ERR_ARG);      // the clamp needs the table's size
+    const int g = grid_for((long)d.B * d.L * (d.H / 4), 256);
+    BY_DTYPE(p->dtype, hipLaunchKernelGGL((embed_fwd_kernel<float, const int32_t*>), dim3(g), dim3(256), 0, STREAM(stream), d, row_shift),
+             hipLaunchKernelGGL((embed_fwd_kernel<bf16_t, const int32_t*>), dim3(g), dim3(256), 0, STREAM(stream), d, row_shift));
+    MVLT_LAUNCH_CHECK();
+    return MVLT_OK;
+}
 extern "C" int mvlt_embed_bwd(const MvltEmbed* p, void* stream) {
     EmbDev d{}; int rc = fill_emb(p, d); if (rc) return rc;
     MVLT_CHECK(p->dout, MVLT_ERR_ARG);
@@ -1340,6 +1367,23 @@ extern "C" int mvlt_attn_cached(const MvltAttnCached* p, void* stream) {
         BY_DTYPE(p->dtype, hipLaunchKernelGGL(attn_cached_serial_kernel<float>, grid, dim3(64), 0, STREAM(stream), *p),
                  hipLaunchKernelGGL(attn_cached_serial_kernel<bf16_t>, grid, dim3(64), 0, STREAM(stream), *p));
     }
+    MVLT_LAUNCH_CHECK();
+    return MVLT_OK;
+}
+extern "C" int mvlt_attn_cached_rows(const MvltAttnCached* p, const int32_t* row_shift, void* stream) {
+    MVLT_CHECK(p && row_shift && p->qkv_new && p->k_cache && p->v_cache && p->out, MVLT_ERR_ARG);
+    MVLT_CHECK(p->hd > 0 && p->B > 0 && p->nH > 0 && p->n_new > 0 && p->n_new <= p->cache_cap, MVLT_ERR_ARG);
+    // the rows' own positions are clamped on the device; the common one is checked where the host knows it
+    MVLT_CHECK(p->past_dev || (p->past >= 0 && p->past + p->n_new <= p->cache_cap), MVLT_ERR_ARG);
+    MVLT_CHECK(p->hd == 64 && p->n_new <= CACHED_MAXNEW && aligned16(p->qkv_new) && aligned16(p->k_cache) && aligned16(p->v_cache) &&
+               aligned16(p->out), MVLT_ERR_UNSUPPORTED);
+    MVLT_CHECK(p->dtype == MVLT_F32 || p->dtype == MVLT_BF16, MVLT_ERR_UNSUPPORTED);
+    dim3 grid(p->B * p->nH);
+    if (p->cache_cap > 64 && p->dtype == MVLT_BF16)          // the same choice of waves as mvlt_attn_cached (bit-equality needs it)
+        hipLaunchKernelGGL((attn_cached_kernel<bf16_t, 4, const int32_t*>), grid, dim3(256), 0, STREAM(stream), *p, row_shift);
+    else
+        BY_DTYPE(p->dtype, hipLaunchKernelGGL((attn_cached_kernel<float, 1, const int32_t*>), grid, dim3(64), 0, STREAM(stream), *p, row_shift),
+                 hipLaunchKernelGGL((attn_cached_kernel<bf16_t, 1, const int32_t*>), grid, dim3(64), 0, STREAM(stream), *p, row_shift));
     MVLT_LAUNCH_CHECK();
     return MVLT_OK;
 }

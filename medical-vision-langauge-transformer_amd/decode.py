@@ -37,6 +37,14 @@ gather of every layer's cache by beam index per token.  ``MVLT_BEAM_DEVICE=1`` /
 shapes of the fused route): the scorer's ``process`` runs on the device too (``mvlt_beam_step`` on a ``BeamDeviceState``), so the loop
 has no per-token read-back and is replayed as one HIP graph per token (``_BeamGraph``; ``MVLT_DECODE_GRAPH=0``: eager); ``finalize``
 stays on the host, after one read-back.
+Text prompts (``greedy_search(input_ids=, prompt_lengths=)``, the reference's ``input_ids`` argument, here with a length per row):
+``prompt_tables`` lays the rows out as ``prompt_b [MASK] filler`` [B, P_max + 1], ``_prefill`` runs ONE dense seq2seq pass over
+``[CLS] img [SEP]`` + that text (causal over the text: row b's [MASK] sees its own prompt only), takes every row's own [MASK] row and
+fills the caches; from then on the common position ``past`` starts at n_img + 2 + P_max and a table ``row_shift[b] = P_b - P_max``
+places row b at its own position in the two kernels of the cached step that know positions (``mvlt_embed_fwd_rows``,
+``mvlt_attn_cached_rows``: slots behind a row's position are never read, so the filler needs no clean-up).  The picks, their device
+state and ``past`` / ``col`` are untouched; the prompted graphs live in slots of their own, keyed by the cache capacity too.  The
+ids and scores returned are the continuation's; the logit rules see the continuation only.  No prompt: today's calls, byte for byte.
 Logit rules in beam search (``beam_search(repetition_penalty=, no_repeat_ngram_size=, min_length=)``): HF 4.16 places the processors
 on the log-probabilities, ahead of the beam score.  The fused and the device route run ``mvlt_beam_rules_plan`` over the int32 live
 sequences (the hypotheses' own tokens after the beam reorder: ``BeamDeviceState.seq`` on the device route) and the rule-aware
@@ -142,6 +150,54 @@ def _beam_route(num_beams, head_dim, max_length, fused_on, device_scorer, device
     return 'fused' if fused else 'plain'
 
 
+def check_prompt(input_ids, prompt_lengths, B, n_img, max_length, pos_rows):
+    """The prompt lengths of a prompted decode as a list of B host integers, or ValueError: ``input_ids`` int64 [B, P_max],
+    ``prompt_lengths`` None (every row has P_max tokens) or B host integers (list / tuple / CPU tensor: a device tensor would
+    have to be read back) with 0 <= P_b <= P_max, and the last position the decode can write, that of the [MASK] behind
+    max_length new tokens, inside the position table: n_img + 2 + P_max + max_length + 1 <= pos_rows."""
+    if not torch.is_tensor(input_ids) or input_ids.dim() != 2 or input_ids.dtype != torch.int64:
+        raise ValueError("input_ids must be an int64 tensor [B, P_max]")
+    if input_ids.shape[0] != B:
+        raise ValueError(f"input_ids has {input_ids.shape[0]} rows for a batch of {B} images")
+    p_max = input_ids.shape[1]
+    if prompt_lengths is None:
+        lens = [p_max] * B
+    else:
+        if torch.is_tensor(prompt_lengths):
+            if prompt_lengths.device.type != 'cpu':
+                raise ValueError("prompt_lengths are host integers (a list or a CPU tensor): the decode reads nothing back")
+            if prompt_lengths.dtype.is_floating_point or prompt_lengths.dtype == torch.bool:
+                raise ValueError("prompt_lengths must be integers")
+            prompt_lengths = prompt_lengths.reshape(-1).tolist()
+        lens = list(prompt_lengths)
+        if len(lens) != B:
+            raise ValueError(f"{len(lens)} prompt lengths for a batch of {B} images")
+        for v in lens:
+            if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= p_max:
+                raise ValueError(f"prompt lengths must be integers in [0, P_max = {p_max}], not {v!r}")
+        lens = [int(v) for v in lens]
+    need = n_img + 2 + p_max + max_length + 1
+    if need > pos_rows:
+        raise ValueError(f"{n_img} image tokens + 2 + a prompt of {p_max} + {max_length} new tokens + [MASK] need {need} positions: "
+                         f"the position table has {pos_rows}")
+    return lens
+
+
+def prompt_tables(input_ids, prompt_lengths, mask_id):
+    """The tables of a prompted decode, a pure function of its arguments (on the device of ``input_ids``, nothing read back):
+    ``text`` int64 [B, P_max + 1], row b = its P_b prompt tokens, [MASK] at column P_b and [MASK] in every column behind it (what
+    lies there is seen by nothing that is kept; the mask id keeps it a valid word row); ``row_shift`` int32 [B] = P_b - P_max, the
+    distance of row b's position from the common one; ``mask_col`` int64 [B] = P_b, the text column of row b's [MASK].
+    ``prompt_lengths``: None (every row P_max) or B host integers, as ``check_prompt`` returns them."""
+    B, p_max = input_ids.shape
+    lens = [p_max] * B if prompt_lengths is None else [int(v) for v in prompt_lengths]
+    mask_col = torch.tensor(lens, dtype=torch.int64).to(input_ids.device)
+    cols = torch.arange(p_max + 1, dtype=torch.int64, device=input_ids.device)[None, :]
+    padded = torch.cat([input_ids, input_ids.new_full((B, 1), mask_id)], dim=1)
+    text = torch.where(cols < mask_col[:, None], padded, torch.full_like(padded, mask_id)).contiguous()
+    return text, (mask_col - p_max).to(torch.int32), mask_col
+
+
 def _sync_due(eos, done, last=None):
     """Read the finished flags back after ``done`` columns?  One host sync per SYNC_EVERY tokens (and at column ``last``)."""
     return eos is not None and (done % SYNC_EVERY == 0 or done == last)
@@ -157,9 +213,10 @@ def _cut(alive, n_cols):
     return n_cols, n_cols
 
 
-def _layers_cached(mv, ar, x, kc, vc, past, n_new, out_last=None, beam=None):
+def _layers_cached(mv, ar, x, kc, vc, past, n_new, out_last=None, beam=None, row_shift=None):
     """x: [B*n_new, H] embeddings of the new tokens -> last hidden [B*n_new, H] (written into ``out_last`` when given).
-    ``beam`` = (num_beams, prefix, slot table): the attention follows beam ancestry through the table (ops.attn_cached_beam)."""
+    ``beam`` = (num_beams, prefix, slot table): the attention follows beam ancestry through the table (ops.attn_cached_beam).
+    ``row_shift`` (int32 [B], device; not with ``beam``): batch row b sits at ``past + row_shift[b]`` (ops.attn_cached(row_shift=))."""
     cfg = mv.config
     H = cfg.hidden_size
     nH = cfg.num_attention_heads
@@ -181,7 +238,7 @@ def _layers_cached(mv, ar, x, kc, vc, past, n_new, out_last=None, beam=None):
         sa, so = layer.attention.self, layer.attention.output
         qkv = ops.gemm(x, ar.compute(sa.query.weight, 3 * H), bias=ar.master_span(sa.query.bias, 3 * H))
         if beam is None:
-            ctx = ops.attn_cached(qkv, kc[i], vc[i], past, (H // nH) ** -0.5)
+            ctx = ops.attn_cached(qkv, kc[i], vc[i], past, (H // nH) ** -0.5, row_shift=row_shift)
         else:
             ctx = ops.attn_cached_beam(qkv, kc[i], vc[i], past, (H // nH) ** -0.5, beam[0], beam[1], beam[2])
         if split:
@@ -205,11 +262,11 @@ def _layers_cached(mv, ar, x, kc, vc, past, n_new, out_last=None, beam=None):
     return x
 
 
-def _embed_new(mv, ids, past, dtype):
+def _embed_new(mv, ids, past, dtype, row_shift=None):
     cfg = mv.config
     return ops.embed_fwd(ids.contiguous(), None, mv.word_embeddings.weight.data, mv.position_embeddings.weight.data,
                          mv.token_type_embeddings.weight.data, cfg.cls_token_id, cfg.sep_token_id, dtype=dtype,
-                         pos_offset=past, type_override=0)
+                         pos_offset=past, type_override=0, row_shift=row_shift)
 
 
 def _fill_cache_from_qkv(qkv, B, Lq, nH, hd, kc, vc, keep):
@@ -255,12 +312,29 @@ def _step0(mv, feat, mask_col, kc, vc, stride=1):
     return hidden[:, -1], L0 - 1
 
 
-def _step2(mv, ar, new_ids, past, kc, vc, cd, out_last=None, beam=None):
+def _prefill(mv, feat, text, mask_col, kc, vc):
+    """Step 0 of a prompted decode: ONE dense seq2seq forward over [CLS] img [SEP] text, ``text`` [B, P_max + 1] of
+    ``prompt_tables``.  The mask is causal over the text, so row b's [MASK] at text column P_b sees its own prompt and nothing
+    behind it.  Positions [0, n_img + 2 + P_max) go into the caches: those of row b at and beyond n_img + 2 + P_b hold its
+    [MASK] and the filler, which the cached steps overwrite or never read (mvlt_attn_cached_rows reads below the row's own
+    position only).  Returns (the hidden row of every sample's own [MASK] [B, H]; the common position n_img + 2 + P_max)."""
+    B, n_img, H = feat.shape
+    nH = mv.config.num_attention_heads
+    hidden, _, saved = mv._forward(feat, text, text, None, True, True)
+    Lq = n_img + 2 + text.shape[1]
+    for i in range(len(mv.encoder.layer)):
+        _fill_cache_from_qkv(saved["layers"][i][1], B, Lq, nH, H // nH, kc[i], vc[i], Lq - 1)
+    rows = torch.arange(B, dtype=torch.int64, device=feat.device)
+    return hidden[rows, mask_col + (n_img + 2)], Lq - 1
+
+
+def _step2(mv, ar, new_ids, past, kc, vc, cd, out_last=None, beam=None, row_shift=None):
     """The cached forward of the 2 tokens ``new_ids`` [rows, 2] = [last token, MASK] at positions past, past + 1
-    (model.py:82-108, :587-591) -> the [MASK] rows [rows, H], a view of the [rows * 2, H] output (``out_last`` when given)."""
+    (model.py:82-108, :587-591) -> the [MASK] rows [rows, H], a view of the [rows * 2, H] output (``out_last`` when given).
+    ``row_shift`` (prompted decode): row b's two positions are past + row_shift[b] and the one behind it."""
     rows, H = new_ids.shape[0], mv.config.hidden_size
-    x = _embed_new(mv, new_ids, past, cd).view(rows * 2, H)
-    return _layers_cached(mv, ar, x, kc, vc, past, 2, out_last=out_last, beam=beam).view(rows, 2, H)[:, -1]
+    x = _embed_new(mv, new_ids, past, cd, row_shift).view(rows * 2, H)
+    return _layers_cached(mv, ar, x, kc, vc, past, 2, out_last=out_last, beam=beam, row_shift=row_shift).view(rows, 2, H)[:, -1]
 
 
 def _head(model, ar, hlast):
@@ -352,11 +426,14 @@ class _GreedyGraph(_DecodeGraph):
     the all-finished flags back."""
 
     def __init__(self, model, key, B, n_img, max_length, cd, pad, eos, mask_id, mode='greedy', temperature=1.0, top_k=0, top_p=1.0,
-                 rules=(1.0, 0, 0)):
+                 rules=(1.0, 0, 0), p_max=None):
         dev = next(model.parameters()).device
         H = model.config.hidden_size
         self.key, self.model, self.cd, self.graph = key, model, cd, None
-        self.kc, self.vc = _alloc_cache(model, B, n_img, max_length, cd, dev)
+        # p_max (prompted decode): room for the longest prompt in front of the new tokens, and the rows' distances from the
+        # common position in a static table the loop fills per call; None: the graph without either
+        self.kc, self.vc = _alloc_cache(model, B, n_img, max_length + (p_max or 0), cd, dev)
+        self.row_shift = None if p_max is None else torch.zeros(B, dtype=torch.int32, device=dev)
         self.past = torch.zeros(1, dtype=torch.int32, device=dev)
         self.col = torch.zeros(1, dtype=torch.int64, device=dev)
         self.new_ids = torch.full((B, 2), mask_id, dtype=torch.int64, device=dev)       # [last token, MASK]
@@ -406,10 +483,12 @@ class _GreedyGraph(_DecodeGraph):
         """The pick, then the 2-token cached forward of [last token, MASK] at positions past, past+1.  `past` was advanced by the
         pick that produced the token: the previous step's [MASK] slot is overwritten (model.py:890-894)."""
         self.head()
-        _step2(self.model.MVLBert, Arena.of(self.model, self.cd), self.new_ids, self.past, self.kc, self.vc, self.cd, out_last=self.hfull)
+        _step2(self.model.MVLBert, Arena.of(self.model, self.cd), self.new_ids, self.past, self.kc, self.vc, self.cd, out_last=self.hfull,
+               row_shift=self.row_shift)
 
 
-def _greedy_graph_loop(model, ar, feat, max_length, pad, eos, mask_id, cd, mode, seed, temperature, top_k, top_p, rules=(1.0, 0, 0)):
+def _greedy_graph_loop(model, ar, feat, max_length, pad, eos, mask_id, cd, mode, seed, temperature, top_k, top_p, rules=(1.0, 0, 0),
+                       prompt=None):
     B, n_img, _ = feat.shape
     key = (B, n_img, max_length, cd, pad, eos, mask_id, ar.flat.data_ptr(), feat.device.index)
     slot = "_mvlt_greedy_graph"
@@ -419,9 +498,20 @@ def _greedy_graph_loop(model, ar, feat, max_length, pad, eos, mask_id, cd, mode,
             key = key + (top_k, top_p)
     if rules != (1.0, 0, 0):          # a graph with rules takes the slot of its mode, like a new temperature
         key = key + ("rules",) + tuple(rules)
-    gg = _GreedyGraph.of(model, slot, key, B, n_img, max_length, cd, pad, eos, mask_id, mode, temperature, top_k, top_p, rules)
+    if prompt is None:
+        gg = _GreedyGraph.of(model, slot, key, B, n_img, max_length, cd, pad, eos, mask_id, mode, temperature, top_k, top_p, rules)
+    else:          # prompted: slots of their own beside the two above (no call recaptures another's graph), keyed by the cache capacity too
+        text, row_shift, mask_col = prompt
+        p_max = text.shape[1] - 1
+        key = key + ("prompt", n_img + 2 + p_max + max_length + 1)
+        slot = "_mvlt_prompt_graph" if mode == 'greedy' else "_mvlt_prompt_sample_graph"
+        gg = _GreedyGraph.of(model, slot, key, B, n_img, max_length, cd, pad, eos, mask_id, mode, temperature, top_k, top_p, rules, p_max)
+        gg.row_shift.copy_(row_shift)
     gg.seed.fill_(ops.s64(int(seed) & ((1 << 64) - 1)))
-    hlast, past = _step0(model.MVLBert, feat, gg.new_ids[:, 1:2].contiguous(), gg.kc, gg.vc)
+    if prompt is None:
+        hlast, past = _step0(model.MVLBert, feat, gg.new_ids[:, 1:2].contiguous(), gg.kc, gg.vc)
+    else:
+        hlast, past = _prefill(model.MVLBert, feat, text, mask_col, gg.kc, gg.vc)
     gg.past.fill_(past - 1); gg.col.zero_(); gg.unfinished.fill_(1); gg.alive.zero_(); gg.ticket.zero_()      # (the first pick advances `past`; the picks raise `alive`)
     gg.hlast.copy_(hlast)
     done = 0
@@ -439,13 +529,15 @@ def _greedy_graph_loop(model, ar, feat, max_length, pad, eos, mask_id, cd, mode,
     return ids, scores
 
 
-def _greedy_eager_loop(model, ar, feat, max_length, pad, eos, mask_id, cd, pick, seed, temperature, top_k, top_p, rules=(1.0, 0, 0)):
+def _greedy_eager_loop(model, ar, feat, max_length, pad, eos, mask_id, cd, pick, seed, temperature, top_k, top_p, rules=(1.0, 0, 0),
+                       prompt=None):
     mv = model.MVLBert
     B, n_img, _ = feat.shape
     dev = feat.device
     head = model.MLM_head_seq2seq
     V = head.predictions.decoder.out_features
-    kc, vc = _alloc_cache(model, B, n_img, max_length, cd, dev)
+    row_shift = None if prompt is None else prompt[1]
+    kc, vc = _alloc_cache(model, B, n_img, max_length + (0 if prompt is None else prompt[0].shape[1] - 1), cd, dev)
     mask_col = torch.full((B, 1), mask_id, dtype=torch.int64, device=dev)
     lr = None
     if rules != (1.0, 0, 0):          # the history the plan reads: the id matrix as the graph keeps it, and the column count
@@ -483,7 +575,10 @@ def _greedy_eager_loop(model, ar, feat, max_length, pad, eos, mask_id, cd, pick,
         nxt = torch.multinomial(probs, num_samples=1, replacement=True).squeeze(1)
         return nxt, torch.log(probs.gather(1, nxt[:, None])).squeeze(1)
 
-    hlast, past = _step0(mv, feat, mask_col, kc, vc)
+    if prompt is None:
+        hlast, past = _step0(mv, feat, mask_col, kc, vc)
+    else:
+        hlast, past = _prefill(mv, feat, prompt[0], prompt[2], kc, vc)
     unfinished = torch.ones(B, dtype=torch.int64, device=dev)
     ids_cols, scores, alive, flags = [], [], [], []        # `alive`: device scalars, one per column; `flags`: what was read back
     while len(ids_cols) < max_length:
@@ -505,7 +600,7 @@ def _greedy_eager_loop(model, ar, feat, max_length, pad, eos, mask_id, cd, pick,
         if len(ids_cols) >= max_length:
             break
         new_ids = torch.cat([nxt[:, None], mask_col], dim=1)              # [last_token, MASK] (model.py:587-591)
-        hlast = _step2(mv, ar, new_ids, past, kc, vc, cd)
+        hlast = _step2(mv, ar, new_ids, past, kc, vc, cd, row_shift=row_shift)
         past += 1                                                         # drop the [MASK] slot (model.py:890-894)
     n_out, n_scores = _cut(flags, len(ids_cols))
     ids_cols, scores = ids_cols[:n_out], scores[:n_scores]
@@ -517,7 +612,7 @@ def _greedy_eager_loop(model, ar, feat, max_length, pad, eos, mask_id, cd, pick,
 @torch.no_grad()
 def greedy_search(model, image_feature, learning_strategy='unilm', sample_mode='greedy', max_length=None,
                   pad_token_id=None, eos_token_id=None, seed=None, temperature=1.0, top_k=0, top_p=1.0,
-                  repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0):
+                  repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, input_ids=None, prompt_lengths=None):
     """Returns ``(input_ids [B, n_steps], token_scores)`` like the reference
     (model.py:984: scores of all but the final step, concatenated along dim -1).
     ``sample_mode='sample'``, B <= 64: Gumbel-max draws from softmax(logits / temperature), reproducible from ``seed``
@@ -532,11 +627,26 @@ def greedy_search(model, image_feature, learning_strategy='unilm', sample_mode='
     RepetitionPenaltyLogitsProcessor, NoRepeatNGramLogitsProcessor and MinLengthLogitsProcessor on the raw logits, ahead of the
     temperature and the filters, over the history as stored (PAD of a finished row included); a banned token takes part in
     nothing and the scores follow the processed logits.  Both modes, any B, graph and eager loop the same tokens; with all
-    three off the call is the one without them.  The vocabulary must exceed max_length (ValueError)."""
+    three off the call is the one without them.  The vocabulary must exceed max_length (ValueError).
+    ``input_ids`` (int64 [B, P_max], device) / ``prompt_lengths`` (None: every row P_max tokens, the reference's dense prefix;
+    or B host integers 0 <= P_b <= P_max, nothing is read back): the decode continues row b's own P_b prompt tokens --
+    ``[CLS] img [SEP] prompt_b [MASK]`` on the first pass (model.py:583-591), row b at position n_img + 2 + P_b from then on;
+    what ``input_ids`` holds behind a row's length is never looked at.  ``max_length`` counts NEW tokens, the returned ids and
+    scores are those of the continuation only (the reference returns the dense prefix in front; a ragged batch has no such
+    matrix), and the logit rules see the continuation as stored: the prompt is no part of their history.  Both loops, every
+    pick, any B.  ValueError: the cases of ``check_prompt`` (n_img + 2 + P_max + max_length + 1 positions must exist).  The
+    first pass is the dense forward and has its reach: n_img + 2 + P_max + 1 <= 208 positions (mvlt_attn_fwd refuses more)."""
     top_k, top_p = ops.check_sample_filter(top_k, top_p)
     rules = check_logit_rules(repetition_penalty, no_repeat_ngram_size, min_length)
     if learning_strategy != 'unilm':
         raise NotImplementedError("only learning_strategy='unilm' is coherent with the KV cache (SURVEY.md 3.3)")
+    if input_ids is None and prompt_lengths is not None:
+        raise ValueError("prompt_lengths without input_ids")
+    lens = None
+    if input_ids is not None:          # refused before any device work
+        lens = check_prompt(input_ids, prompt_lengths, image_feature.shape[0], image_feature.shape[1],
+                            max_length if max_length is not None else model.config.max_length,
+                            model.MVLBert.position_embeddings.weight.shape[0])
     cd, ar, max_length, pad, eos, mask_id, feat = _resolve(model, image_feature, max_length, pad_token_id, eos_token_id)
     V = model.MLM_head_seq2seq.predictions.decoder.out_features
     top_k, top_p = (top_k if top_k < V else 0), min(top_p, 1.0)          # the values that mean "off" in one spelling each
@@ -554,7 +664,10 @@ def greedy_search(model, image_feature, learning_strategy='unilm', sample_mode='
         if seed is None:
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
     search = _greedy_graph_loop if loop == 'graph' else _greedy_eager_loop
-    return search(model, ar, feat, max_length, pad, eos, mask_id, cd, pick, seed, temperature, top_k, top_p, rules)
+    if input_ids is None:
+        return search(model, ar, feat, max_length, pad, eos, mask_id, cd, pick, seed, temperature, top_k, top_p, rules)
+    prompt = prompt_tables(input_ids.to(feat.device), lens, mask_id)
+    return search(model, ar, feat, max_length, pad, eos, mask_id, cd, pick, seed, temperature, top_k, top_p, rules, prompt)
 
 
 # ----------------------------------------------------------------------------- K sampled reports per image in one pass

@@ -859,7 +859,7 @@ class MVLBertForImageCaption(MVLBertPretrainedModel):
     @torch.no_grad()
     def generate(self, image, num_beams=1, learning_strategy='unilm', sample_mode='greedy', max_length=None, seed=None, temperature=1.0,
                  top_k=0, top_p=1.0, repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, device_scorer=None,
-                 num_return_sequences=1):
+                 num_return_sequences=1, prompt_ids=None, prompt_lengths=None):
         """The one call that reaches every decode option (the reference leaves ``generate`` an empty stub).  ``num_beams == 1``:
         ``decode.greedy_search`` -> (ids, token scores), greedy or sampled, with filters and logit rules on the raw logits.
         ``num_beams > 1``: ``decode.beam_search`` -> sequences [B, <= max_length], with the logit rules on the log-probabilities
@@ -867,10 +867,18 @@ class MVLBertForImageCaption(MVLBertPretrainedModel):
         returns for the same ``num_beams``.
         ``num_return_sequences=K > 1`` (``num_beams == 1`` and ``sample_mode='sample'`` without ``top_k`` / ``top_p``; anything
         else raises ValueError): K sampled reports per image from one decode pass, ``decode.sample_many(include_greedy=False)``
-        -> (ids [B, K, n], log-probabilities [B, K, n]).  K = 1 is the call without the argument."""
+        -> (ids [B, K, n], log-probabilities [B, K, n]).  K = 1 is the call without the argument.
+        ``prompt_ids`` (int64 [B, P_max]) / ``prompt_lengths`` (None or B host integers): the report continues row b's own
+        prompt (``decode.greedy_search(input_ids=, prompt_lengths=)``: ids and scores of the continuation, ``max_length`` new
+        tokens).  ``num_beams == 1`` and ``num_return_sequences == 1`` only; anything else raises ValueError."""
         if num_beams < 1:
             raise ValueError("generate() decodes: num_beams must be at least 1")
         from . import decode
+        if prompt_ids is None and prompt_lengths is not None:
+            raise ValueError("prompt_lengths without prompt_ids")
+        if prompt_ids is not None and (num_beams > 1 or num_return_sequences != 1):
+            raise ValueError("a text prompt continues one greedy or sampled report per image: num_beams and num_return_sequences "
+                             "must be 1 (beam search and the one-pass multi-sample decode take no prompt)")
         if num_beams > 1 and (sample_mode != 'greedy' or seed is not None or float(temperature) != 1.0 or top_k != 0 or top_p != 1.0):
             raise ValueError("sample_mode / seed / temperature / top_k / top_p belong to num_beams == 1: beam search does not sample")
         if int(num_return_sequences) != num_return_sequences or num_return_sequences < 1:
@@ -896,7 +904,7 @@ class MVLBertForImageCaption(MVLBertPretrainedModel):
         return decode.greedy_search(self, image_feature, learning_strategy=learning_strategy, sample_mode=sample_mode,
                                     max_length=max_length, seed=seed, temperature=temperature, top_k=top_k, top_p=top_p,
                                     repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
-                                    min_length=min_length)
+                                    min_length=min_length, input_ids=prompt_ids, prompt_lengths=prompt_lengths)
 
     def encode_forward(self, image_feature, caption, learning_strategy):
         text_out, _, _, sep_out = self.MVLBert(text_idx=caption, text_mask=None, image_feature=image_feature,

@@ -1465,8 +1465,10 @@ def _embed_struct(dtype, B, n_img, T, H, text_ids, word, pos, typ, cls_id, sep_i
 
 
 def embed_fwd(text_ids, image_feature, word, pos, typ, cls_id, sep_id, *, dtype=None, pos_offset=0,
-              type_override=-1, pack=None, out=None):
-    """MVLBert.get_embedding sum.  image_feature None -> cached-step (text only) layout."""
+              type_override=-1, pack=None, out=None, row_shift=None):
+    """MVLBert.get_embedding sum.  image_feature None -> cached-step (text only) layout.
+    ``row_shift`` (int32 [B], device; None: the entry point without it): the position of batch row b is shifted by row_shift[b]
+    and clamped into the position table (mvlt_embed_fwd_rows)."""
     if image_feature is not None:
         B, n_img, H = image_feature.shape
         dtype = image_feature.dtype
@@ -1481,6 +1483,11 @@ def embed_fwd(text_ids, image_feature, word, pos, typ, cls_id, sep_id, *, dtype=
     p.image_feature, p.out = _p(image_feature), _p(out)
     if pack is not None:
         p.row_start, p.seq_len = _p(pack[0]), _p(pack[1])
+    if row_shift is not None:
+        assert row_shift.dtype == torch.int32 and row_shift.is_cuda and row_shift.is_contiguous() and row_shift.numel() == B
+        p.pos_rows = pos.shape[0]
+        L.check(L.lib().mvlt_embed_fwd_rows(C.byref(p), _p(row_shift), _stream()), "mvlt_embed_fwd_rows")
+        return out
     L.check(L.lib().mvlt_embed_fwd(C.byref(p), _stream()), "mvlt_embed_fwd")
     return out
 
@@ -1749,8 +1756,10 @@ def grad_norm_finish(partial, grad_scale=1.0, max_norm=0.0, skip_nonfinite=False
     return out, flags
 
 
-def attn_cached(qkv_new, k_cache, v_cache, past, scale, out=None):
-    """past: int, or an int32 device tensor [1] (position kept on the GPU by a replayed decode loop)."""
+def attn_cached(qkv_new, k_cache, v_cache, past, scale, out=None, row_shift=None):
+    """past: int, or an int32 device tensor [1] (position kept on the GPU by a replayed decode loop).
+    ``row_shift`` (int32 [B], device; None: the entry point without it): batch row b sits at ``past + row_shift[b]``, clamped
+    into its cache (mvlt_attn_cached_rows: hd = 64, n_new <= 4)."""
     B, nH, cap, hd = k_cache.shape
     n_new = qkv_new.shape[0] // B
     if out is None:
@@ -1763,6 +1772,10 @@ def attn_cached(qkv_new, k_cache, v_cache, past, scale, out=None):
     else:
         p.past = past
     p.qkv_new, p.k_cache, p.v_cache, p.out, p.scale = _p(qkv_new), _p(k_cache), _p(v_cache), _p(out), float(scale)
+    if row_shift is not None:
+        assert row_shift.dtype == torch.int32 and row_shift.is_cuda and row_shift.is_contiguous() and row_shift.numel() == B
+        L.check(L.lib().mvlt_attn_cached_rows(C.byref(p), _p(row_shift), _stream()), "mvlt_attn_cached_rows")
+        return out
     L.check(L.lib().mvlt_attn_cached(C.byref(p), _stream()), "mvlt_attn_cached")
     return out
 
