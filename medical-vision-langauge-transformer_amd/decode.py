@@ -9,7 +9,12 @@ over ``[CLS] img [SEP] [MASK]``; every later step (``_step2``) feeds the 2 token
 K/V in place and attends causally (``mvlt_attn_cached``).  "Trimming the [MASK]
 slot" (model.py:890-894) is just ``past += 1``: the next step overwrites it.
 Every search is argument resolution (``_resolve``), a route (``_greedy_route`` / ``_beam_route``: pure functions of the call's
-arguments and of the switches ``_env`` reads per call) and one loop per route; the two replayed graphs share ``_DecodeGraph``.
+arguments and of the switches ``_env`` reads per call) and one loop per route; the replayed graphs share ``_DecodeGraph``.
+A non-beam search (``greedy_search``, ``sample_many``) is its argument checks and three choices: a row layout (``_Plain`` /
+``_Prompted`` / ``_SharedPrefix``: which first pass fills the caches, how the rows find their K / V in ``_step2``), a pick
+(``_PICKS``: eager form and captured form per name, row chunks of 64 in ``_pick`` alone) and the logit rules.  The token loop
+exists once per kind -- ``_graph_loop`` (a ``_TokenGraph`` over a ``_TokenState``, replayed by ``_replay``, which the beam graph
+shares) and ``_eager_loop`` -- so what is wired into a layout or a pick reaches both; ``_graph_slot_key`` names a graph's slot and key.
 Greedy mode replays one captured HIP graph per token (``_GreedyGraph``: position,
 output column and finished flags live on the device; ``MVLT_DECODE_GRAPH=0`` selects
 the eager loop).  'sample' mode (B <= 64) is the same graph with the Gumbel-max pick of ``mvlt_gemm_sample_step`` as
@@ -54,6 +59,7 @@ its ``log_softmax`` rows and uses neither kernel.  All rules off is the code pat
 from __future__ import annotations
 
 import os
+from types import SimpleNamespace
 
 import torch
 
@@ -101,6 +107,39 @@ def _greedy_route(sample_mode, B, filtered, graph_on):
     if sample_mode == 'greedy':
         return 'eager', 'gemm_argmax' if B <= 64 else 'argmax'
     return 'eager', 'gemm_sample' if B <= 64 else 'multinomial'
+
+
+def _graph_slot_key(B, n_img, max_length, cd, pad, eos, mask_id, arena, device, mode='greedy', temperature=1.0, top_k=0, top_p=1.0,
+                    rules=(1.0, 0, 0), p_max=None, S=None):
+    """(slot, key) of the replayed graph of a non-beam search, a pure function of its arguments: the name under which the graph
+    lives in ``model.__dict__`` and what a call must share with it to replay it.  A sampled graph lives beside the greedy one,
+    the prompted graphs (``p_max``, keyed by the cache capacity too) beside both and the multi-sample graph (``S`` rows per image;
+    temperature and the split of S are data) beside all four, so no call recaptures another's graph; a filter or a rule set takes
+    the slot of its mode, like a new temperature.  ``arena`` / ``device``: the address of the weights, the device index."""
+    if S is not None:
+        slot, key = "_mvlt_multi_sample_graph", (B, S, n_img, max_length, cd, pad, eos, mask_id, arena, device)
+    else:
+        slot, key = "_mvlt_greedy_graph", (B, n_img, max_length, cd, pad, eos, mask_id, arena, device)
+        if mode != 'greedy':
+            slot, key = "_mvlt_sample_graph", key + (mode, float(temperature))
+            if (top_k, top_p) != (0, 1.0):
+                key = key + (top_k, top_p)
+    if rules != (1.0, 0, 0):
+        key = key + ("rules",) + tuple(rules)
+    if p_max is not None:
+        slot = "_mvlt_prompt_graph" if mode == 'greedy' else "_mvlt_prompt_sample_graph"
+        key = key + ("prompt", n_img + 2 + p_max + max_length + 1)
+    return slot, key
+
+
+def _default_seed():
+    """A 63-bit seed from torch's default CPU generator: torch.manual_seed makes an unseeded sampled decode reproducible."""
+    return int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+
+
+def _check_temperature(temperature, finite=False):
+    if not float(temperature) > 0.0 or (finite and float(temperature) == float("inf")):
+        raise ValueError("temperature must be positive")
 
 
 def check_logit_rules(repetition_penalty=1.0, no_repeat_ngram_size=0, min_length=0, num_beams=1, V=None, max_length=None):
@@ -417,47 +456,163 @@ class _DecodeGraph:
         self.graph = g
 
 
-class _GreedyGraph(_DecodeGraph):
-    """The whole per-token work of greedy decoding -- last-row MLM head + argmax + [END]/PAD bookkeeping + the
-    2-token cached forward -- captured ONCE as a HIP graph and replayed per token.  Everything a replay needs
-    lives in static device buffers: the cache position (``past``: read by the embedding and attention kernels
-    through ``pos_offset_dev`` / ``past_dev``), the output column index, the ids fed to the next step, the
-    unfinished flags, and the [B, max_length] output matrices.  The host only replays and, every 8 tokens, reads
-    the all-finished flags back."""
+def _replay(graph, alive, tail, max_length, eos):
+    """Token loop of a captured graph: a replay per token (token t, then the forward that prepares token t + 1), ``tail()`` for
+    the last token, which needs no forward; ``alive`` (the per-column flags on the device) is read back every SYNC_EVERY
+    columns.  Returns the number of columns produced."""
+    for t in range(max_length - 1):
+        graph.replay()
+        if _sync_due(eos, t + 1) and 0 in alive[t + 1 - SYNC_EVERY:t + 1].tolist():
+            return t + 1
+    tail()
+    return max_length
 
-    def __init__(self, model, key, B, n_img, max_length, cd, pad, eos, mask_id, mode='greedy', temperature=1.0, top_k=0, top_p=1.0,
-                 rules=(1.0, 0, 0), p_max=None):
-        dev = next(model.parameters()).device
-        H = model.config.hidden_size
-        self.key, self.model, self.cd, self.graph = key, model, cd, None
-        # p_max (prompted decode): room for the longest prompt in front of the new tokens, and the rows' distances from the
-        # common position in a static table the loop fills per call; None: the graph without either
-        self.kc, self.vc = _alloc_cache(model, B, n_img, max_length + (p_max or 0), cd, dev)
-        self.row_shift = None if p_max is None else torch.zeros(B, dtype=torch.int32, device=dev)
-        self.past = torch.zeros(1, dtype=torch.int32, device=dev)
+
+# ----------------------------------------------------------------------------- the non-beam searches: a row layout, a pick, one loop
+class _TokenState:
+    """The device side of a token loop over ``rows`` rows, in static buffers, with the prepared ``L.MvltGreedyState`` /
+    ``L.MvltSampleState`` (``state``) that the ``_step`` heads take: the cache position (``past``: read by the embedding and
+    attention kernels through ``pos_offset_dev`` / ``past_dev``), the output column, the ids fed to the next step, the unfinished
+    flags, the [rows, max_length] outputs, the per-column "a row is unfinished" flags, the seed cell and the ticket of the
+    finishing launch, which advances all of them.  ``past`` / ``inv_temperature``: what the state holds from construction --
+    the warm-up pass of a capture really runs on it, so the position must lie inside the cache."""
+
+    def __init__(self, rows, max_length, pad, eos, mask_id, dev, sampled, past=0, inv_temperature=1.0):
+        self.past = torch.full((1,), past, dtype=torch.int32, device=dev)
         self.col = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.new_ids = torch.full((B, 2), mask_id, dtype=torch.int64, device=dev)       # [last token, MASK]
-        # last hidden states of the two new tokens of every sample; the MLM head reads the [MASK] rows in place (row stride 2 H)
-        self.hfull = torch.zeros((B * 2, H), dtype=cd, device=dev)
-        self.hlast = self.hfull.view(B, 2, H)[:, 1]
-        self.unfinished = torch.ones(B, dtype=torch.int64, device=dev)
-        self.ids = torch.zeros((B, max_length), dtype=torch.int64, device=dev)
-        self.scores = torch.zeros((B, max_length), dtype=torch.float32, device=dev)
+        self.new_ids = torch.full((rows, 2), mask_id, dtype=torch.int64, device=dev)       # [last token, MASK]
+        self.unfinished = torch.ones(rows, dtype=torch.int64, device=dev)
+        self.ids = torch.zeros((rows, max_length), dtype=torch.int64, device=dev)
+        self.scores = torch.zeros((rows, max_length), dtype=torch.float32, device=dev)
         self.alive = torch.ones(max_length, dtype=torch.int64, device=dev)
-        # device-side state of the greedy loop, handed to mvlt_gemm_argmax_greedy: the pick, PAD for finished samples, the
-        # EOS flags, the ids / scores columns, the next input id, `past` and `col` are all advanced by its finishing launch
-        # (mode 'sample': mvlt_gemm_sample_step, the same state plus the seed cell the loop fills before the first replay)
-        self.mode, self.top_k, self.top_p = mode, top_k, top_p          # (top_k, top_p) = (0, 1.0): no filter
         self.seed = torch.zeros(1, dtype=torch.int64, device=dev)
-        st = self.state = L.MvltGreedyState() if mode == 'greedy' else L.MvltSampleState()
-        if mode != 'greedy':
-            st.seed, st.tag0, st.inv_temperature = self.seed.data_ptr(), SAMPLE_TAG0, 1.0 / float(temperature)
+        self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
+        st = self.state = L.MvltSampleState() if sampled else L.MvltGreedyState()
+        if sampled:
+            st.seed, st.tag0, st.inv_temperature = self.seed.data_ptr(), SAMPLE_TAG0, inv_temperature
         st.unfinished, st.eos_id, st.pad_id, st.has_eos = self.unfinished.data_ptr(), (eos if eos is not None else -1), pad, int(eos is not None)
         st.col, st.past = self.col.data_ptr(), self.past.data_ptr()
         st.ids, st.ld_ids, st.scores, st.ld_scores = self.ids.data_ptr(), max_length, self.scores.data_ptr(), max_length
-        st.alive, st.new_ids, st.ld_new = self.alive.data_ptr(), self.new_ids.data_ptr(), 2
-        self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
-        st.ticket = self.ticket.data_ptr()
+        st.alive, st.new_ids, st.ld_new, st.ticket = self.alive.data_ptr(), self.new_ids.data_ptr(), 2, self.ticket.data_ptr()
+
+    def reset(self, past):
+        """Start of a decode whose first pass ended at position ``past`` (the first pick advances `past`; the picks raise `alive`)."""
+        self.past.fill_(past - 1); self.col.zero_(); self.unfinished.fill_(1); self.alive.zero_(); self.ticket.zero_()
+
+    def set_seed(self, seed):
+        self.seed.fill_(ops.s64(int(seed) & ((1 << 64) - 1)))
+
+
+class _Plain:
+    """Row layout: how the rows of a search find their K / V -- which first pass fills the caches (``first_pass`` -> the [MASK]
+    rows [R, H] and the common position) and the keywords ``_step2`` attends with (``attn(table)``; ``table``: the layout's
+    int32 device table, the call's own or the static copy of a graph).  Plain: a row per image, every row at the common position.
+    ``S`` rows per image, ``p_max`` cache slots in front of the new tokens, ``warm_past``: a valid position before any first pass."""
+    S, p_max, table, warm_past = 1, 0, None, 0
+
+    def first_pass(self, mv, feat, kc, vc, mask_ids):
+        return _step0(mv, feat, mask_ids.contiguous(), kc, vc)
+
+    def attn(self, table):
+        return {}
+
+
+class _Prompted(_Plain):
+    """Row b behind its own P_b prompt tokens (the tables of ``prompt_tables``): one dense prefill, then ``row_shift[b]`` places
+    the row at its own position."""
+
+    def __init__(self, text, row_shift, mask_col):
+        self.text, self.table, self.mask_col, self.p_max = text, row_shift, mask_col, text.shape[1] - 1
+
+    def first_pass(self, mv, feat, kc, vc, mask_ids):
+        return _prefill(mv, feat, self.text, self.mask_col, kc, vc)
+
+    def attn(self, table):
+        return {'row_shift': table}
+
+
+class _SharedPrefix(_Plain):
+    """S rows per image that share its prefix: step 0 once per image into every S-th cache row, the cached steps read it through
+    ``mvlt_attn_cached_beam`` with the constant table ``slot`` int32 [R, max_length] (no cache row is copied)."""
+
+    def __init__(self, S, prefix, slot):
+        self.S, self.prefix, self.table, self.warm_past = S, prefix, slot, prefix - 1
+
+    def first_pass(self, mv, feat, kc, vc, mask_ids):
+        hlast, past = _step0(mv, feat, mask_ids[:feat.shape[0]].contiguous(), kc, vc, stride=self.S)
+        return hlast.repeat_interleave(self.S, 0), past
+
+    def attn(self, table):
+        return {'beam': (self.S, self.prefix, table)}
+
+
+def _pick_argmax(t2, W, bias, p, tag, row0, rules):
+    logits = p.logits(t2)
+    nxt = ops.argmax(logits, p.V)
+    return nxt, logits[:, :p.V].float().gather(1, nxt[:, None]).squeeze(1)
+
+
+def _pick_multinomial(t2, W, bias, p, tag, row0, rules):
+    probs = ops.softmax_rows(p.logits(t2), p.V)
+    nxt = torch.multinomial(probs, num_samples=1, replacement=True).squeeze(1)
+    return nxt, torch.log(probs.gather(1, nxt[:, None])).squeeze(1)
+
+
+# pick -> (eager form (t2, W, bias, p, tag, row0, rules) -> (tokens, scores); captured form (t2, W, bias, state, p, rules), which
+# keeps the books on the device; rows per call).  ``p``: the call's parameters (seed, temperature, top_k, top_p, the row tables
+# noise_row / inv_t of 'rows'; logits / V for the torch picks, which have no captured form and no rules).
+_PICKS = {
+    'gemm_argmax': (lambda a, W, b, p, tag, r0, rs: ops.gemm_argmax(a, W, b, rules=rs),
+                    lambda a, W, b, st, p, rs: ops.gemm_argmax_greedy(a, W, b, st, rules=rs), 64),
+    # the pick of the graph loop, stand-alone: same seed, tag and column -> same tokens
+    'gemm_sample': (lambda a, W, b, p, tag, r0, rs: ops.gemm_sample(a, W, b, p.seed, tag, p.temperature, rules=rs),
+                    lambda a, W, b, st, p, rs: ops.gemm_sample_step(a, W, b, st, rules=rs), 64),
+    # rows beyond 64 in chunks, the noise indexed by the batch row
+    'filtered': (lambda a, W, b, p, tag, r0, rs: ops.gemm_sample_filtered(a, W, b, p.seed, tag, p.temperature, p.top_k, p.top_p, row0=r0, rules=rs),
+                 lambda a, W, b, st, p, rs: ops.gemm_sample_filtered_step(a, W, b, st, p.top_k, p.top_p, rules=rs), 64),
+    'rows': (lambda a, W, b, p, tag, r0, rs: ops.gemm_pick_rows(a, W, b, p.noise_row, p.inv_t, p.seed, tag, rules=rs),
+             lambda a, W, b, st, p, rs: ops.gemm_pick_rows_step(a, W, b, st, p.noise_row, p.inv_t, rules=rs), None),
+    'argmax': (_pick_argmax, None, None),
+    'multinomial': (_pick_multinomial, None, None),
+}
+
+
+def _pick(pick, t2, W, bias, p, tag, lr):
+    """The eager form of ``pick`` over all rows of ``t2``, in row chunks where its entry point takes 64 rows; ``lr``: the
+    ``ops.LogitRules`` of the call (the bitmaps of this token first) or None."""
+    eager, _, chunk = _PICKS[pick]
+    if lr is not None:
+        lr.plan()
+    if chunk is None or t2.shape[0] <= chunk:
+        return eager(t2, W, bias, p, tag, 0, lr.struct() if lr is not None else None)
+    parts = [eager(t2[r0:r0 + 64], W, bias, p, tag, r0, lr.struct(r0) if lr is not None else None) for r0 in range(0, t2.shape[0], 64)]
+    return torch.cat([a for a, _ in parts]), torch.cat([b for _, b in parts])
+
+
+class _TokenGraph(_DecodeGraph, _TokenState):
+    """The whole per-token work of a non-beam search -- last-row MLM head + pick + [END]/PAD bookkeeping (the captured form of
+    ``pick``) + the 2-token cached forward under ``layout`` -- captured ONCE as a HIP graph and replayed per token: one stream, no
+    parallel branches.  Everything a replay needs lives in static device buffers: the ``_TokenState``, the caches, the hidden
+    rows, and what a call brings as DATA (the layout's table, the row tables of the 'rows' pick), which the loop fills per call.
+    The host only replays and, every 8 tokens, reads the all-finished flags back."""
+
+    def __init__(self, model, key, rows, layout, pick, p, n_img, max_length, cd, pad, eos, mask_id, rules=(1.0, 0, 0)):
+        dev = next(model.parameters()).device
+        H = model.config.hidden_size
+        self.key, self.model, self.cd, self.graph, self.pick = key, model, cd, None, pick
+        # layout.p_max (prompted decode): room for the longest prompt in front of the new tokens
+        self.kc, self.vc = _alloc_cache(model, rows, n_img, max_length + layout.p_max, cd, dev)
+        # zero tables, no noise rows, temperature 1, a position inside the cache: valid for the warm-up pass, which really runs
+        self.table = None if layout.table is None else torch.zeros(tuple(layout.table.shape), dtype=torch.int32, device=dev)
+        self.attn = layout.attn(self.table)
+        _TokenState.__init__(self, rows, max_length, pad, eos, mask_id, dev, pick != 'gemm_argmax', layout.warm_past, 1.0 / float(p.temperature))
+        # last hidden states of the two new tokens of every row; the MLM head reads the [MASK] rows in place (row stride 2 H)
+        self.hfull = torch.zeros((rows * 2, H), dtype=cd, device=dev)
+        self.hlast = self.hfull.view(rows, 2, H)[:, 1]
+        self.p = SimpleNamespace(top_k=p.top_k, top_p=p.top_p)          # (top_k, top_p) = (0, 1.0): no filter
+        if pick == 'rows':
+            self.p.noise_row = torch.full((rows,), -1, dtype=torch.int32, device=dev)
+            self.p.inv_t = torch.ones(rows, dtype=torch.float32, device=dev)
         # logit rules: the graph owns the bitmaps; the plan reads the history where the picks write it (ids, col)
         self.rules = None
         if rules != (1.0, 0, 0):
@@ -465,124 +620,78 @@ class _GreedyGraph(_DecodeGraph):
             self.rules = ops.LogitRules(V, *rules, eos, self.ids, self.col)
 
     def head(self):
-        """token <- argmax(MLM head(hlast)); record it in column `col`; past += 1; col += 1 (all on the device)."""
-        # decoder GEMM fused with the greedy pick and its bookkeeping: the [B, 30522] logits are never written
+        """token <- pick(MLM head(hlast)); record it in column `col`; past += 1; col += 1 (all on the device)."""
+        # decoder GEMM fused with the pick and its bookkeeping: the [rows, 30522] logits are never written
         t2, W, bias = _head(self.model, Arena.of(self.model, self.cd), self.hlast)
         rules = None
         if self.rules is not None:          # the bitmaps of this token, then the rule-aware form of the same head
             self.rules.plan()
             rules = self.rules.struct()
-        if self.mode != 'greedy' and (self.top_k, self.top_p) != (0, 1.0):
-            ops.gemm_sample_filtered_step(t2, W, bias, self.state, self.top_k, self.top_p, rules=rules)
-        elif self.mode != 'greedy':
-            ops.gemm_sample_step(t2, W, bias, self.state, rules=rules)
-        else:
-            ops.gemm_argmax_greedy(t2, W, bias, self.state, rules=rules)
+        _PICKS[self.pick][1](t2, W, bias, self.state, self.p, rules)
 
     def body(self):
         """The pick, then the 2-token cached forward of [last token, MASK] at positions past, past+1.  `past` was advanced by the
         pick that produced the token: the previous step's [MASK] slot is overwritten (model.py:890-894)."""
         self.head()
         _step2(self.model.MVLBert, Arena.of(self.model, self.cd), self.new_ids, self.past, self.kc, self.vc, self.cd, out_last=self.hfull,
-               row_shift=self.row_shift)
+               **self.attn)
 
 
-def _greedy_graph_loop(model, ar, feat, max_length, pad, eos, mask_id, cd, mode, seed, temperature, top_k, top_p, rules=(1.0, 0, 0),
-                       prompt=None):
-    B, n_img, _ = feat.shape
-    key = (B, n_img, max_length, cd, pad, eos, mask_id, ar.flat.data_ptr(), feat.device.index)
-    slot = "_mvlt_greedy_graph"
-    if mode != 'greedy':          # a graph of its own beside the greedy one: neither recaptures the other
-        key, slot = key + (mode, float(temperature)), "_mvlt_sample_graph"
-        if (top_k, top_p) != (0, 1.0):          # a filtered graph takes the sampled graph's slot, like a new temperature
-            key = key + (top_k, top_p)
-    if rules != (1.0, 0, 0):          # a graph with rules takes the slot of its mode, like a new temperature
-        key = key + ("rules",) + tuple(rules)
-    if prompt is None:
-        gg = _GreedyGraph.of(model, slot, key, B, n_img, max_length, cd, pad, eos, mask_id, mode, temperature, top_k, top_p, rules)
-    else:          # prompted: slots of their own beside the two above (no call recaptures another's graph), keyed by the cache capacity too
-        text, row_shift, mask_col = prompt
-        p_max = text.shape[1] - 1
-        key = key + ("prompt", n_img + 2 + p_max + max_length + 1)
-        slot = "_mvlt_prompt_graph" if mode == 'greedy' else "_mvlt_prompt_sample_graph"
-        gg = _GreedyGraph.of(model, slot, key, B, n_img, max_length, cd, pad, eos, mask_id, mode, temperature, top_k, top_p, rules, p_max)
-        gg.row_shift.copy_(row_shift)
-    gg.seed.fill_(ops.s64(int(seed) & ((1 << 64) - 1)))
-    if prompt is None:
-        hlast, past = _step0(model.MVLBert, feat, gg.new_ids[:, 1:2].contiguous(), gg.kc, gg.vc)
-    else:
-        hlast, past = _prefill(model.MVLBert, feat, text, mask_col, gg.kc, gg.vc)
-    gg.past.fill_(past - 1); gg.col.zero_(); gg.unfinished.fill_(1); gg.alive.zero_(); gg.ticket.zero_()      # (the first pick advances `past`; the picks raise `alive`)
+class _GreedyGraph(_TokenGraph):
+    """The graph of ``greedy_search``: ``mode`` 'greedy' (``mvlt_gemm_argmax_greedy``) or 'sample' (``mvlt_gemm_sample_step``, with
+    a filter ``mvlt_gemm_sample_filtered_step``: the same state plus the seed cell), plain or prompted (``row_shift``: the static
+    table of the rows' distances from the common position, None without a prompt)."""
+    mode = property(lambda self: 'greedy' if self.pick == 'gemm_argmax' else 'sample')
+    row_shift = property(lambda self: self.table)
+
+
+class _MultiSampleGraph(_TokenGraph):
+    """The graph of ``sample_many`` over R = B * S rows that share the image prefix of their image: the per-row pick
+    (``mvlt_gemm_pick_rows_step``: greedy and sampled rows in one head, any R) and the cached forward through
+    ``mvlt_attn_cached_beam`` with the constant slot table.  What a row does (greedy or sampled, its noise row, its temperature)
+    is DATA in two device tables, so one capture serves every num_samples / include_greedy / temperature with the same S."""
+
+
+def _graph_loop(graph, model, feat, layout, pick, p, rules, max_length, pad, eos, mask_id, cd, flat):
+    """``graph`` = (class, slot, key): the model's graph of that slot (captured when the key is new), the call's data into its
+    static buffers, the first pass, then a replay per token.  Returns what ``_eager_loop`` returns."""
+    cls, slot, key = graph
+    gg = cls.of(model, slot, key, feat.shape[0] * layout.S, layout, pick, p, feat.shape[1], max_length, cd, pad, eos, mask_id, rules)
+    if gg.table is not None:
+        gg.table.copy_(layout.table)
+    gg.set_seed(p.seed)
+    if pick == 'rows':
+        gg.p.noise_row.copy_(p.noise_row)
+        gg.p.inv_t.copy_(p.inv_t)
+    hlast, past = layout.first_pass(model.MVLBert, feat, gg.kc, gg.vc, gg.new_ids[:, 1:2])
+    gg.reset(past)
     gg.hlast.copy_(hlast)
-    done = 0
-    for t in range(max_length - 1):
-        gg.graph.replay()                        # token t, then the forward that prepares token t+1
-        done = t + 1
-        if _sync_due(eos, done) and 0 in gg.alive[done - SYNC_EVERY:done].tolist():
-            break
-    else:
-        gg.head()                                # last token: head only
-        done = max_length
+    done = _replay(gg.graph, gg.alive, gg.head, max_length, eos)
     n_out, n_scores = _cut(gg.alive[:done].tolist() if eos is not None else [], done)
-    ids = gg.ids[:, :n_out].clone()
-    scores = gg.scores[:, :n_scores].t().reshape(-1).clone() if n_scores > 0 else torch.empty(0, device=feat.device)
-    return ids, scores
+    if not flat:
+        return gg.ids[:, :n_out].clone(), gg.scores[:, :n_out].clone()
+    return gg.ids[:, :n_out].clone(), gg.scores[:, :n_scores].t().reshape(-1).clone() if n_scores > 0 else torch.empty(0, device=feat.device)
 
 
-def _greedy_eager_loop(model, ar, feat, max_length, pad, eos, mask_id, cd, pick, seed, temperature, top_k, top_p, rules=(1.0, 0, 0),
-                       prompt=None):
+def _eager_loop(model, ar, feat, layout, pick, p, rules, max_length, pad, eos, mask_id, cd, flat):
+    """The token loop launch by launch over R = B * layout.S rows: ``(ids [R, n_out], scores)``, cut where the reference's
+    per-token check would have stopped (``_cut``).  ``flat``: the scores of all but the column that ended the decode, concatenated
+    column after column (``greedy_search``); else [R, n_out], a score per id (``sample_many``)."""
     mv = model.MVLBert
-    B, n_img, _ = feat.shape
-    dev = feat.device
-    head = model.MLM_head_seq2seq
-    V = head.predictions.decoder.out_features
-    row_shift = None if prompt is None else prompt[1]
-    kc, vc = _alloc_cache(model, B, n_img, max_length + (0 if prompt is None else prompt[0].shape[1] - 1), cd, dev)
-    mask_col = torch.full((B, 1), mask_id, dtype=torch.int64, device=dev)
+    dev, R = feat.device, feat.shape[0] * layout.S
+    attn = layout.attn(layout.table)
+    kc, vc = _alloc_cache(model, R, feat.shape[1], max_length + layout.p_max, cd, dev)
+    mask_col = torch.full((R, 1), mask_id, dtype=torch.int64, device=dev)
     lr = None
     if rules != (1.0, 0, 0):          # the history the plan reads: the id matrix as the graph keeps it, and the column count
-        hist = torch.zeros((B, max_length), dtype=torch.int64, device=dev)
-        lr = ops.LogitRules(V, *rules, eos, hist, torch.zeros(1, dtype=torch.int64, device=dev))
-
-    def next_from(hlast):
-        t2, W, bias = _head(model, ar, hlast.contiguous())
-        tag = SAMPLE_TAG0 + len(ids_cols)
-        if lr is not None:            # the fused picks in row chunks of 64 (pick: 'gemm_argmax' | 'gemm_sample' | 'filtered')
-            lr.plan()
-            parts = []
-            for r0 in range(0, B, 64):
-                a, rs = t2[r0:r0 + 64], lr.struct(r0)
-                if pick == 'gemm_argmax':
-                    parts.append(ops.gemm_argmax(a, W, bias, rules=rs))
-                elif pick == 'gemm_sample':
-                    parts.append(ops.gemm_sample(a, W, bias, seed, tag, temperature, rules=rs))
-                else:
-                    parts.append(ops.gemm_sample_filtered(a, W, bias, seed, tag, temperature, top_k, top_p, row0=r0, rules=rs))
-            return torch.cat([a for a, _ in parts]), torch.cat([b for _, b in parts])
-        if pick == 'gemm_argmax':
-            return ops.gemm_argmax(t2, W, bias)
-        if pick == 'filtered':        # stand-alone filtered pick; rows beyond 64 in chunks, the noise indexed by the batch row
-            parts = [ops.gemm_sample_filtered(t2[r0:r0 + 64], W, bias, seed, tag, temperature, top_k, top_p, row0=r0)
-                     for r0 in range(0, t2.shape[0], 64)]
-            return torch.cat([a for a, _ in parts]), torch.cat([b for _, b in parts])
-        if pick == 'gemm_sample':     # the pick of the graph loop, stand-alone: same seed, tag and column -> same tokens
-            return ops.gemm_sample(t2, W, bias, seed, tag, temperature)
-        logits, _ = head._logits(ar, t2)
-        if pick == 'argmax':
-            nxt = ops.argmax(logits, V)
-            return nxt, logits[:, :V].float().gather(1, nxt[:, None]).squeeze(1)
-        probs = ops.softmax_rows(logits, V)
-        nxt = torch.multinomial(probs, num_samples=1, replacement=True).squeeze(1)
-        return nxt, torch.log(probs.gather(1, nxt[:, None])).squeeze(1)
-
-    if prompt is None:
-        hlast, past = _step0(mv, feat, mask_col, kc, vc)
-    else:
-        hlast, past = _prefill(mv, feat, prompt[0], prompt[2], kc, vc)
-    unfinished = torch.ones(B, dtype=torch.int64, device=dev)
+        V = model.MLM_head_seq2seq.predictions.decoder.out_features
+        lr = ops.LogitRules(V, *rules, eos, torch.zeros((R, max_length), dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int64, device=dev))
+    hlast, past = layout.first_pass(mv, feat, kc, vc, mask_col)
+    unfinished = torch.ones(R, dtype=torch.int64, device=dev)
     ids_cols, scores, alive, flags = [], [], [], []        # `alive`: device scalars, one per column; `flags`: what was read back
     while len(ids_cols) < max_length:
-        nxt, score = next_from(hlast)
+        t2, W, bias = _head(model, ar, hlast.contiguous())
+        nxt, score = _pick(pick, t2, W, bias, p, SAMPLE_TAG0 + len(ids_cols), lr)
         if eos is not None:
             nxt = nxt * unfinished + pad * (1 - unfinished)
             unfinished = unfinished * (nxt != eos).long()
@@ -591,22 +700,21 @@ def _greedy_eager_loop(model, ar, feat, max_length, pad, eos, mask_id, cd, pick,
             lr.ids[:, len(ids_cols)] = nxt
             lr.col.fill_(len(ids_cols) + 1)
         ids_cols.append(nxt[:, None])
+        scores.append(score if flat else score[:, None])
         if _sync_due(eos, len(ids_cols), last=max_length):
             block = torch.stack(alive[-SYNC_EVERY:]).tolist()
             flags[len(alive) - len(block):] = block
             if 0 in block:
                 break
-        scores.append(score)
         if len(ids_cols) >= max_length:
             break
         new_ids = torch.cat([nxt[:, None], mask_col], dim=1)              # [last_token, MASK] (model.py:587-591)
-        hlast = _step2(mv, ar, new_ids, past, kc, vc, cd, row_shift=row_shift)
+        hlast = _step2(mv, ar, new_ids, past, kc, vc, cd, **attn)
         past += 1                                                         # drop the [MASK] slot (model.py:890-894)
     n_out, n_scores = _cut(flags, len(ids_cols))
-    ids_cols, scores = ids_cols[:n_out], scores[:n_scores]
-    input_ids = torch.cat(ids_cols, dim=-1) if ids_cols else None
-    token_scores = torch.cat(scores, dim=-1) if scores else torch.empty(0, device=dev)
-    return input_ids, token_scores
+    scores = scores[:n_scores] if flat else scores[:n_out]
+    return (torch.cat(ids_cols[:n_out], dim=-1) if ids_cols else None,
+            torch.cat(scores, dim=-1) if scores else torch.empty(0, device=dev))
 
 
 @torch.no_grad()
@@ -659,15 +767,18 @@ def greedy_search(model, image_feature, learning_strategy='unilm', sample_mode='
     if sample_mode == 'greedy':
         seed, temperature = 0, 1.0               # unused by the greedy pick, and no part of its graph's key
     elif pick != 'multinomial':
-        if not float(temperature) > 0.0:
-            raise ValueError("temperature must be positive")
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
-    search = _greedy_graph_loop if loop == 'graph' else _greedy_eager_loop
-    if input_ids is None:
-        return search(model, ar, feat, max_length, pad, eos, mask_id, cd, pick, seed, temperature, top_k, top_p, rules)
-    prompt = prompt_tables(input_ids.to(feat.device), lens, mask_id)
-    return search(model, ar, feat, max_length, pad, eos, mask_id, cd, pick, seed, temperature, top_k, top_p, rules, prompt)
+        _check_temperature(temperature)
+        seed = _default_seed() if seed is None else seed
+    head = model.MLM_head_seq2seq
+    p = SimpleNamespace(seed=seed, temperature=temperature, top_k=top_k, top_p=top_p, V=V, logits=lambda t2: head._logits(ar, t2)[0])
+    layout = _Plain() if input_ids is None else _Prompted(*prompt_tables(input_ids.to(feat.device), lens, mask_id))
+    if loop == 'eager':
+        return _eager_loop(model, ar, feat, layout, pick, p, rules, max_length, pad, eos, mask_id, cd, True)
+    # the fused head of the graph holds the whole batch in one 64-row tile; a filter only swaps the sampled head's entry point
+    pick = 'gemm_argmax' if sample_mode == 'greedy' else 'filtered' if (top_k, top_p) != (0, 1.0) else 'gemm_sample'
+    slot, key = _graph_slot_key(feat.shape[0], feat.shape[1], max_length, cd, pad, eos, mask_id, ar.flat.data_ptr(), feat.device.index,
+                                sample_mode, temperature, top_k, top_p, rules, None if input_ids is None else layout.p_max)
+    return _graph_loop((_GreedyGraph, slot, key), model, feat, layout, pick, p, rules, max_length, pad, eos, mask_id, cd, True)
 
 
 # ----------------------------------------------------------------------------- K sampled reports per image in one pass
@@ -685,130 +796,6 @@ def multi_sample_tables(B, num_samples, include_greedy, temperature, max_length)
     inv_t = torch.where(sampled, torch.tensor(1.0 / float(temperature), dtype=torch.float64), torch.tensor(1.0, dtype=torch.float64))
     slot = s.to(torch.int32)[:, None].expand(B * S, max_length).contiguous()
     return noise_row, inv_t.to(torch.float32), slot
-
-
-class _MultiSampleGraph(_DecodeGraph):
-    """``_GreedyGraph`` over R = B * S rows that share the image prefix of their image: body = the per-row pick
-    (``mvlt_gemm_pick_rows_step``: greedy and sampled rows in one head, any R) + the 2-token cached forward through
-    ``mvlt_attn_cached_beam`` with the constant slot table -- one stream, no parallel branches, static buffers only.  What a row
-    does (greedy or sampled, its noise row, its temperature) is DATA in two device tables the loop fills per call, so one capture
-    serves every num_samples / include_greedy / temperature with the same S."""
-
-    def __init__(self, model, key, B, S, n_img, max_length, cd, pad, eos, mask_id, rules=(1.0, 0, 0)):
-        dev = next(model.parameters()).device
-        H = model.config.hidden_size
-        R = B * S
-        self.key, self.model, self.cd, self.graph, self.S = key, model, cd, None, S
-        self.prefix = n_img + 2
-        self.kc, self.vc = _alloc_cache(model, R, n_img, max_length, cd, dev)
-        self.past = torch.full((1,), self.prefix - 1, dtype=torch.int32, device=dev)      # a valid position for the warm-up pass, which really runs
-        self.col = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.new_ids = torch.full((R, 2), mask_id, dtype=torch.int64, device=dev)
-        self.hfull = torch.zeros((R * 2, H), dtype=cd, device=dev)
-        self.hlast = self.hfull.view(R, 2, H)[:, 1]
-        self.unfinished = torch.ones(R, dtype=torch.int64, device=dev)
-        self.ids = torch.zeros((R, max_length), dtype=torch.int64, device=dev)
-        self.scores = torch.zeros((R, max_length), dtype=torch.float32, device=dev)
-        self.alive = torch.ones(max_length, dtype=torch.int64, device=dev)
-        self.seed = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.noise_row = torch.full((R,), -1, dtype=torch.int32, device=dev)
-        self.inv_t = torch.ones(R, dtype=torch.float32, device=dev)
-        self.slot = torch.zeros((R, max_length), dtype=torch.int32, device=dev)
-        st = self.state = L.MvltSampleState()
-        st.seed, st.tag0, st.inv_temperature = self.seed.data_ptr(), SAMPLE_TAG0, 1.0
-        st.unfinished, st.eos_id, st.pad_id, st.has_eos = self.unfinished.data_ptr(), (eos if eos is not None else -1), pad, int(eos is not None)
-        st.col, st.past = self.col.data_ptr(), self.past.data_ptr()
-        st.ids, st.ld_ids, st.scores, st.ld_scores = self.ids.data_ptr(), max_length, self.scores.data_ptr(), max_length
-        st.alive, st.new_ids, st.ld_new, st.ticket = self.alive.data_ptr(), self.new_ids.data_ptr(), 2, self.ticket.data_ptr()
-        self.rules = None
-        if rules != (1.0, 0, 0):
-            V = model.MLM_head_seq2seq.predictions.decoder.out_features
-            self.rules = ops.LogitRules(V, *rules, eos, self.ids, self.col)
-
-    def head(self):
-        t2, W, bias = _head(self.model, Arena.of(self.model, self.cd), self.hlast)
-        rules = None
-        if self.rules is not None:
-            self.rules.plan()
-            rules = self.rules.struct()
-        ops.gemm_pick_rows_step(t2, W, bias, self.state, self.noise_row, self.inv_t, rules=rules)
-
-    def body(self):
-        self.head()
-        _step2(self.model.MVLBert, Arena.of(self.model, self.cd), self.new_ids, self.past, self.kc, self.vc, self.cd, out_last=self.hfull,
-               beam=(self.S, self.prefix, self.slot))
-
-
-def _multi_graph_loop(model, ar, feat, S, tables, max_length, pad, eos, mask_id, cd, seed, rules):
-    B, n_img, _ = feat.shape
-    key = (B, S, n_img, max_length, cd, pad, eos, mask_id, ar.flat.data_ptr(), feat.device.index)
-    if rules != (1.0, 0, 0):
-        key = key + ("rules",) + tuple(rules)
-    gg = _MultiSampleGraph.of(model, "_mvlt_multi_sample_graph", key, B, S, n_img, max_length, cd, pad, eos, mask_id, rules)
-    gg.seed.fill_(ops.s64(int(seed) & ((1 << 64) - 1)))
-    for dst, src in zip((gg.noise_row, gg.inv_t, gg.slot), tables):
-        dst.copy_(src)
-    hlast, past = _step0(model.MVLBert, feat, gg.new_ids[::S, 1:2].contiguous(), gg.kc, gg.vc, stride=S)
-    gg.past.fill_(past - 1); gg.col.zero_(); gg.unfinished.fill_(1); gg.alive.zero_(); gg.ticket.zero_()
-    gg.hlast.copy_(hlast.repeat_interleave(S, 0))
-    done = 0
-    for t in range(max_length - 1):
-        gg.graph.replay()
-        done = t + 1
-        if _sync_due(eos, done) and 0 in gg.alive[done - SYNC_EVERY:done].tolist():
-            break
-    else:
-        gg.head()                                # last token: head only
-        done = max_length
-    n_out, _ = _cut(gg.alive[:done].tolist() if eos is not None else [], done)
-    return gg.ids[:, :n_out].clone(), gg.scores[:, :n_out].clone()
-
-
-def _multi_eager_loop(model, ar, feat, S, tables, max_length, pad, eos, mask_id, cd, seed, rules):
-    mv = model.MVLBert
-    B, n_img, _ = feat.shape
-    dev, R = feat.device, B * S
-    V = model.MLM_head_seq2seq.predictions.decoder.out_features
-    noise_row, inv_t, slot = (t.to(dev) for t in tables)
-    kc, vc = _alloc_cache(model, R, n_img, max_length, cd, dev)
-    mask_col = torch.full((R, 1), mask_id, dtype=torch.int64, device=dev)
-    lr = None
-    if rules != (1.0, 0, 0):
-        lr = ops.LogitRules(V, *rules, eos, torch.zeros((R, max_length), dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int64, device=dev))
-    hlast, past = _step0(mv, feat, mask_col[:B], kc, vc, stride=S)
-    prefix = past
-    hlast = hlast.repeat_interleave(S, 0)
-    unfinished = torch.ones(R, dtype=torch.int64, device=dev)
-    ids_cols, scores, alive, flags = [], [], [], []
-    while len(ids_cols) < max_length:
-        t2, W, bias = _head(model, ar, hlast.contiguous())
-        rs = None
-        if lr is not None:
-            lr.plan()
-            rs = lr.struct()
-        nxt, score = ops.gemm_pick_rows(t2, W, bias, noise_row, inv_t, seed, SAMPLE_TAG0 + len(ids_cols), rules=rs)
-        if eos is not None:
-            nxt = nxt * unfinished + pad * (1 - unfinished)
-            unfinished = unfinished * (nxt != eos).long()
-            alive.append(unfinished.max())
-        if lr is not None:
-            lr.ids[:, len(ids_cols)] = nxt
-            lr.col.fill_(len(ids_cols) + 1)
-        ids_cols.append(nxt[:, None])
-        scores.append(score[:, None])
-        if _sync_due(eos, len(ids_cols), last=max_length):
-            block = torch.stack(alive[-SYNC_EVERY:]).tolist()
-            flags[len(alive) - len(block):] = block
-            if 0 in block:
-                break
-        if len(ids_cols) >= max_length:
-            break
-        new_ids = torch.cat([nxt[:, None], mask_col], dim=1)
-        hlast = _step2(mv, ar, new_ids, past, kc, vc, cd, beam=(S, prefix, slot))
-        past += 1
-    n_out, _ = _cut(flags, len(ids_cols))
-    return torch.cat(ids_cols[:n_out], dim=-1), torch.cat(scores[:n_out], dim=-1)
 
 
 @torch.no_grad()
@@ -833,8 +820,7 @@ def sample_many(model, image_feature, num_samples, include_greedy=True, seed=Non
     if int(num_samples) != num_samples or num_samples < 1:
         raise ValueError("num_samples must be a positive integer")
     num_samples = int(num_samples)
-    if not float(temperature) > 0.0 or float(temperature) == float("inf"):
-        raise ValueError("temperature must be positive")
+    _check_temperature(temperature, finite=True)
     rules = check_logit_rules(repetition_penalty, no_repeat_ngram_size, min_length)
     cfg = model.config
     if cfg.hidden_size // cfg.num_attention_heads != 64:
@@ -847,11 +833,19 @@ def sample_many(model, image_feature, num_samples, include_greedy=True, seed=Non
     S = num_samples + int(bool(include_greedy))
     if B * S * V >= 2 ** 32:
         raise ValueError(f"{B * S} rows of {V} logits: the noise index rows * V must stay below 2^32")
-    if seed is None:
-        seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+    seed = _default_seed() if seed is None else seed
+    graph_on, n_img = _env()[0], feat.shape[1]
     tables = multi_sample_tables(B, num_samples, include_greedy, temperature, max_length)
-    loop = _multi_graph_loop if _env()[0] else _multi_eager_loop
-    ids, scores = loop(model, ar, feat, S, tables, max_length, pad, eos, mask_id, cd, seed, rules)
+    if not graph_on:          # the eager loop reads the tables where they lie; a graph copies them into its own
+        tables = [t.to(feat.device) for t in tables]
+    # what a row does is data (noise_row, inv_t): the state's own temperature stays 1, and no part of the graph's key
+    p = SimpleNamespace(seed=seed, temperature=1.0, top_k=0, top_p=1.0, noise_row=tables[0], inv_t=tables[1])
+    layout = _SharedPrefix(S, n_img + 2, tables[2])
+    if graph_on:
+        slot, key = _graph_slot_key(B, n_img, max_length, cd, pad, eos, mask_id, ar.flat.data_ptr(), feat.device.index, rules=rules, S=S)
+        ids, scores = _graph_loop((_MultiSampleGraph, slot, key), model, feat, layout, 'rows', p, rules, max_length, pad, eos, mask_id, cd, False)
+    else:
+        ids, scores = _eager_loop(model, ar, feat, layout, 'rows', p, rules, max_length, pad, eos, mask_id, cd, False)
     n = ids.shape[1]
     return ids.view(B, S, n), scores.view(B, S, n)
 
@@ -1087,13 +1081,8 @@ def _beam_device(model, ar, feat, nb, max_length, pad, eos, mask_id, cd, graph_o
     def all_done(t):          # after the beam step of token t
         return _sync_due(eos, t + 1) and 0 in st.alive[t + 1 - SYNC_EVERY:t + 1].tolist()
 
-    if graph_on:
-        for t in range(max_length - 1):
-            bg.graph.replay()                    # the beam step of token t, then the forward and candidates of token t + 1
-            if all_done(t):
-                break
-        else:
-            bg.step()                            # last token: the beam step only
+    if graph_on:          # a replay: the beam step of token t, then the forward and candidates of token t + 1; last token: the beam step only
+        _replay(bg.graph, st.alive, bg.step, max_length, eos)
         if cand_log is not None:
             cand_log.copy_(bg.log)
     else:

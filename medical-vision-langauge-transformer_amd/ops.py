@@ -380,6 +380,14 @@ class LogitRules:
                     "mvlt_decode_rules_plan")
 
 
+def _head_call(name, args, rules):
+    """Launch the head entry point ``name`` on ``args`` and the stream -- with ``rules`` (a prepared ``L.MvltLogitRules``) its
+    ``_rules`` form, which takes the same arguments with the rules ahead of the stream."""
+    if rules is not None:
+        name, args = name + "_rules", args + (C.byref(rules),)
+    L.check(getattr(L.lib(), name)(*args, _stream()), name)
+
+
 def gemm_argmax(A, W, bias=None, rules=None):
     """argmax_n (A @ W^T + bias) and its value, without materialising the logits (greedy decoding).
     A: [M <= 64, K], W: [N, K] -> (int64 [M], f32 [M]).  ``rules`` (here and in the five head functions below): a prepared
@@ -390,10 +398,7 @@ def gemm_argmax(A, W, bias=None, rules=None):
     pi = torch.empty((M, nblk), dtype=torch.int32, device=A.device)
     idx = torch.empty(M, dtype=torch.int64, device=A.device)
     val = torch.empty(M, dtype=torch.float32, device=A.device)
-    if rules is not None:
-        L.check(L.lib().mvlt_gemm_argmax_rules(C.byref(p), _p(pv), _p(pi), _p(idx), _p(val), C.byref(rules), _stream()), "mvlt_gemm_argmax_rules")
-        return idx, val
-    L.check(L.lib().mvlt_gemm_argmax(C.byref(p), _p(pv), _p(pi), _p(idx), _p(val), _stream()), "mvlt_gemm_argmax")
+    _head_call("mvlt_gemm_argmax", (C.byref(p), _p(pv), _p(pi), _p(idx), _p(val)), rules)
     return idx, val
 
 
@@ -403,11 +408,7 @@ def gemm_argmax_greedy(A, W, bias, state, rules=None):
     # A.stride(0), not _ld(A): the head reads the [MASK] rows in place, at row stride 2 H of the step's hidden states
     p, M, N = _head_gemm(A, W, bias, lda=A.stride(0))
     pv, pi = _head_parts(1, M, N, A.device)
-    if rules is not None:
-        L.check(L.lib().mvlt_gemm_argmax_greedy_rules(C.byref(p), _p(pv), _p(pi), C.byref(state), C.byref(rules), _stream()),
-                "mvlt_gemm_argmax_greedy_rules")
-        return
-    L.check(L.lib().mvlt_gemm_argmax_greedy(C.byref(p), _p(pv), _p(pi), C.byref(state), _stream()), "mvlt_gemm_argmax_greedy")
+    _head_call("mvlt_gemm_argmax_greedy", (C.byref(p), _p(pv), _p(pi), C.byref(state)), rules)
 
 
 def _sample_parts(M, N, device):
@@ -423,12 +424,8 @@ def gemm_sample(A, W, bias, seed, tag, temperature=1.0, rules=None):
     pv, pi = _sample_parts(M, N, A.device)
     idx = torch.empty(M, dtype=torch.int64, device=A.device)
     lp = torch.empty(M, dtype=torch.float32, device=A.device)
-    if rules is not None:
-        L.check(L.lib().mvlt_gemm_sample_rules(C.byref(p), _p(pv), _p(pi), _p(idx), _p(lp), int(seed) & ((1 << 64) - 1), int(tag) & 0xFFFFFFFF,
-                                               1.0 / float(temperature), C.byref(rules), _stream()), "mvlt_gemm_sample_rules")
-        return idx, lp
-    L.check(L.lib().mvlt_gemm_sample(C.byref(p), _p(pv), _p(pi), _p(idx), _p(lp), int(seed) & ((1 << 64) - 1), int(tag) & 0xFFFFFFFF,
-                                     1.0 / float(temperature), _stream()), "mvlt_gemm_sample")
+    _head_call("mvlt_gemm_sample", (C.byref(p), _p(pv), _p(pi), _p(idx), _p(lp), int(seed) & ((1 << 64) - 1), int(tag) & 0xFFFFFFFF,
+                                    1.0 / float(temperature)), rules)
     return idx, lp
 
 
@@ -437,11 +434,7 @@ def gemm_sample_step(A, W, bias, state, rules=None):
     ``state``: a prepared ``L.MvltSampleState`` (decode._GreedyGraph, mode 'sample')."""
     p, M, N = _head_gemm(A, W, bias)
     pv, pi = _sample_parts(M, N, A.device)
-    if rules is not None:
-        L.check(L.lib().mvlt_gemm_sample_step_rules(C.byref(p), _p(pv), _p(pi), C.byref(state), C.byref(rules), _stream()),
-                "mvlt_gemm_sample_step_rules")
-        return
-    L.check(L.lib().mvlt_gemm_sample_step(C.byref(p), _p(pv), _p(pi), C.byref(state), _stream()), "mvlt_gemm_sample_step")
+    _head_call("mvlt_gemm_sample_step", (C.byref(p), _p(pv), _p(pi), C.byref(state)), rules)
 
 
 def _pick_rows_tables(M, noise_row, inv_t):
@@ -462,12 +455,7 @@ def gemm_pick_rows(A, W, bias, noise_row, inv_t, seed, tag, rules=None):
     idx = torch.empty(M, dtype=torch.int64, device=A.device)
     lp = torch.empty(M, dtype=torch.float32, device=A.device)
     seed, tag = int(seed) & ((1 << 64) - 1), int(tag) & 0xFFFFFFFF
-    if rules is not None:
-        L.check(L.lib().mvlt_gemm_pick_rows_rules(C.byref(p), _p(pv), _p(pi), _p(noise_row), _p(inv_t), _p(idx), _p(lp), seed, tag,
-                                                  C.byref(rules), _stream()), "mvlt_gemm_pick_rows_rules")
-        return idx, lp
-    L.check(L.lib().mvlt_gemm_pick_rows(C.byref(p), _p(pv), _p(pi), _p(noise_row), _p(inv_t), _p(idx), _p(lp), seed, tag, _stream()),
-            "mvlt_gemm_pick_rows")
+    _head_call("mvlt_gemm_pick_rows", (C.byref(p), _p(pv), _p(pi), _p(noise_row), _p(inv_t), _p(idx), _p(lp), seed, tag), rules)
     return idx, lp
 
 
@@ -478,12 +466,7 @@ def gemm_pick_rows_step(A, W, bias, state, noise_row, inv_t, rules=None):
     p, M, N = _head_gemm(A, W, bias)
     _pick_rows_tables(M, noise_row, inv_t)
     pv, pi = _sample_parts(M, N, A.device)
-    if rules is not None:
-        L.check(L.lib().mvlt_gemm_pick_rows_step_rules(C.byref(p), _p(pv), _p(pi), _p(noise_row), _p(inv_t), C.byref(state), C.byref(rules),
-                                                       _stream()), "mvlt_gemm_pick_rows_step_rules")
-        return
-    L.check(L.lib().mvlt_gemm_pick_rows_step(C.byref(p), _p(pv), _p(pi), _p(noise_row), _p(inv_t), C.byref(state), _stream()),
-            "mvlt_gemm_pick_rows_step")
+    _head_call("mvlt_gemm_pick_rows_step", (C.byref(p), _p(pv), _p(pi), _p(noise_row), _p(inv_t), C.byref(state)), rules)
 
 
 def check_sample_filter(top_k, top_p):
@@ -526,13 +509,8 @@ def gemm_sample_filtered(A, W, bias, seed, tag, temperature=1.0, top_k=0, top_p=
     f, _ = _sample_filter(M, N, A.device, top_k, top_p, row0)
     idx = torch.empty(M, dtype=torch.int64, device=A.device)
     lp = torch.empty(M, dtype=torch.float32, device=A.device)
-    if rules is not None:
-        L.check(L.lib().mvlt_gemm_sample_filtered_rules(C.byref(p), _p(pv), _p(pi), C.byref(f), _p(idx), _p(lp), int(seed) & ((1 << 64) - 1),
-                                                        int(tag) & 0xFFFFFFFF, 1.0 / float(temperature), C.byref(rules), _stream()),
-                "mvlt_gemm_sample_filtered_rules")
-        return idx, lp
-    L.check(L.lib().mvlt_gemm_sample_filtered(C.byref(p), _p(pv), _p(pi), C.byref(f), _p(idx), _p(lp), int(seed) & ((1 << 64) - 1),
-                                              int(tag) & 0xFFFFFFFF, 1.0 / float(temperature), _stream()), "mvlt_gemm_sample_filtered")
+    _head_call("mvlt_gemm_sample_filtered", (C.byref(p), _p(pv), _p(pi), C.byref(f), _p(idx), _p(lp), int(seed) & ((1 << 64) - 1),
+                                             int(tag) & 0xFFFFFFFF, 1.0 / float(temperature)), rules)
     return idx, lp
 
 
@@ -543,12 +521,7 @@ def gemm_sample_filtered_step(A, W, bias, state, top_k=0, top_p=1.0, rules=None)
     p, M, N = _head_gemm(A, W, bias)
     pv, pi = _sample_parts(M, N, A.device)
     f, _ = _sample_filter(M, N, A.device, top_k, top_p, 0)
-    if rules is not None:
-        L.check(L.lib().mvlt_gemm_sample_filtered_step_rules(C.byref(p), _p(pv), _p(pi), C.byref(f), C.byref(state), C.byref(rules), _stream()),
-                "mvlt_gemm_sample_filtered_step_rules")
-        return
-    L.check(L.lib().mvlt_gemm_sample_filtered_step(C.byref(p), _p(pv), _p(pi), C.byref(f), C.byref(state), _stream()),
-            "mvlt_gemm_sample_filtered_step")
+    _head_call("mvlt_gemm_sample_filtered_step", (C.byref(p), _p(pv), _p(pi), C.byref(f), C.byref(state)), rules)
 
 
 BEAM_MAX_BEAMS, BEAM_MAX_CAND = 8, 16          # limits of mvlt_gemm_beam_candidates (csrc/skinny.hip BEAM_MAXB / BEAM_MAXC)
@@ -610,10 +583,7 @@ def gemm_beam_candidates(A, W, bias, beam_scores, num_beams, n_cand, want_lse=Fa
     c = L.MvltBeamCand()
     c.num_beams, c.n_cand, c.beam_scores, c.x, c.ldx = int(num_beams), int(n_cand), _p(beam_scores), _p(ws), ldx
     c.cand_score, c.cand_beam, c.cand_tok, c.lse = _p(out[0]), _p(out[1]), _p(out[2]), (_p(lse) if want_lse else None)
-    if rules is not None:
-        L.check(L.lib().mvlt_gemm_beam_candidates_rules(C.byref(p), C.byref(c), C.byref(rules), _stream()), "mvlt_gemm_beam_candidates_rules")
-        return out, lse
-    L.check(L.lib().mvlt_gemm_beam_candidates(C.byref(p), C.byref(c), _stream()), "mvlt_gemm_beam_candidates")
+    _head_call("mvlt_gemm_beam_candidates", (C.byref(p), C.byref(c)), rules)
     return out, lse
 
 

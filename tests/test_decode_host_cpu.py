@@ -102,6 +102,33 @@ def test_greedy_route_refusals(graph_on):
         decode._greedy_route('beam', 3, False, graph_on)
 
 
+# (B, n_img, max_length, cd, pad, eos, mask_id, address of the weights, device index): what every graph key starts from
+_KEY = (3, 49, 8, "bf16", 0, None, 103, 1234, 0)
+_RULES = (1.2, 3, 10)
+
+
+@pytest.mark.parametrize("kw, slot, key", [
+    (dict(), "_mvlt_greedy_graph", (3, 49, 8, "bf16", 0, None, 103, 1234, 0)),
+    (dict(mode='sample', temperature=0.8), "_mvlt_sample_graph", (3, 49, 8, "bf16", 0, None, 103, 1234, 0, 'sample', 0.8)),
+    (dict(mode='sample', temperature=2, top_k=5, top_p=0.9), "_mvlt_sample_graph", (3, 49, 8, "bf16", 0, None, 103, 1234, 0, 'sample', 2.0, 5, 0.9)),
+    (dict(rules=_RULES), "_mvlt_greedy_graph", (3, 49, 8, "bf16", 0, None, 103, 1234, 0, "rules", 1.2, 3, 10)),
+    (dict(p_max=6), "_mvlt_prompt_graph", (3, 49, 8, "bf16", 0, None, 103, 1234, 0, "prompt", 66)),
+    (dict(p_max=0), "_mvlt_prompt_graph", (3, 49, 8, "bf16", 0, None, 103, 1234, 0, "prompt", 60)),          # an empty prompt is a prompt
+    (dict(mode='sample', temperature=0.8, p_max=6), "_mvlt_prompt_sample_graph", (3, 49, 8, "bf16", 0, None, 103, 1234, 0, 'sample', 0.8, "prompt", 66)),
+    (dict(mode='sample', temperature=0.8, top_k=5, top_p=0.9, rules=_RULES, p_max=6), "_mvlt_prompt_sample_graph",
+     (3, 49, 8, "bf16", 0, None, 103, 1234, 0, 'sample', 0.8, 5, 0.9, "rules", 1.2, 3, 10, "prompt", 66)),
+    (dict(S=3), "_mvlt_multi_sample_graph", (3, 3, 49, 8, "bf16", 0, None, 103, 1234, 0)),
+    (dict(S=3, rules=_RULES), "_mvlt_multi_sample_graph", (3, 3, 49, 8, "bf16", 0, None, 103, 1234, 0, "rules", 1.2, 3, 10)),
+], ids=["greedy", "sampled", "sampled+filter", "greedy+rules", "prompted", "empty-prompt", "prompted-sampled", "prompted-all", "multi", "multi+rules"])
+def test_graph_slot_and_key(kw, slot, key):
+    """The slot names and the key tuples as the loops built them before they shared ``_graph_slot_key``, written out: the key
+    starts with B, a prompted key ends with the cache capacity (n_img + 2 + p_max + max_length + 1), the multi-sample key holds S
+    and neither the temperature nor the split of S."""
+    got = decode._graph_slot_key(*_KEY, **kw)
+    assert got == (slot, key)
+    assert type(got[1][10]) is float if kw.get("mode") == 'sample' else True          # float(temperature): 2 and 2.0 are one key
+
+
 @pytest.mark.parametrize("args, route", [
     # (num_beams, head_dim, max_length, fused_on, device_scorer, device_on)
     ((8, 64, 150, True, False, False), 'fused'),
